@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path (BASELINE.json: Mray/s at fixed spp).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, renders W warm-up frames, times K frames, and prints the JSON line; its rates, counts and
+roofline come from the timed frames. --full adds the figures that take runs of their own (cpu_baseline; the --exclusive-spp pass).
+--dump-outputs DIR writes the film of the last timed frame (rank 0, after the reduce), as a caller of
+PathIntegrator.Render receives it: DIR/film.npy [H, W, 31] and DIR/weight.npy [H, W], float32. Above 64 MB in all,
+the files hold a fixed, seeded sample of the pixels instead ([n, 31], [n], and pixel_index.npy: y * W + x).
 
 Workload (config.workload): killeroo-simple.pbrt, 700x700, PathIntegrator maxdepth 5,
 Halton, box filter, SampledSpectrum-31, 1024 spp -- BASELINE.json configs[1]. A *step*
@@ -27,8 +33,8 @@ The JSON line also carries
                  By default one sub-renderer (one stream) renders the frame, so each launch has
                  the GPU to itself while it is timed; --streams K runs K sub-renderers
                  concurrently (a few % more throughput, but then a timed launch shares the CUs).
-  cpu_baseline:  the CPU oracle (a port of the reference algorithm, oracle/) timed on the
-                 host cores on a bounded sample of the same workload (rank 0, N = 1 only)
+  cpu_baseline:  --full only: the CPU oracle (a port of the reference algorithm, oracle/) timed
+                 on the host cores on a bounded sample of the same workload (rank 0, N = 1 only)
 """
 import argparse
 import json
@@ -40,7 +46,24 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (6.29 measured)
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak 8.0 TB/s (6.29 measured)
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs writes at most this much (a 700x700 film is 62.7 MB)
+
+
+def dump_outputs(out_dir, film32):
+    """film32: the host copy of the [H, W, 32] device film (31 bins + filter-weight sum). Writes what
+    PathIntegrator.Render returns for it, or a seeded sample of its pixels when that exceeds the budget."""
+    import numpy as np
+    h, w, c = film32.shape
+    arrays = {"film": film32[..., :31], "weight": film32[..., 31]}
+    if film32.nbytes > DUMP_BUDGET_BYTES - 4096:   # (4096: the .npy headers)
+        n = (DUMP_BUDGET_BYTES - 4096) // (film32.itemsize * c + 8)
+        pix = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+        flat = film32.reshape(h * w, c)[pix]
+        arrays = {"film": flat[:, :31], "weight": flat[:, 31], "pixel_index": pix.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
 
 
 def main():
@@ -54,13 +77,17 @@ def main():
                     help="render the seeded procedural scene of tools/make_procedural_scene.py with this many "
                          "triangles instead of --scene (BASELINE configs 4/5 stand-in)")
     ap.add_argument("--pool", type=int, default=0, help="resident path slots (0 = library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: cpu_baseline and the --exclusive-spp pass")
     ap.add_argument("--cpu-samples", type=int, default=80_000_000,
-                    help="camera samples the CPU oracle renders for cpu_baseline (0 = skip)")
+                    help="with --full: camera samples the CPU oracle renders for cpu_baseline (0 = skip)")
     ap.add_argument("--streams", type=int, default=0,
                     help="concurrent sub-renderers (0 = MIPT_STREAMS from the environment, else 1)")
     ap.add_argument("--exclusive-spp", type=int, default=0,
-                    help="with --streams > 1: spp of an extra one-stream pass that times the traversal kernel alone (0 = skip)")
+                    help="with --full and --streams > 1: spp of an extra one-stream pass that times the traversal kernel alone (0 = skip)")
     ap.add_argument("--dump-film", default=None, help="rank 0 saves the (reduced) film of the last step as .npy: [H, W, 32] = 31 bins + weight")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the last timed step's film as DIR/film.npy and DIR/weight.npy (float32, at most 64 MB)")
     ap.add_argument("--pmc-traffic", type=float, default=None,
                     help="HBM bytes per k_extend launch from a separate rocprofv3 --pmc pass")
     a = ap.parse_args()
@@ -153,6 +180,8 @@ def main():
     ptdist.barrier()
     torch.cuda.synchronize()
     dt = ptdist.max_over_ranks(time.perf_counter() - t0)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, film32.cpu().numpy())
 
     per_rank = frame.per_rank_timings()
     sums = ptdist.sum_over_ranks([acc[k] for k in keys])
@@ -209,7 +238,7 @@ def main():
 
     # The same kernel with the GPU to itself: one untimed 64-spp pass through a one-stream
     # integrator (rank 0, N = 1), so the concurrent-launch figure above has its reference.
-    if rank == 0 and world == 1 and a.exclusive_spp > 0 and roofline["concurrent_streams"] > 1:
+    if a.full and rank == 0 and world == 1 and a.exclusive_spp > 0 and roofline["concurrent_streams"] > 1:
         os.environ["MIPT_STREAMS"] = "1"
         solo = pt.CreatePathIntegrator(scene, local_rank)
         os.environ["MIPT_STREAMS"] = str(roofline["concurrent_streams"])
@@ -226,7 +255,7 @@ def main():
         del solo
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and a.cpu_samples > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_samples > 0:
         import oracle_binding as ob
         cores = os.cpu_count() or 1
         try:

@@ -24,7 +24,7 @@ open('/tmp/matzoo.pbrt', 'w').write(st.material_zoo(res=700, spp=256, depth=6))"
   OUT=gpurun_out/${TAG}_$w
   mkdir -p $OUT
   echo "== $w: bench"
-  timeout -k 10 500 python bench.py --steps 3 --warmup 1 $ARGS > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --steps 3 --warmup 1 $ARGS > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
   tools/profile_round.sh $OUT $ARGS > $OUT/profile.log 2>&1 || { echo "profile failed"; tail -5 $OUT/profile.log; exit 1; }
   python - <<PY
 import json
