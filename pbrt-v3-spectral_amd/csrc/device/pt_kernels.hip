@@ -34,9 +34,6 @@
 #include <type_traits>
 #include "d_sampling.h"
 #include "d_texture.h"
-#ifdef MIPT_SORT_EXPERIMENT
-#include <hipcub/hipcub.hpp>
-#endif
 
 using namespace dpt;
 
@@ -237,19 +234,7 @@ struct DevCounters {
     DevCursor shadeCount[MAX_CLASSES];  // entries in shading queue c
     DevCursor travNext[3];              // work cursors of the persistent traversal kernels (extend/shadow/mis)
     DevCursor ovfCount[3];              // entries in Pool::ovfQ (extend/shadow/mis)
-#ifdef MIPT_EXP_STAMPS
-    unsigned long long phase[24];       // diagnostic build: wave-cycles of k_shade between its stamps (s_memtime), summed over waves
-    unsigned long long phaseWaves;
-#endif
 };
-#ifdef MIPT_EXP_STAMPS
-// In-kernel stamps (MI355X_MICROARCH.md, "in-kernel stamps"): one wave-uniform s_memtime per phase boundary, the difference
-// to the previous stamp added to phase[k]. Diagnostic build only (tools/shade_experiments.sh stamps).
-#define STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-        if (stampOn && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) atomicAdd(&ctr->phase[k], t_ - stampLast); stampLast = t_; } while (0)
-#else
-#define STAMP(k) do {} while (0)
-#endif
 constexpr size_t ITER_CLEAR_BYTES = sizeof(DevCursor) * (5 + MAX_CLASSES + 3 + 3);
 DEV DevStats &Stats(DevCounters *ctr) { return ctr->stats[blockIdx.x & (STAT_STRIPES - 1)]; }
 
@@ -839,12 +824,8 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
             bool needPop = false, got = false, finished = false;
             int tkChild = 0, tkMeta = 0;
             if (walking) {
-#ifdef MIPT_NO_FAST_BOX
-                got = OpenNode<W, !ANY>(s.wnodes, st.cur, r, tMax, spill, lane, st.sp, &tkChild, &tkMeta, nodeCount);
-#else
                 if (__any(r.slow)) got = OpenNode<W, !ANY, false>(s.wnodes, st.cur, r, tMax, spill, lane, st.sp, &tkChild, &tkMeta, nodeCount);
                 else got = OpenNode<W, !ANY, W == 4>(s.wnodes, st.cur, r, tMax, spill, lane, st.sp, &tkChild, &tkMeta, nodeCount);
-#endif
                 needPop = !got;
                 st.cur = -1;
             }
@@ -1499,10 +1480,6 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
     const int nBands = s.nBands;
     unsigned wantBits = 0, restartBits = 0, contBits = 0, gotBits = 0;   // bit ch: state of this thread's slot in chunk ch
     unsigned finBits = 0, finZeroBits = 0, finInBBits = 0;
-#ifdef MIPT_EXP_STAMPS
-    unsigned long long stampLast = __builtin_amdgcn_s_memtime();
-    const bool stampOn = (blockIdx.x % 61u) == 0u;
-#endif
     // ---------------------------------------------------------------- pass 1: film flush
     // The finished paths are a third of the block's slots: they are listed first (in slot order: neighbours in the list are
     // samples of the same pixel more often than not) and flushed by all lanes together, as the refill below -- chunk by
@@ -1560,7 +1537,6 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
     }
     __syncthreads();
     const unsigned totFin = sTotFin;
-    STAMP(19);
 #pragma unroll 1
     for (unsigned round = 0; round < (totFin + BLOCK - 1) / BLOCK; ++round) {
         const unsigned fi = round * BLOCK + threadIdx.x;
@@ -1643,7 +1619,6 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
         // in flight)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        STAMP(20);
         {
             const int half = lane >> 5, bin = lane & 31;
             const int filterTableSize = 16;
@@ -1697,11 +1672,7 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
                         else if (!zero) acc += (sL[(waveBase + p) * 33 + bin] * 1.f) * fw;      // contribSum += L * sampleWeight * fw
                     }
                 }
-#ifdef MIPT_EXP_NOFILMATOMIC
-                if (tgt >= 0 && acc == 12345.678f) atomicAdd(film + (size_t)tgt * 32 + bin, acc);   // (timing experiment)
-#else
                 if (tgt >= 0 && acc != 0.f) atomicAdd(film + (size_t)tgt * 32 + bin, acc);   // (x + 0 == x: a black bin is not sent)
-#endif
             }
             // Wider footprints (other filters, samples on a pixel border): one row update per sample and pixel reached.
             unsigned long long mask = __ballot(fin && !restart && myTarget < 0);
@@ -1736,7 +1707,6 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // the rows are read before the next round overwrites them
         __builtin_amdgcn_wave_barrier();
-        STAMP(21);
     }
     __syncthreads();
     // ---------------------------------------------------------------- pass 2: refill
@@ -1830,7 +1800,6 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
             sGot[e] = 1;
         } else if (want) pool.I(I_FLAGS, slot) = 0;   // stays free (its finished path has been flushed)
     }
-    STAMP(22);
     __syncthreads();
 #pragma unroll 1
     for (int ch = 0; ch < SLOT_CHUNKS; ++ch) {
@@ -1862,7 +1831,6 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
         if (isPrim) pool.extQ[sPrimBase + sPrim[ch][wave] + (unsigned)__popcll(pm & ltMask)] = slot;
         if (isCont) pool.extQ[pool.n - 1 - (sContBase + sCont[ch][wave] + (unsigned)__popcll(cm & ltMask))] = slot;
     }
-    STAMP(23);
     CountAdd(&Stats(ctr).cameraRays, cam);
     CountAdd(&Stats(ctr).badSamples, bad);
 }
@@ -1894,20 +1862,6 @@ DEV void ShadingToWorld(const mi_instance &in, TriShading *ts) {
 // Build the SurfaceInteraction of a recorded hit.
 DEV void HitInteraction(const DScene &s, int prim, const V3 &ro, const V3 &rd, float b0, float b1, float b2, SurfaceInteraction *si) {
     const mi_prim p = s.prims[prim];
-#ifdef MIPT_EXP_FLATTRI
-    if (p.shape >= 0) {   // (timing experiment: the interaction from the pre-gathered leaf record, no indexed N / UV gather)
-        const float4 a = s.primTri[3 * prim], b = s.primTri[3 * prim + 1], c = s.primTri[3 * prim + 2];
-        const V3 p0(a.x, a.y, a.z), p1(b.x, b.y, b.z), p2(c.x, c.y, c.z);
-        si->p = b0 * p0 + b1 * p1 + b2 * p2;
-        si->pError = gammaf(7) * V3(absf(b0 * p0.x) + absf(b1 * p1.x) + absf(b2 * p2.x), absf(b0 * p0.y) + absf(b1 * p1.y) + absf(b2 * p2.y), absf(b0 * p0.z) + absf(b1 * p1.z) + absf(b2 * p2.z));
-        si->wo = Normalize(-rd);
-        V3 n = Normalize(Cross(p0 - p2, p1 - p2)), du, dv;
-        CoordinateSystem(n, &du, &dv);
-        n = Faceforward(n, si->wo);
-        si->n = n; si->shN = n; si->dpdu = du; si->shDpdu = du;
-        return;
-    }
-#endif
     if (p.shape >= 0) TriInteraction(s, p.shape, b0, b1, b2, rd, si);
     else { float t; SphereInteraction(s.spheres[~p.shape], ro, rd, kInfinity, si, &t); }
 }
@@ -1971,18 +1925,6 @@ DEV void StoreSpectrumLines(SpectrumTile &t, const Pool &pool, int spectrum, uin
 #ifndef MIPT_SHADE_WAVES_PER_EU
 #define MIPT_SHADE_WAVES_PER_EU 4
 #endif
-// Timing experiments (tools/shade_experiments.sh; the films of these builds are wrong, only k_shade's time is read):
-// MIPT_EXP_NOSPEC evaluates one quad of every spectral pass instead of eight, MIPT_EXP_NOSTORE leaves the spectra unstored.
-#ifdef MIPT_EXP_NOSPEC
-constexpr int EXP_NQ = 1;
-#else
-constexpr int EXP_NQ = NQ;
-#endif
-#ifdef MIPT_EXP_NOSTORE
-#define EXP_STORE(x) false
-#else
-#define EXP_STORE(x) (x)
-#endif
 
 template <int NL, unsigned TM>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT_SHADE_WAVES_PER_EU, 8))) k_shade(DScene s, Pool pool, DevCounters *ctr, unsigned classes) {
@@ -1997,29 +1939,12 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
     }
     const uint32_t qi = blk * BLOCK + threadIdx.x;
     constexpr bool HALTON_ONLY = (TM & TM_SAMPLERS) == 0;
-#ifdef MIPT_NO_SIMPLE_SPECTRA
-    constexpr bool SIMPLE_SPECTRA = false;
-#else
     constexpr bool SIMPLE_SPECTRA = NL <= 2 && TM_SIMPLE_KINDS(TM);   // the straight-line spectral passes (d_bsdf.h, SimpleLobes)
-#endif
     // more than two lobes: f is summed lobe by lobe into the lane's column of the spectrum tile (AccumulateF, d_bsdf.h)
-#ifdef MIPT_NO_ACCUMULATE
-    constexpr bool ACCUM = false;
-#else
     constexpr bool ACCUM = NL > 2 || (TM & TM_TEXTURED) != 0;   // (image-textured lobes too: their spectra quad by quad, TexturedQuad)
-#endif
-#ifdef MIPT_FUSED_HALTON
-    constexpr bool FUSED_HALTON = HALTON_ONLY;
-#else
-    constexpr bool FUSED_HALTON = false;   // (measured: the side-by-side digit loops cost 29 more scratch instructions and 7 % of the kernel)
-#endif
     __shared__ SpectrumTile tile;
     auto rdTile = [&](int c) -> float4 { return tile.q[c][threadIdx.x]; };
     auto wrTile = [&](int c, const float4 &v) { tile.q[c][threadIdx.x] = v; };
-#ifdef MIPT_EXP_STAMPS
-    unsigned long long stampLast = __builtin_amdgcn_s_memtime();
-    const bool stampOn = (blockIdx.x % 61u) == 0u;   // (one block in 61 reports: the atomics of every wave would be the kernel)
-#endif
     unsigned totalPaths = 0, pathLen = 0, zeroNow = 0;
     bool wantShadow = false, wantMis = false;
     uint32_t slot = 0;
@@ -2040,7 +1965,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
         const bool emitCheck = bounces == 0 || (flags & F_SPECULAR);
         const bool needIsect = found && (bounces < s.maxDepth || emitCheck);
         const bool needRay = needIsect || (!found && emitCheck && TM_LIGHT(TM, MI_LIGHT_INFINITE) && s.nInfiniteLights > 0);
-        STAMP(1);
         float4 ray0 = make_float4(0.f, 0.f, 0.f, 0.f), ray1 = make_float4(0.f, 0.f, 1.f, 1.f);
         if (needRay) { ray0 = pool.R(R_RAY0, slot); ray1 = pool.R(R_RAY1, slot); }
         V3 ro(ray0.x, ray0.y, ray0.z), rd(ray1.x, ray1.y, ray1.z);
@@ -2055,7 +1979,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
         }
         if (needIsect) { const float4 hr = pool.R(R_HIT, slot); HitInteraction(s, prim, roS, rdS, hr.y, hr.z, hr.w, &isect); }
-        STAMP(2);
         SurfaceInteraction isectObj;
         if constexpr ((TM & TM_INSTANCES) != 0) {
             if (inst >= 0) { isectObj = isect; InteractionToWorld(s.instances[inst], &isect); }
@@ -2103,7 +2026,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             }
         }
         if (!found || bounces >= s.maxDepth) finished = true;
-        STAMP(3);
         int newFlags = 0;
         if (!finished && s.prims[prim].material < 0) {  // interface without BSDF: continue through it, path.cpp:108-113
             Ray r = SpawnRay(isect, rd);
@@ -2249,7 +2171,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             if constexpr (!HALTON_ONLY) { if (IsPixelSampler(s)) ps.dim = pool.I(I_DIM, slot); }
             const int *__restrict__ pixelPlane = pool.i + (size_t)I_PIXEL * pool.n, *__restrict__ samplePlane = pool.i + (size_t)I_SAMPLE * pool.n;
             const int nonSpec = MI_BSDF_ALL & ~MI_BSDF_SPECULAR;
-        STAMP(4);
             // ---- direct lighting: UniformSampleOneLight + EstimateDirect, integrator.cpp:85-215
             if (NumComponents(fr, nonSpec) > 0) {
                 ++totalPaths;
@@ -2257,26 +2178,20 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                 if (s.nLights > 0) {
                     const uint32_t di = LightDistribIndex(s, isect.p);
                     float selPdf;
-                    // the five dimensions of the estimate (light choice, light sample, BSDF sample): with the Halton sampler
-                    // -- values are a pure function of (index, dimension) -- their digit loops run side by side
+                    // the five dimensions of the estimate (light choice, light sample, BSDF sample)
                     float u5[5];
-                    if constexpr (FUSED_HALTON) { ScrambledDimensionsFused<5>(s.primes, s.primeSums, s.perms, s.primeMagic, ps.index, ps.dim, u5); ps.dim += 1; }
-                    else u5[0] = Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot);
+                    u5[0] = Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot);
                     const int lightNum = SampleDiscrete(s.ldFunc + (size_t)di * s.nLights, s.ldCdf + (size_t)di * (s.nLights + 1),
                                                         s.ldFuncInt[di], (int)s.nLights, u5[0], &selPdf);
                     if (selPdf != 0) {
-                        if constexpr (FUSED_HALTON) ps.dim += 4;
-                        else {   // uLight = Get2D(), uScattering = Get2D() (integrator.cpp:100-101)
-                            Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[1], &u5[2]);
-                            Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[3], &u5[4]);
-                        }
+                        // uLight = Get2D(), uScattering = Get2D() (integrator.cpp:100-101)
+                        Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[1], &u5[2]);
+                        Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[3], &u5[4]);
                         const float uL0 = u5[1], uL1 = u5[2], uS0 = u5[3], uS1 = u5[4];
-        STAMP(5);
                         const mi_light &light = s.lights[lightNum];
                         const bool selIsOne = (selPdf == 1.f);  // x / 1 == x: skip the division
                         const Divisor selDiv = MakeDivisor(selPdf);
                         const LightSample ls = SampleLi<TM>(s, light, isect, uL0, uL1);
-        STAMP(6);
                         const float lightPdf = ls.pdf;
                         if (lightPdf > 0 && !ls.black) {
                             BSDFEvalT<NL> ev;
@@ -2285,7 +2200,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                             auto fQuad = [&](int c) -> float4 { if constexpr (ACCUM) return rdTile(c); else return EvalQuad<NL, TM>(ev, mat->bxdf, c, ltp); };
                             const float absdot = AbsDot(ls.wi, isect.shN);
                             const float scatteringPdf = BSDF_Pdf<TM>(fr, isect.wo, ls.wi, nonSpec);
-        STAMP(7);
                             const bool delta = IsDeltaLight(light);
                             float weight = 1.f;
                             if (!delta) { float pf = 1 * lightPdf, pg = 1 * scatteringPdf; weight = (pf * pf) / (pf * pf + pg * pg); }
@@ -2350,18 +2264,17 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                     return true;
                                 };
 #pragma unroll 1
-                                for (int c = 0; c < EXP_NQ; ++c)
+                                for (int c = 0; c < NQ; ++c)
                                     if (!quad(c, std::false_type{})) quad(c, std::true_type{});
                                 fNonBlack |= accF != 0u; liNonBlack |= accLi != 0u; nzAny |= accNz != 0u;
                             } else {
 #pragma unroll 1
-                                for (int c = 0; c < EXP_NQ; ++c) neeQuad(c, fQuad(c), LiQuad<TM>(s, light, ls, c));
+                                for (int c = 0; c < NQ; ++c) neeQuad(c, fQuad(c), LiQuad<TM>(s, light, ls, c));
                             }
                             // the tile holds L + contribution, the candidate (F_CAND): only one whose shadow ray will be traced
                             // is ever read
                             const bool traced = fNonBlack && liNonBlack;
-        STAMP(8);
-                            StoreSpectrumLines(tile, pool, LOtherPlane(flags), slot, EXP_STORE(traced));
+                            StoreSpectrumLines(tile, pool, LOtherPlane(flags), slot, traced);
                             if (traced) newFlags |= F_CAND | (nzAny ? F_NEE_NZ : 0);
                             if (traced) {  // the shadow ray is traced iff f != 0 (integrator.cpp:138-150)
                                 Ray sr = SpawnRayTo(isect, ls.pLight);
@@ -2369,7 +2282,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                 pool.R(R_SH1, slot) = make_float4(sr.d.y, sr.d.z, 0.f, 0.f);
                                 newFlags |= F_SHADOW;
                             }
-        STAMP(9);
                         }
                         if (!IsDeltaLight(light)) {  // BSDF sampling with MIS, integrator.cpp:167-213
                             V3 wi;
@@ -2379,7 +2291,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                             V3 wiLocal;
                             const bool ok = BSDF_Sample_f<NL, TM, !ACCUM>(fr, isect.wo, &wi, uS0, uS1, &sPdf, nonSpec, &sampledType, &ev, &wiLocal);
                             auto fQuad = [&](int c) -> float4 { if constexpr (ACCUM) return rdTile(c); else return EvalQuad<NL, TM>(ev, mat->bxdf, c, ltp); };
-        STAMP(10);
                             if (ok && sPdf > 0) {
                                 const float absdot = AbsDot(wi, isect.shN);
                                 // Pdf_Li has no side effect: evaluate it before knowing whether f is black
@@ -2428,7 +2339,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                         else AccumulateFLocal<NL, TM>(fr, fr.WorldToLocal(isect.wo), wiLocal, Dot(wi, fr.ng) * Dot(isect.wo, fr.ng) > 0, nonSpec, ltp, rdTile, wrTile);
                                     }
                                 }
-        STAMP(11);
                                 auto darkQuad = [&](int c, const float4 &fq) {   // (only: is f black? -- that decides whether the ray exists)
 #pragma unroll
                                     for (int k = 0; k < 4; ++k)
@@ -2475,7 +2385,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                             return true;
                                         };
 #pragma unroll 1
-                                        for (int c = 0; c < EXP_NQ; ++c)
+                                        for (int c = 0; c < NQ; ++c)
                                             if (!quad(c, std::false_type{})) quad(c, std::true_type{});
                                     }
                                     if (go && !dark) {
@@ -2508,22 +2418,21 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                             return true;
                                         };
 #pragma unroll 1
-                                        for (int c = 0; c < EXP_NQ; ++c)
+                                        for (int c = 0; c < NQ; ++c)
                                             if (!quad(c, std::false_type{})) quad(c, std::true_type{});
                                     }
                                     fNonBlack |= accF != 0u;
                                 } else {
                                     if (dark) {
 #pragma unroll 1
-                                        for (int c = 0; c < EXP_NQ; ++c) darkQuad(c, fQuad(c));
+                                        for (int c = 0; c < NQ; ++c) darkQuad(c, fQuad(c));
                                     }
                                     if (go && !dark) {
 #pragma unroll 1
-                                        for (int c = 0; c < EXP_NQ; ++c) misQuad(c, fQuad(c), isEnvLight ? zero4 : LoadSpec4(light.L, c));
+                                        for (int c = 0; c < NQ; ++c) misQuad(c, fQuad(c), isEnvLight ? zero4 : LoadSpec4(light.L, c));
                                     }
                                 }
-                                StoreSpectrumLines(tile, pool, Q_LMIS, slot, EXP_STORE(go && !dark));   // whole 128-B lines, as for the light sample
-        STAMP(12);
+                                StoreSpectrumLines(tile, pool, Q_LMIS, slot, go && !dark);   // whole 128-B lines, as for the light sample
                                 if (fNonBlack && go) {
                                     if (dark) newFlags |= F_MIS_DARK;
                                     pool.R(R_MI0, slot) = make_float4(mr.o.x, mr.o.y, mr.o.z, mr.d.x);
@@ -2542,8 +2451,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                 float pdf = 0;
                 int sflags = 0;
                 float u2[2];
-                if constexpr (FUSED_HALTON) { ScrambledDimensionsFused<2>(s.primes, s.primeSums, s.perms, s.primeMagic, ps.index, ps.dim, u2); ps.dim += 2; }
-                else Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u2[0], &u2[1]);
+                Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u2[0], &u2[1]);
                 const float u0 = u2[0], u1 = u2[1];
                 BSDFEvalT<NL> ev;
                 V3 wiLocal;
@@ -2555,7 +2463,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                     }
                 }
                 auto fQuad = [&](int c) -> float4 { if constexpr (ACCUM) return rdTile(c); else return EvalQuad<NL, TM>(ev, mat->bxdf, c, ltp); };
-        STAMP(13);
                 bool fNonBlack = false;
                 if (ok && pdf != 0.f) {
                     const float absdot = AbsDot(wi, isect.shN);
@@ -2615,16 +2522,15 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                             return true;
                         };
 #pragma unroll 1
-                        for (int c = 0; c < EXP_NQ; ++c)
+                        for (int c = 0; c < NQ; ++c)
                             if (!quad(c, std::false_type{})) quad(c, std::true_type{});
                         fNonBlack |= accF != 0u;
                     } else {
 #pragma unroll 1
-                        for (int c = 0; c < EXP_NQ; ++c) contQuad(c, fQuad(c));
+                        for (int c = 0; c < NQ; ++c) contQuad(c, fQuad(c));
                     }
                     // (the new throughput is stored below, once it is known that a later vertex will read it)
                     bool killed = false;
-        STAMP(14);
                     if (fNonBlack) {
                         // Russian roulette, path.cpp:176-184
                         if (maxRR < s.rrThreshold && bounces > 3) {
@@ -2647,8 +2553,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                     // light (after a specular bounce, path.cpp:91-101); a path that ends here, or whose last ray only
                     // has to be traced, leaves none behind
                     const bool needBeta = fNonBlack && !killed && (bounces + 1 < s.maxDepth || (sflags & MI_BSDF_SPECULAR));
-                    StoreSpectrumLines(tile, pool, Q_BETA, slot, EXP_STORE(needBeta));
-        STAMP(15);
+                    StoreSpectrumLines(tile, pool, Q_BETA, slot, needBeta);
                     if (needBeta) betaWritten = true;
                     if (fNonBlack) {
                         if (killed) finished = true;
@@ -2662,7 +2567,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                 }
                 if (!(ok && pdf != 0.f && fNonBlack)) finished = true;
             }
-        STAMP(16);
             dimNow = ps.dim;
             if constexpr (!HALTON_ONLY) { if (IsPixelSampler(s)) { pool.I(I_DIM, slot) = ps.dim; dimNow = 0; } }
             if (!HALTON_ONLY && s.samplerType >= MI_SAMPLER_RANDOM) {   // the stream moves on with the path
@@ -2688,7 +2592,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             pool.I(I_FLAGS, slot) = StateWord(newFlags, finished ? bounces : bounces + 1, dimNow);
         }
     }
-    STAMP(17);
     __shared__ unsigned sAppend[10];
     unsigned posS, posM;
     BlockReserve2(&ctr->shadowCount.v, wantShadow, &ctr->misCount.v, wantMis, sAppend, &posS, &posM);
@@ -2704,10 +2607,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             if (packed >> 16) atomicAdd(&st8.pathLengthSum, (unsigned long long)(packed >> 16));
         }
     }
-    STAMP(18);
-#ifdef MIPT_EXP_STAMPS
-    if (stampOn && (threadIdx.x & 63) == 0) atomicAdd(&ctr->phaseWaves, 1ull);
-#endif
 }
 
 #if MIPT_HAS_MAIN
@@ -2977,28 +2876,45 @@ __global__ void k_film_split(const float *film32, float *filmSum, float *weightS
 }
 #endif   // MIPT_HAS_MAIN
 
-// The k_shade instances LaunchShade uses, in three groups of about equal compile time.
+// Every k_shade instance, in launch order (LaunchShade): X(part, NL, TM). The part is the MIPT_PART that compiles the
+// instance (three groups of about equal compile time); without MIPT_PART the kernel table instantiates them all.
 constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_TEXTURED;
-#define MIPT_SHADE_GROUP_1(X) X(MI_MAX_BXDFS, TM_ALL) X(4, TM_GENERIC) X(2, TM_GENERIC) \
-    X(2, TM_DIFFUSE | TM_LIGHTS_ALL) X(2, TM_DIFFUSE | TM_LIGHTS_NO_ENV) X(2, TM_DIFFUSE | TM_LIGHTS_ALL | TM_SAMPLERS) X(2, TM_DIFFUSE | TM_LIGHTS_NO_ENV | TM_SAMPLERS)
-#define MIPT_SHADE_GROUP_2(X) X(MI_MAX_BXDFS, TM_FULL) X(2, TM_ALL) X(2, TM_FULL) \
-    X(2, TM_PLASTIC | TM_LIGHTS_ALL) X(2, TM_PLASTIC | TM_LIGHTS_NO_ENV) X(2, TM_PLASTIC | TM_LIGHTS_ALL | TM_SAMPLERS) X(2, TM_PLASTIC | TM_LIGHTS_NO_ENV | TM_SAMPLERS)
-#define MIPT_SHADE_GROUP_3(X) X(MI_MAX_BXDFS, TM_GENERIC) X(4, TM_FULL) X(2, TM_GLASS | TM_LIGHTS_ALL | TM_SAMPLERS) X(4, TM_UBER | TM_LIGHTS_ALL | TM_SAMPLERS) X(MI_MAX_BXDFS, TM_DISNEY | TM_LIGHTS_ALL | TM_SAMPLERS) \
-    X(2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) X(2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS)
-#define MIPT_SHADE_DEFINE(NL_, TM_) template __global__ void k_shade<NL_, (TM_)>(DScene, Pool, DevCounters *, unsigned);
-#define MIPT_SHADE_EXTERN(NL_, TM_) extern template __global__ void k_shade<NL_, (TM_)>(DScene, Pool, DevCounters *, unsigned);
-// MIPT_HOT_ONLY (tools/shade_experiments.sh): a one-translation-unit build with the matte and plastic Halton instances
-// alone -- what the killeroo / Cornell-without-glass frames launch -- for quick same-box A/B runs of k_shade experiments.
-#ifdef MIPT_PART
-#if MIPT_PART == 0
-MIPT_SHADE_GROUP_1(MIPT_SHADE_EXTERN) MIPT_SHADE_GROUP_2(MIPT_SHADE_EXTERN) MIPT_SHADE_GROUP_3(MIPT_SHADE_EXTERN)
-#elif MIPT_PART == 1
-MIPT_SHADE_GROUP_1(MIPT_SHADE_DEFINE)
-#elif MIPT_PART == 2
-MIPT_SHADE_GROUP_2(MIPT_SHADE_DEFINE)
+#define MIPT_SHADE_INSTANCES(X) \
+    X(1, 2, TM_DIFFUSE | TM_LIGHTS_ALL) X(1, 2, TM_DIFFUSE | TM_LIGHTS_NO_ENV) \
+    X(1, 2, TM_DIFFUSE | TM_LIGHTS_ALL | TM_SAMPLERS) X(1, 2, TM_DIFFUSE | TM_LIGHTS_NO_ENV | TM_SAMPLERS) \
+    X(2, 2, TM_PLASTIC | TM_LIGHTS_ALL) X(2, 2, TM_PLASTIC | TM_LIGHTS_NO_ENV) \
+    X(2, 2, TM_PLASTIC | TM_LIGHTS_ALL | TM_SAMPLERS) X(2, 2, TM_PLASTIC | TM_LIGHTS_NO_ENV | TM_SAMPLERS) \
+    X(1, 2, TM_GENERIC) \
+    X(3, 2, TM_GLASS | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(3, 4, TM_UBER | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(3, MI_MAX_BXDFS, TM_DISNEY | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(1, 4, TM_GENERIC) \
+    X(3, 4, TM_FULL) \
+    X(3, MI_MAX_BXDFS, TM_GENERIC) \
+    X(3, 2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(3, 2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(2, 2, TM_FULL) \
+    X(2, MI_MAX_BXDFS, TM_FULL) \
+    X(2, 2, TM_ALL) \
+    X(1, MI_MAX_BXDFS, TM_ALL)
+#ifdef MIPT_PART   // each part defines its own instances and declares the others
+#if MIPT_PART == 1
+#define MIPT_SHADE_IN_1
 #else
-MIPT_SHADE_GROUP_3(MIPT_SHADE_DEFINE)
+#define MIPT_SHADE_IN_1 extern
 #endif
+#if MIPT_PART == 2
+#define MIPT_SHADE_IN_2
+#else
+#define MIPT_SHADE_IN_2 extern
+#endif
+#if MIPT_PART == 3
+#define MIPT_SHADE_IN_3
+#else
+#define MIPT_SHADE_IN_3 extern
+#endif
+#define MIPT_SHADE_INSTANCE(P_, NL_, TM_) MIPT_SHADE_IN_##P_ template __global__ void k_shade<NL_, (TM_)>(DScene, Pool, DevCounters *, unsigned);
+MIPT_SHADE_INSTANCES(MIPT_SHADE_INSTANCE)
 #endif
 
 }  // namespace dptk
@@ -3021,6 +2937,52 @@ struct SubRenderer {
     DevCounters result{};
 };
 
+// The k_shade instances by their index in MIPT_SHADE_INSTANCES.
+struct ShadeInstance {
+    int nl;
+    unsigned tm;
+    void (*kernel)(DScene, Pool, DevCounters *, unsigned);
+};
+#define MIPT_SHADE_ENTRY(P_, NL_, TM_) {NL_, (TM_), k_shade<NL_, (TM_)>},
+static const ShadeInstance kShadeInstances[] = {MIPT_SHADE_INSTANCES(MIPT_SHADE_ENTRY)};
+#undef MIPT_SHADE_ENTRY
+constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstances[0]);
+
+// The k_shade instance of a shading class (an index into kShadeInstances, -1: none) from its lobe types and Fresnel kinds
+// `types` and its longest lobe list `lobes` (the overflow class counts MI_MAX_BXDFS lobes; the miss class has neither
+// types nor lobes, so it takes the matte instance). `hot`: the lights and sampler bits of the scene's variant of the matte
+// and plastic instances.
+static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot) {
+    auto pick = [](int nl, unsigned tm) {
+        for (int i = 0; i < N_SHADE_INSTANCES; ++i)
+            if (kShadeInstances[i].nl == nl && kShadeInstances[i].tm == tm) return i;
+        return -1;
+    };
+    auto fits = [types](unsigned tm) { return (types & ~tm) == 0; };
+    // (textured "disney" classes go to the eight-lobe instance whatever their lobe count: only that one reads the rules
+    // that form their spectra from the colour -- LobeTexT::rules, d_bsdf.h)
+    const unsigned disneyBits = (1u << MI_BXDF_DISNEY_DIFFUSE) | (1u << MI_BXDF_DISNEY_FAKE_SS) | (1u << MI_BXDF_DISNEY_RETRO) |
+                                (1u << MI_BXDF_DISNEY_SHEEN) | (1u << MI_BXDF_DISNEY_CLEARCOAT) | (1u << (16 + MI_FRESNEL_DISNEY));
+    const bool textured = (types & TM_TEXTURED) != 0, texturedDisney = textured && (types & disneyBits) != 0;
+    // scenes with object instances: the two fully general instances, by lobe count
+    if (instanced) return pick(lobes > 2 || texturedDisney ? MI_MAX_BXDFS : 2, TM_ALL);
+    // the other instances are compiled for a subset of the lobe types and take the classes that fit
+    if (!textured && lobes <= 2) {
+        if (fits(TM_DIFFUSE)) return pick(2, TM_DIFFUSE | hot);
+        if (fits(TM_PLASTIC)) return pick(2, TM_PLASTIC | hot);
+        if (fits(TM_GLASS)) return pick(2, TM_GLASS | TM_LIGHTS_ALL | TM_SAMPLERS);
+        return pick(2, TM_GENERIC);
+    }
+    if (!textured) {   // the lobe sets of "uber" and "disney": instances without the rest of the BxDF code
+        if (lobes <= 4 && fits(TM_UBER)) return pick(4, TM_UBER | TM_LIGHTS_ALL | TM_SAMPLERS);
+        if (fits(TM_DISNEY)) return pick(MI_MAX_BXDFS, TM_DISNEY | TM_LIGHTS_ALL | TM_SAMPLERS);
+        return pick(lobes <= 4 ? 4 : MI_MAX_BXDFS, TM_GENERIC);
+    }
+    if (lobes <= 2 && fits(TM_DIFFUSE | TM_TEXTURED)) return pick(2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS);
+    if (lobes <= 2 && fits(TM_PLASTIC | TM_TEXTURED)) return pick(2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS);
+    return pick(texturedDisney ? MI_MAX_BXDFS : lobes <= 2 ? 2 : lobes <= 4 ? 4 : MI_MAX_BXDFS, TM_FULL);
+}
+
 struct mi_pt {
     int device = 0;
     DScene scene{};
@@ -3032,19 +2994,13 @@ struct mi_pt {
     long long spp = 0;
     std::vector<SubRenderer> subs;
     double lastSeconds[8] = {0};
-    unsigned smallClasses = 1u << MISS_CLASS, largeClasses = 0;  // shading classes with <= 2 lobes / with more
     uint32_t nTextures = 0;
     std::vector<int> textureTypes;
     bool hasAlphaMasks = false;      // picks the traversal kernels compiled with the alpha-mask test
     bool hasInstances = false;       // ... and with the TransformedPrimitive code (those carry the alpha-mask test too)
     bool hasQuadrics = false;        // the scene has spheres: the quadric lists of rays can overflow (k_resolve_overflow is launched)
     bool hasInfiniteLight = false;   // picks the kernels compiled with the environment-light code
-    unsigned diffuseClasses = 0, plasticClasses = 0;
-    unsigned texturedDiffuse = 0, texturedPlastic = 0;           // textured classes that fit the diffuse / plastic lobe masks
-    unsigned glassClasses = 0;                                   // untextured glass / mirror lobe sets (<= 2 lobes)
-    unsigned uberClasses = 0, disneyClasses = 0;                 // untextured uber-like (<= 4 lobes) and Disney lobe sets: instances of their own
-    unsigned mediumClasses = 0, texturedMedium = 0;              // 3- and 4-lobe classes (uber with Kr / Kt, translucent): 4-lobe instances
-    unsigned texturedSmall = 0, texturedLarge = 0;               // classes of image-textured materials (taken out of small / largeClasses)              // subsets of smallClasses run by the lobe-specialised kernels
+    unsigned shadeClasses[N_SHADE_INSTANCES] = {0};   // per k_shade instance: the shading classes it runs (ShadeInstanceOf)
     int numCUs = 256;
 };
 
@@ -3406,10 +3362,11 @@ int mi_pt_create(const mi_scene_desc *d, int device_ordinal, mi_pt **out) {
     }
     // shading classes: one per distinct lobe-type list, in order of first appearance
     std::vector<int> matClass(d->n_materials, 0);
+    int classLobes[MAX_CLASSES] = {0};       // per class: the longest lobe list
+    unsigned classTypes[MAX_CLASSES] = {0};  // per class: lobe types (bits 0..15) and fresnel kinds (bits 16..) present
+    s.classMask = 1u << MISS_CLASS;
     {
         std::vector<std::vector<int>> signatures;
-        int classLobes[MAX_CLASSES] = {0};       // per class: the longest lobe list
-        unsigned classTypes[MAX_CLASSES] = {0};  // per class: lobe types (bits 0..15) and fresnel kinds (bits 16..) present
         for (uint32_t i = 0; i < d->n_materials; ++i) {
             const mi_material &m = d->materials[i];
             std::vector<int> sig;
@@ -3419,7 +3376,7 @@ int mi_pt_create(const mi_scene_desc *d, int device_ordinal, mi_pt **out) {
             while (c < signatures.size() && signatures[c] != sig) ++c;
             if (c == signatures.size()) signatures.push_back(sig);
             matClass[i] = (int)std::min<size_t>(c, MISS_CLASS - 1);
-            ((m.n_bxdfs > 2 || c >= (size_t)MISS_CLASS - 1) ? pt->largeClasses : pt->smallClasses) |= 1u << matClass[i];
+            s.classMask |= 1u << matClass[i];
             classLobes[matClass[i]] = std::max(classLobes[matClass[i]], (c >= (size_t)MISS_CLASS - 1) ? MI_MAX_BXDFS : (int)m.n_bxdfs);
             for (int j = 0; j < m.n_bxdfs; ++j) {
                 classTypes[matClass[i]] |= (1u << m.bxdf[j].type) | (1u << (16 + m.bxdf[j].fresnel));
@@ -3427,53 +3384,6 @@ int mi_pt_create(const mi_scene_desc *d, int device_ordinal, mi_pt **out) {
             }
             if (m.textured) classTypes[matClass[i]] |= TM_TEXTURED;
         }
-        pt->smallClasses &= ~pt->largeClasses;   // a shared overflow class runs the 8-lobe kernel
-        pt->smallClasses |= 1u << MISS_CLASS;
-        s.classMask = pt->smallClasses | pt->largeClasses;
-        // kernels compiled for a subset of the lobe types take the classes that fit
-        pt->diffuseClasses = 1u << MISS_CLASS;
-        for (int c = 0; c < MISS_CLASS; ++c) {
-            if (!((pt->smallClasses >> c) & 1u)) continue;
-            if ((classTypes[c] & ~TM_DIFFUSE) == 0) pt->diffuseClasses |= 1u << c;
-            else if ((classTypes[c] & ~TM_PLASTIC) == 0) pt->plasticClasses |= 1u << c;
-        }
-        for (int c = 0; c < MISS_CLASS; ++c)
-            if (((pt->smallClasses >> c) & 1u) && !((pt->diffuseClasses | pt->plasticClasses) >> c & 1u) && !(classTypes[c] & TM_TEXTURED) &&
-                (classTypes[c] & ~TM_GLASS) == 0)
-                pt->glassClasses |= 1u << c;
-        if (getenv("MIPT_NO_SPECIALISE")) pt->diffuseClasses = pt->plasticClasses = pt->glassClasses = 0;
-        if (getenv("MIPT_ALL_LIGHTS")) pt->hasInfiniteLight = true;
-        pt->smallClasses &= ~(pt->diffuseClasses | pt->plasticClasses | pt->glassClasses);
-        unsigned disneyTextured = 0u;
-        for (int c = 0; c < MISS_CLASS; ++c)
-            if (classTypes[c] & TM_TEXTURED) {
-                if (((pt->smallClasses >> c) & 1u) && !getenv("MIPT_NO_SPECIALISE")) {
-                    if ((classTypes[c] & ~(TM_DIFFUSE | TM_TEXTURED)) == 0) { pt->texturedDiffuse |= 1u << c; pt->smallClasses &= ~(1u << c); }
-                    else if ((classTypes[c] & ~(TM_PLASTIC | TM_TEXTURED)) == 0) { pt->texturedPlastic |= 1u << c; pt->smallClasses &= ~(1u << c); }
-                }
-                // (textured "disney" classes go to the eight-lobe instance whatever their lobe count: only that one reads the
-                // rules that form their spectra from the colour -- LobeTexT::rules, d_bsdf.h)
-                const unsigned disneyBits = (1u << MI_BXDF_DISNEY_DIFFUSE) | (1u << MI_BXDF_DISNEY_FAKE_SS) | (1u << MI_BXDF_DISNEY_RETRO) |
-                                            (1u << MI_BXDF_DISNEY_SHEEN) | (1u << MI_BXDF_DISNEY_CLEARCOAT) | (1u << (16 + MI_FRESNEL_DISNEY));
-                if (classTypes[c] & disneyBits) {
-                    if ((pt->smallClasses >> c) & 1u) { pt->smallClasses &= ~(1u << c); pt->largeClasses |= 1u << c; }
-                    disneyTextured |= 1u << c;
-                }
-                if ((pt->smallClasses >> c) & 1u) { pt->texturedSmall |= 1u << c; pt->smallClasses &= ~(1u << c); }
-                if ((pt->largeClasses >> c) & 1u) { pt->texturedLarge |= 1u << c; pt->largeClasses &= ~(1u << c); }
-            }
-        if (!getenv("MIPT_NO_SPECIALISE"))
-            for (int c = 0; c < MISS_CLASS; ++c) {   // the lobe sets of "uber" and "disney": instances without the rest of the BxDF code
-                if (!((pt->largeClasses >> c) & 1u)) continue;
-                if (classLobes[c] <= 4 && (classTypes[c] & ~TM_UBER) == 0) { pt->uberClasses |= 1u << c; pt->largeClasses &= ~(1u << c); }
-                else if ((classTypes[c] & ~TM_DISNEY) == 0) { pt->disneyClasses |= 1u << c; pt->largeClasses &= ~(1u << c); }
-            }
-        if (!getenv("MIPT_NO_SPECIALISE"))
-            for (int c = 0; c < MISS_CLASS; ++c)
-                if (classLobes[c] <= 4) {
-                    if ((pt->largeClasses >> c) & 1u) { pt->mediumClasses |= 1u << c; pt->largeClasses &= ~(1u << c); }
-                    if (((pt->texturedLarge & ~disneyTextured) >> c) & 1u) { pt->texturedMedium |= 1u << c; pt->texturedLarge &= ~(1u << c); }
-                }
     }
     // pre-gathered leaf records: positions of each BVH-ordered primitive + flags
     {
@@ -3740,6 +3650,15 @@ int mi_pt_create(const mi_scene_desc *d, int device_ordinal, mi_pt **out) {
     s.rrThreshold = d->integrator.rr_threshold;
     s.nBands = d->integrator.n_ca_bands;
     s.bandDelta = (int)std::round((float)MI_NSPEC / (float)s.nBands);  // spectralpath.cpp:258
+    // each shading class to its k_shade instance; the matte and plastic instances exist with and without the
+    // environment-light code and with the Halton sampler alone or all three
+    const unsigned hot = (pt->hasInfiniteLight ? TM_LIGHTS_ALL : TM_LIGHTS_NO_ENV) | (s.samplerType == MI_SAMPLER_HALTON ? 0u : TM_SAMPLERS);
+    for (int c = 0; c < MAX_CLASSES; ++c) {
+        if (!((s.classMask >> c) & 1u)) continue;
+        const int i = ShadeInstanceOf(classTypes[c], classLobes[c], pt->hasInstances, hot);
+        if (i < 0) { g_err = "no k_shade instance for shading class " + std::to_string(c); mi_pt_destroy(pt); return MI_ERR_UNSUPPORTED; }
+        pt->shadeClasses[i] |= 1u << c;
+    }
     pt->spp = d->sampler.samples_per_pixel;
     if (d->n_nodes) for (int i = 0; i < 3; ++i) { s.wbMin[i] = d->nodes[0].bmin[i]; s.wbMax[i] = d->nodes[0].bmax[i]; }
     if (d->sampler.type >= MI_SAMPLER_ZEROTWO && d->sampler.pixel_dims > 0) {
@@ -3805,49 +3724,6 @@ int mi_pt_create(const mi_scene_desc *d, int device_ordinal, mi_pt **out) {
     return MI_OK;
 }
 
-#ifdef MIPT_SORT_EXPERIMENT
-// Experiment (not part of the product build): how much would the traversal kernels gain from coherent work lists? Sorts a
-// ray queue by (origin cell 8x8x8, direction octant) with hipcub before the traversal launch; MIPT_SORT = bit mask of the
-// modes to sort (1: continuation rays, 2: shadow rays, 4: MIS rays). The sort's own time is not the question here: the
-// traversal kernels' durations in a rocprofv3 kernel trace are.
-__global__ void k_sort_keys(DScene s, Pool pool, const uint32_t *queue, unsigned n, int mode, uint32_t *keys) {
-    const unsigned i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t slot = queue[i];
-    const float4 r0 = pool.R(mode == 0 ? R_RAY0 : (mode == 1 ? R_SH0 : R_MI0), slot), r1 = pool.R(mode == 0 ? R_RAY1 : (mode == 1 ? R_SH1 : R_MI1), slot);
-    const float dx = mode == 0 ? r1.x : r0.w, dy = mode == 0 ? r1.y : r1.x, dz = mode == 0 ? r1.z : r1.y;
-    auto cell = [&](float v, int a) { const float t = (v - s.wbMin[a]) / (s.wbMax[a] - s.wbMin[a]); return (unsigned)min(7, max(0, (int)(t * 8.f))); };
-    const unsigned cx = cell(r0.x, 0), cy = cell(r0.y, 1), cz = cell(r0.z, 2);
-    unsigned m = 0;
-    for (int b = 0; b < 3; ++b) m |= (((cx >> b) & 1u) << (3 * b)) | (((cy >> b) & 1u) << (3 * b + 1)) | (((cz >> b) & 1u) << (3 * b + 2));
-    keys[i] = (m << 3) | (dx < 0 ? 1u : 0u) | (dy < 0 ? 2u : 0u) | (dz < 0 ? 4u : 0u);
-}
-static void SortQueueExperiment(mi_pt *pt, SubRenderer &sub, int mode) {
-    static int mask = getenv("MIPT_SORT") ? atoi(getenv("MIPT_SORT")) : 0;
-    if (!((mask >> mode) & 1)) return;
-    hipStream_t st = sub.stream;
-    static uint32_t *keys = nullptr, *keysOut = nullptr, *valsOut = nullptr;
-    static void *temp = nullptr;
-    static size_t tempBytes = 0;
-    const size_t cap = sub.pool.n;
-    if (!keys) {
-        hipMalloc((void **)&keys, cap * 4); hipMalloc((void **)&keysOut, cap * 4); hipMalloc((void **)&valsOut, cap * 4);
-        hipcub::DeviceRadixSort::SortPairs(nullptr, tempBytes, keys, keysOut, valsOut, valsOut, (int)cap, 0, 12, st);
-        hipMalloc(&temp, tempBytes);
-    }
-    unsigned cnt[2] = {0, 0};
-    uint32_t *queue;
-    if (mode == 0) { hipMemcpyAsync(&cnt[0], &sub.ctr->contCount.v, 4, hipMemcpyDeviceToHost, st); hipStreamSynchronize(st); queue = sub.pool.extQ + (sub.pool.n - cnt[0]); }
-    else { hipMemcpyAsync(&cnt[0], mode == 1 ? &sub.ctr->shadowCount.v : &sub.ctr->misCount.v, 4, hipMemcpyDeviceToHost, st); hipStreamSynchronize(st); queue = mode == 1 ? sub.pool.shadowQ : sub.pool.misQ; }
-    const unsigned n = cnt[0];
-    if (n < 2) return;
-    hipLaunchKernelGGL(k_sort_keys, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, pt->scene, sub.pool, queue, n, mode, keys);
-    size_t tb = tempBytes;
-    hipcub::DeviceRadixSort::SortPairs(temp, tb, keys, keysOut, queue, valsOut, (int)n, 0, 12, st);
-    hipMemcpyAsync(queue, valsOut, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
-}
-#endif
-
 // The launches of one wavefront iteration, shared by RenderSub and the path-dump tool.
 static void LaunchTraversal(mi_pt *pt, SubRenderer &sub, int mode, dim3 travGrid, bool closestMis = false) {
     if (mode == 2 && pt->scene.misAny && !closestMis) mode = 3;   // the MIS rays as visibility queries (k_trav, MODE 3)
@@ -3877,45 +3753,10 @@ static void LaunchTraversal(mi_pt *pt, SubRenderer &sub, int mode, dim3 travGrid
 }
 
 static void LaunchShade(mi_pt *pt, SubRenderer &sub, dim3 grid) {
-    const DScene &s = pt->scene;
-    const dim3 block(BLOCK);
-    hipStream_t st = sub.stream;
     const dim3 shadeGrid(grid.x + MAX_CLASSES);
-#ifdef MIPT_HOT_ONLY
-    if (pt->diffuseClasses) hipLaunchKernelGGL((k_shade<2, TM_DIFFUSE | TM_LIGHTS_NO_ENV>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->diffuseClasses);
-    if (pt->plasticClasses) hipLaunchKernelGGL((k_shade<2, TM_PLASTIC | TM_LIGHTS_NO_ENV>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->plasticClasses);
-    return;
-#else
-    if (pt->hasInstances) {   // scenes with object instances: the two fully general instances of the kernel, by lobe count
-        const unsigned two = pt->diffuseClasses | pt->plasticClasses | pt->glassClasses | pt->smallClasses | pt->texturedDiffuse | pt->texturedPlastic | pt->texturedSmall;
-        const unsigned more = pt->mediumClasses | pt->texturedMedium | pt->largeClasses | pt->texturedLarge | pt->uberClasses | pt->disneyClasses;
-        if (two) hipLaunchKernelGGL((k_shade<2, TM_ALL>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, two);
-        if (more) hipLaunchKernelGGL((k_shade<MI_MAX_BXDFS, TM_ALL>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, more);
-        return;
-    }
-    // the two hot instances (matte-like and plastic-like classes) exist with and without environment-light code and
-    // with the Halton sampler alone or all three
-#define SHADE_LAUNCH(TM_, CLASSES_) hipLaunchKernelGGL((k_shade<2, TM_>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, CLASSES_)
-#define SHADE_LAUNCH_HOT(TM_, CLASSES_) do { if (!(CLASSES_)) break; \
-        if (halton) { if (pt->hasInfiniteLight) SHADE_LAUNCH(TM_ | TM_LIGHTS_ALL, CLASSES_); else SHADE_LAUNCH(TM_ | TM_LIGHTS_NO_ENV, CLASSES_); } \
-        else { if (pt->hasInfiniteLight) SHADE_LAUNCH(TM_ | TM_LIGHTS_ALL | TM_SAMPLERS, CLASSES_); else SHADE_LAUNCH(TM_ | TM_LIGHTS_NO_ENV | TM_SAMPLERS, CLASSES_); } } while (0)
-    const bool halton = s.samplerType == MI_SAMPLER_HALTON;
-    SHADE_LAUNCH_HOT(TM_DIFFUSE, pt->diffuseClasses);
-    SHADE_LAUNCH_HOT(TM_PLASTIC, pt->plasticClasses);
-#undef SHADE_LAUNCH_HOT
-#undef SHADE_LAUNCH
-    if (pt->smallClasses) hipLaunchKernelGGL((k_shade<2, TM_GENERIC>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->smallClasses);
-    if (pt->glassClasses) hipLaunchKernelGGL((k_shade<2, TM_GLASS | TM_LIGHTS_ALL | TM_SAMPLERS>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->glassClasses);
-    if (pt->uberClasses) hipLaunchKernelGGL((k_shade<4, TM_UBER | TM_LIGHTS_ALL | TM_SAMPLERS>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->uberClasses);
-    if (pt->disneyClasses) hipLaunchKernelGGL((k_shade<MI_MAX_BXDFS, TM_DISNEY | TM_LIGHTS_ALL | TM_SAMPLERS>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->disneyClasses);
-    if (pt->mediumClasses) hipLaunchKernelGGL((k_shade<4, TM_GENERIC>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->mediumClasses);
-    if (pt->texturedMedium) hipLaunchKernelGGL((k_shade<4, TM_FULL>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->texturedMedium);
-    if (pt->largeClasses) hipLaunchKernelGGL((k_shade<MI_MAX_BXDFS, TM_GENERIC>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->largeClasses);
-    if (pt->texturedDiffuse) hipLaunchKernelGGL((k_shade<2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->texturedDiffuse);
-    if (pt->texturedPlastic) hipLaunchKernelGGL((k_shade<2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->texturedPlastic);
-    if (pt->texturedSmall) hipLaunchKernelGGL((k_shade<2, TM_FULL>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->texturedSmall);
-    if (pt->texturedLarge) hipLaunchKernelGGL((k_shade<MI_MAX_BXDFS, TM_FULL>), shadeGrid, block, 0, st, s, sub.pool, sub.ctr, pt->texturedLarge);
-#endif   // MIPT_HOT_ONLY
+    for (int i = 0; i < N_SHADE_INSTANCES; ++i)
+        if (pt->shadeClasses[i])
+            hipLaunchKernelGGL(kShadeInstances[i].kernel, shadeGrid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, pt->shadeClasses[i]);
 }
 
 // One sub-renderer = one path pool with its queues and counters on its own HIP stream.
@@ -4026,9 +3867,6 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         if (alive == 0 && drawn >= wd.totalWork) { harvest(set, false); break; }
         if (alive == 0) { harvest(set, false); havePrev = false; set ^= 1; if (++sub.iterations > 100000000ull) { g_err = "render loop did not terminate"; return MI_ERR_HIP; } continue; }
         HIPCHK(hipEventRecord(ev[7], st));
-#ifdef MIPT_SORT_EXPERIMENT
-        SortQueueExperiment(pt, sub, 0);
-#endif
         LaunchTraversal(pt, sub, 0, travGrid);
         HIPCHK(hipEventRecord(ev[6], st));
         if (pt->hasInstances) hipLaunchKernelGGL((k_resolve_extend<true>), chunkGrid, block, 0, st, s, sub.pool, sub.ctr);
@@ -4038,18 +3876,12 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         HIPCHK(hipEventRecord(ev[2], st));
         LaunchShade(pt, sub, grid);
         HIPCHK(hipEventRecord(ev[3], st));
-#ifdef MIPT_SORT_EXPERIMENT
-        SortQueueExperiment(pt, sub, 1);
-#endif
         LaunchTraversal(pt, sub, 1, travGrid);
         if (pt->hasInstances) hipLaunchKernelGGL((k_resolve_shadow<true>), grid, block, 0, st, s, sub.pool, sub.ctr);
         else hipLaunchKernelGGL((k_resolve_shadow<false>), grid, block, 0, st, s, sub.pool, sub.ctr);
         if (pt->hasQuadrics) { if (pt->hasInstances) hipLaunchKernelGGL((k_resolve_overflow<true>), dim3(OVERFLOW_GRID), block, 0, st, s, sub.pool, sub.ctr, 1);
             else hipLaunchKernelGGL((k_resolve_overflow<false>), dim3(OVERFLOW_GRID), block, 0, st, s, sub.pool, sub.ctr, 1); }
         HIPCHK(hipEventRecord(ev[4], st));
-#ifdef MIPT_SORT_EXPERIMENT
-        SortQueueExperiment(pt, sub, 2);
-#endif
         LaunchTraversal(pt, sub, 2, travGrid);
         if (pt->hasInstances) hipLaunchKernelGGL((k_resolve_mis<true>), grid, block, 0, st, s, sub.pool, sub.ctr);
         else hipLaunchKernelGGL((k_resolve_mis<false>), grid, block, 0, st, s, sub.pool, sub.ctr);
@@ -4064,22 +3896,6 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(&sub.result, sub.ctr, sizeof(DevCounters), hipMemcpyDeviceToHost));
-#ifdef MIPT_EXP_STAMPS
-    {
-        unsigned long long tot = 0;
-        for (int k = 0; k < 19; ++k) tot += sub.result.phase[k];
-        {
-            unsigned long long g = 0;
-            for (int k = 19; k < 24; ++k) g += sub.result.phase[k];
-            fprintf(stderr, "k_generate stamps (scan + lists | L read + guards | film rows | refill | extend lists):");
-            for (int k = 19; k < 24; ++k) fprintf(stderr, " %.1f%%", 100.0 * (double)sub.result.phase[k] / (double)std::max(1ull, g));
-            fprintf(stderr, "\n");
-        }
-        fprintf(stderr, "k_shade stamps: %llu waves, %.0f cycles per wave;", sub.result.phaseWaves, (double)tot / (double)std::max(1ull, sub.result.phaseWaves));
-        for (int k = 0; k < 19; ++k) fprintf(stderr, " [%d] %.1f%%", k, 100.0 * (double)sub.result.phase[k] / (double)std::max(1ull, tot));
-        fprintf(stderr, "\n");
-    }
-#endif
     return MI_OK;
 }
 
