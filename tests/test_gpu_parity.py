@@ -351,11 +351,27 @@ def test_create_rejects_malformed_descriptions(pt):
     # a material whose lobe 0 is not the FresnelSpecular one -- refused, and the scene still renders once they are put back
     mats = (pt.Material * s.desc.n_materials).from_address(C.addressof(s.desc.materials.contents))
     m = next(x for x in mats if x.n_bxdfs > 0)
-    for set_bad, undo, needle in ((lambda: setattr(m.tex[0], "rule", 42), lambda: setattr(m.tex[0], "rule", 0), b"mi_lobe_rule"),
-                                  (lambda: setattr(m, "sigma_tex", 7), lambda: setattr(m, "sigma_tex", -1), b"sigma_tex"),
-                                  (lambda: setattr(m, "rough_flags", 2), lambda: setattr(m, "rough_flags", 0), b"MI_ROUGH_GLASS")):
+    # ... and the refusals that depend on the description alone but used to come after the device uploads had begun: an
+    # empty film, an infinite light without an environment map, a mesh's alpha texture out of range, light-distribution
+    # tables missing, a spatial light distribution too large (the scene of the last three: meshes, spatial light sampling)
+    z = pt.Scene(text=st.material_zoo(res=8, spp=1))
+    assert z.desc.n_meshes > 0 and z.desc.n_textures == 0 and z.desc.light_distrib.type == 2   # MI_LD_SPATIAL
+    film, light, mesh, ld = s.desc.film, s.desc.lights[0], z.desc.meshes[0], z.desc.light_distrib
+    width, light_type, envmap, alpha, ld_func, nvox = film.cropped_bounds[2], light.type, light.envmap, mesh.alpha_tex, ld.func, ld.n_voxels[0]
+    for sc, set_bad, undo, rc, needle in (
+            (s, lambda: setattr(m.tex[0], "rule", 42), lambda: setattr(m.tex[0], "rule", 0), -1, b"mi_lobe_rule"),
+            (s, lambda: setattr(m, "sigma_tex", 7), lambda: setattr(m, "sigma_tex", -1), -1, b"sigma_tex"),
+            (s, lambda: setattr(m, "rough_flags", 2), lambda: setattr(m, "rough_flags", 0), -1, b"MI_ROUGH_GLASS"),
+            (s, lambda: film.cropped_bounds.__setitem__(2, film.cropped_bounds[0]), lambda: film.cropped_bounds.__setitem__(2, width),
+             -1, b"empty film"),
+            (s, lambda: (setattr(light, "type", 3), setattr(light, "envmap", 0)),   # MI_LIGHT_INFINITE; the scene has no maps
+             lambda: (setattr(light, "type", light_type), setattr(light, "envmap", envmap)), -1, b"infinite light without environment map"),
+            (z, lambda: setattr(mesh, "alpha_tex", 0), lambda: setattr(mesh, "alpha_tex", alpha), -1, b"alpha texture index out of range"),
+            (z, lambda: (setattr(ld, "type", 1), setattr(ld, "func", None)),   # MI_LD_POWER without its tables
+             lambda: (setattr(ld, "type", 2), setattr(ld, "func", ld_func)), -1, b"light distribution tables missing"),
+            (z, lambda: ld.n_voxels.__setitem__(0, 0), lambda: ld.n_voxels.__setitem__(0, nvox), -4, b"spatial light distribution too large")):
         set_bad()
-        assert pt.hip_lib().mi_pt_create(s.desc_ptr, 0, C.byref(h)) == -1 and needle in pt.hip_lib().mi_pt_last_error()
+        assert pt.hip_lib().mi_pt_create(sc.desc_ptr, 0, C.byref(h)) == rc and needle in pt.hip_lib().mi_pt_last_error()
         undo()
     integ = pt.CreatePathIntegrator(s)
     film, weight = integ.Render()
