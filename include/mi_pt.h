@@ -415,7 +415,9 @@ typedef struct mi_render_params {
     uint32_t path_pool;   /* resident path slots; 0 = default */
     int64_t spp_override; /* 0 = use sampler.samples_per_pixel */
     int64_t sample_begin; /* first Halton sample number of this pass (0 = from the start);
-                             a pass renders sample numbers [sample_begin, sample_begin + spp) */
+                             a pass renders sample numbers [sample_begin, sample_begin + spp).
+                             sample_begin >= 0 and sample_begin + spp <= 2^31 - 1 (a path keeps its sample number
+                             in an int); mi_pt_render refuses other values with MI_ERR_INVALID */
     void *stream;         /* hipStream_t or NULL */
 } mi_render_params;
 

@@ -4025,6 +4025,13 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
 int mi_pt_render(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *weight_sum, mi_counters *counters) {
     if (!pt || !rp) { g_err = "null argument"; return MI_ERR_INVALID; }
     if (rp->shard_count < 1 || rp->shard_index < 0 || rp->shard_index >= rp->shard_count) { g_err = "bad shard"; return MI_ERR_INVALID; }
+    {   // sample numbers are ints in the path state (I_SAMPLE) and in the oracle: [sample_begin, sample_begin + spp) stays below 2^31 - 1
+        const long long passSpp = rp->spp_override > 0 ? rp->spp_override : pt->spp;
+        if (rp->sample_begin < 0 || rp->sample_begin > 0x7fffffffll || passSpp > 0x7fffffffll - rp->sample_begin) {
+            g_err = "sample numbers out of range: sample_begin >= 0 and sample_begin + spp <= 2^31 - 1";
+            return MI_ERR_INVALID;
+        }
+    }
     if (pt->scene.samplerType >= MI_SAMPLER_ZEROTWO &&
         (rp->sample_begin < 0 || rp->sample_begin + (rp->spp_override > 0 ? rp->spp_override : pt->spp) > pt->spp)) {
         g_err = "a pixel sampler (02sequence / stratified) has tables for samples_per_pixel samples: the pass asks for sample numbers beyond them";

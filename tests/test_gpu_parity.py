@@ -64,21 +64,11 @@ def _check_counters(c, o, tol=1e-4, slack=3):
     assert c["bad_samples"] == o["bad_samples"] == 0
 
 
-def _parity(pt, ob, s, name, exact=True, rel_tol=None, counter_tol=None, weights_exact=True):
-    """Render `s` on the device and with the oracle, record the measured differences, assert the bar of the mode.
-    EXACT mode bar: counters equal (2 counts of slack: the only arithmetic not shared is DivBy's reciprocal form, one ulp in
-    2^-22 of the quotients, d_math.h; measured difference: 0 in every test), image relative L2 < 1e-6 (float atomics:
-    accumulation order; measured <= 2.5e-7), every pixel within 2e-4 x mean radiance (measured <= 4e-5; the target is 1e-3).
-    REFERENCE-LIBM bar: what the caller passes (the BASELINE target at BASELINE sample counts)."""
-    integ = pt.CreatePathIntegrator(s)
-    film, weight = integ.Render()
-    if exact:
-        with ob.exact_libm():
-            ofilm, oweight, oc, _ = ob.render(s)
-    else:
-        ofilm, oweight, oc, _ = ob.render(s)
-    c, o = integ.counters.as_dict(), oc.as_dict()
-    spp = max(1, s.spp)
+def _compare(name, film, weight, c, ofilm, oweight, o, spp, exact=True, rel_tol=None, counter_tol=None, weights_exact=True,
+             counter_slack=None):
+    """Record the measured differences of a device result (film, weight, counter dict c) against the oracle's, assert the bar
+    of the mode (see _parity). counter_slack: the counts of slack, for results summed over several renders (2 per render)."""
+    spp = max(1, spp)
     l2 = _pixel_l2(film, ofilm, spp)
     mean = max(float(ofilm.mean()) / spp, 1e-12)
     m = {"test": name, "mode": "exact" if exact else "reference-libm", "rel_l2": _rel_l2(film, ofilm),
@@ -92,12 +82,34 @@ def _parity(pt, ob, s, name, exact=True, rel_tol=None, counter_tol=None, weights
     else:
         assert np.allclose(weight, oweight, rtol=1e-5, atol=1e-6)
     if exact:
-        _check_counters(c, o, tol=counter_tol if counter_tol is not None else 0.0, slack=2)
+        _check_counters(c, o, tol=counter_tol if counter_tol is not None else 0.0, slack=counter_slack if counter_slack is not None else 2)
         assert m["rel_l2"] < (rel_tol if rel_tol is not None else 1e-6), m
         assert m["max_pixel_l2_over_mean"] < 2e-4, m
     else:
         _check_counters(c, o, tol=counter_tol if counter_tol is not None else 1e-4)
         assert m["rel_l2"] < (rel_tol if rel_tol is not None else 1e-4), m
+    return m
+
+
+def _parity(pt, ob, s, name, exact=True, rel_tol=None, counter_tol=None, weights_exact=True, render=None, oracle=None):
+    """Render `s` on the device and with the oracle, record the measured differences, assert the bar of the mode.
+    EXACT mode bar: counters equal (2 counts of slack: the only arithmetic not shared is DivBy's reciprocal form, one ulp in
+    2^-22 of the quotients, d_math.h; measured difference: 0 in every test), image relative L2 < 1e-6 (float atomics:
+    accumulation order; measured <= 2.5e-7), every pixel within 2e-4 x mean radiance (measured <= 4e-5; the target is 1e-3).
+    REFERENCE-LIBM bar: what the caller passes (the BASELINE target at BASELINE sample counts).
+    render: keywords for integ.Render (path_pool, shard_*, ...); oracle: an (ofilm, oweight, oc) computed before, so that one
+    oracle render serves several device renders of the scene."""
+    integ = pt.CreatePathIntegrator(s)
+    film, weight = integ.Render(**(render or {}))
+    if oracle is not None:
+        ofilm, oweight, oc = oracle
+    elif exact:
+        with ob.exact_libm():
+            ofilm, oweight, oc, _ = ob.render(s)
+    else:
+        ofilm, oweight, oc, _ = ob.render(s)
+    _compare(name, film, weight, integ.counters.as_dict(), ofilm, oweight, oc.as_dict(), s.spp, exact=exact, rel_tol=rel_tol,
+             counter_tol=counter_tol, weights_exact=weights_exact)
     return film, weight, integ, ofilm, oweight, oc
 
 
