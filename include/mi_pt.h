@@ -508,7 +508,10 @@ int mi_pt_light_distribution(mi_pt *pt, float *func, float *func_int, uint64_t c
  * nodes (children given as final indices), their own final indices, the total node count and the final index of each
  * treelet's first node. prim_bounds: n x {min xyz, max xyz}; nodes_out: capacity nodes_capacity (2 n is always enough);
  * ordered_out: n primitive numbers in leaf order. The tree is the one the reference builds on one thread (leaves in
- * Morton order): the host restatement in libmipt_host.so builds the same nodes, bit for bit. */
+ * Morton order): the host restatement in libmipt_host.so builds the same nodes, bit for bit (mi_bvh_build_host; its
+ * mi_bvh_upper_sah is the `upper` the front end passes, include/mi_scene.h). MI_ERR_UNSUPPORTED (message in
+ * mi_bvh_last_error) when more than 65535 primitives share one Morton code: they would be one leaf, and a node's count has
+ * 16 bits (the reference CHECKs that away, bvh.cpp:646). */
 typedef int (*mi_bvh_upper_fn)(void *user, uint32_t n_treelets, const float *root_bounds, const int32_t *treelet_sizes,
                                mi_bvh_node *upper_nodes, int32_t *upper_index, uint32_t *n_upper, uint32_t *n_total,
                                int32_t *treelet_offset);

@@ -47,6 +47,18 @@ const char *mi_scene_film_filename(const mi_scene *s);
 void mi_scene_free(mi_scene *s);
 const char *mi_scene_last_error(void);
 
+/* The host BVH builders on raw bounds, as the front end runs them on a scene's primitives. prim_bounds: n x {min xyz, max xyz}
+ * float32; split_method: one of MI_BVH_SPLIT_*; nodes_out: room for nodes_capacity nodes (2 n always suffices); ordered_out:
+ * n primitive numbers in leaf order. MI_ERR_UNSUPPORTED (message in mi_scene_last_error) when a leaf would hold more than
+ * 65535 primitives -- that many share one centre or one Morton code, and a node's count has 16 bits. */
+enum { MI_BVH_SPLIT_SAH = 0, MI_BVH_SPLIT_MIDDLE = 1, MI_BVH_SPLIT_EQUAL = 2, MI_BVH_SPLIT_HLBVH = 3 };
+int mi_bvh_build_host(const float *prim_bounds, uint32_t n, int32_t max_prims_in_node, int32_t split_method, mi_bvh_node *nodes_out,
+                      uint32_t nodes_capacity, uint32_t *n_nodes, int32_t *ordered_out);
+/* buildUpperSAH (src/accelerators/bvh.cpp:534-638) over treelet roots, with the signature of mi_bvh_upper_fn: the callback
+ * the front end hands to mi_bvh_build_hlbvh (include/mi_pt.h), and the upper tree of the host HLBVH build. */
+int mi_bvh_upper_sah(void *user, uint32_t n_treelets, const float *root_bounds, const int32_t *treelet_sizes, mi_bvh_node *upper_nodes,
+                     int32_t *upper_index, uint32_t *n_upper, uint32_t *n_total, int32_t *treelet_offset);
+
 /* Film::WriteImage, spectral branch: "<w> <h> 31\nv3 \n" then 31 planes of w*h
  * float64 (plane-major), values multiplied by `scale`. film_sum is [h*w*31]. */
 int mi_film_write_dat(const char *filename, int w, int h, const float *film_sum, float scale);

@@ -64,6 +64,11 @@ __global__ void __launch_bounds__(HB_BLOCK) k_centroid_bounds(const PrimBounds *
         for (int a = 0; a < 3; ++a) { atomicMin(&bounds6[a], OrderedOf(mn[a])); atomicMax(&bounds6[3 + a], OrderedOf(mx[a])); }
 }
 
+// Union(Bounds3f, Bounds3f) takes std::min / std::max component by component (geometry.h:1267-1275): of two equal values,
+// -0 and +0 among them, the FIRST argument stays. fminf / fmaxf order the zeros instead, so the node bounds use these.
+__device__ __forceinline__ float MinOf(float a, float b) { return b < a ? b : a; }
+__device__ __forceinline__ float MaxOf(float a, float b) { return a < b ? b : a; }
+
 __device__ __forceinline__ uint32_t LeftShift3(uint32_t x) {   // bvh.cpp:107-130
     if (x == (1u << 10)) --x;
     x = (x | (x << 16)) & 0x30000ffu;
@@ -171,15 +176,17 @@ __global__ void __launch_bounds__(HB_BLOCK) k_treelet_starts(const uint32_t *__r
 struct LbvhNode {
     float mn[3], mx[3];
     int32_t second;      // interior: treelet-relative index of the second child; leaf: first primitive (index into the sorted order)
-    uint16_t nPrims;
+    uint16_t nPrims;     // 0: interior. A leaf's count, at most kMaxLeafPrims (a larger leaf is stored clamped and flagged)
     uint8_t axis, pad;
 };
+static_assert(sizeof(LbvhNode) == 32, "LbvhNode is 32 bytes");
+constexpr int kMaxLeafPrims = 65535;   // what nPrims (and mi_bvh_node::n_prims) can hold
 
 // emitLBVH for treelet t = sorted primitives [start, start + count): nodes into scratch[2 * start ...], in the order the
 // recursion creates them (a node before its subtrees, the first subtree before the second). One lane per treelet.
 __global__ void __launch_bounds__(64) k_emit_lbvh(const uint32_t *__restrict__ codes, const int32_t *__restrict__ idx, const PrimBounds *__restrict__ pb,
                                                   const uint32_t *__restrict__ starts, uint32_t nTreelets, uint32_t n, int maxPrimsInNode,
-                                                  LbvhNode *scratch, int32_t *treeletSize, float *rootBounds) {
+                                                  LbvhNode *scratch, int32_t *treeletSize, float *rootBounds, uint32_t *biggestLeaf) {
     const uint32_t t = blockIdx.x * 64 + threadIdx.x;
     if (t >= nTreelets) return;
     const uint32_t start = starts[t], end = (t + 1 < nTreelets) ? starts[t + 1] : n;
@@ -196,13 +203,18 @@ __global__ void __launch_bounds__(64) k_emit_lbvh(const uint32_t *__restrict__ c
         if (tk.parent >= 0) nodes[tk.parent].second = me;   // (only the second child arrives with a parent)
         LbvhNode &nd = nodes[me];
         if (tk.bit == -1 || tk.count < maxPrimsInNode) {
-            float mn[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()}, mx[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+            const float big = 3.402823466e+38f;   // Bounds3f(): max / lowest of float, geometry.h:753-758
+            float mn[3] = {big, big, big}, mx[3] = {-big, -big, -big};
             for (int i = 0; i < tk.count; ++i) {
                 const PrimBounds b = pb[idx[tk.first + i]];
-                for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], b.mn[a]); mx[a] = fmaxf(mx[a], b.mx[a]); }
+                for (int a = 0; a < 3; ++a) { mn[a] = MinOf(mn[a], b.mn[a]); mx[a] = MaxOf(mx[a], b.mx[a]); }
             }
             for (int a = 0; a < 3; ++a) { nd.mn[a] = mn[a]; nd.mx[a] = mx[a]; }
-            nd.second = tk.first; nd.nPrims = (uint16_t)tk.count; nd.axis = 0; nd.pad = 0;
+            // tk.count >= 1. A run of more than kMaxLeafPrims equal codes does not fit the 16 bits: the node stays a leaf (a
+            // wrapped count of 0 would make it an interior node whose `second` is a primitive index), the host reads the
+            // flag and refuses the build.
+            if (tk.count > kMaxLeafPrims) atomicMax(biggestLeaf, (uint32_t)tk.count);
+            nd.second = tk.first; nd.nPrims = (uint16_t)(tk.count > kMaxLeafPrims ? kMaxLeafPrims : tk.count); nd.axis = 0; nd.pad = 0;
             continue;
         }
         int searchStart = 0, searchEnd = tk.count - 1;   // the split point, bvh.cpp:506-521
@@ -219,7 +231,7 @@ __global__ void __launch_bounds__(64) k_emit_lbvh(const uint32_t *__restrict__ c
         LbvhNode &nd = nodes[k];
         if (nd.nPrims > 0) continue;
         const LbvhNode &c0 = nodes[k + 1], &c1 = nodes[nd.second];
-        for (int a = 0; a < 3; ++a) { nd.mn[a] = fminf(c0.mn[a], c1.mn[a]); nd.mx[a] = fmaxf(c0.mx[a], c1.mx[a]); }
+        for (int a = 0; a < 3; ++a) { nd.mn[a] = MinOf(c0.mn[a], c1.mn[a]); nd.mx[a] = MaxOf(c0.mx[a], c1.mx[a]); }
     }
     treeletSize[t] = nNodes;
     for (int a = 0; a < 3; ++a) { rootBounds[6 * t + a] = nodes[0].mn[a]; rootBounds[6 * t + 3 + a] = nodes[0].mx[a]; }
@@ -275,7 +287,7 @@ int mi_bvh_build_hlbvh(int device_ordinal, const float *prim_bounds, uint32_t n,
     const int maxPrims = std::min(255, std::max(1, (int)max_prims_in_node));
     const uint32_t nTiles = (n + HB_TILE - 1) / HB_TILE, nBlk = (n + HB_BLOCK - 1) / HB_BLOCK;
     constexpr uint32_t kMaxTreelets = 4096;
-    Buf dPb, dBounds, dCodes[2], dIdx[2], dZeros, dStarts, dCount, dScratch, dSize, dRoot, dOffset, dOut;
+    Buf dPb, dBounds, dCodes[2], dIdx[2], dZeros, dStarts, dCount, dScratch, dSize, dRoot, dOffset, dOut, dBiggest;
     HB_CHK(dPb.alloc((size_t)n * sizeof(PrimBounds)));
     HB_CHK(hipMemcpy(dPb.p, prim_bounds, (size_t)n * sizeof(PrimBounds), hipMemcpyHostToDevice));
     HB_CHK(dBounds.alloc(6 * 4));
@@ -310,8 +322,17 @@ int mi_bvh_build_hlbvh(int device_ordinal, const float *prim_bounds, uint32_t n,
     HB_CHK(dScratch.alloc(2 * (size_t)n * sizeof(LbvhNode)));
     HB_CHK(dSize.alloc((size_t)nTreelets * 4));
     HB_CHK(dRoot.alloc((size_t)nTreelets * 24));
+    HB_CHK(dBiggest.alloc(4));
+    HB_CHK(hipMemset(dBiggest.p, 0, 4));
     hipLaunchKernelGGL(k_emit_lbvh, dim3((nTreelets + 63) / 64), dim3(64), 0, 0, dCodes[cur].as<uint32_t>(), dIdx[cur].as<int32_t>(), dPb.as<PrimBounds>(),
-                       dStarts.as<uint32_t>(), nTreelets, n, maxPrims, dScratch.as<LbvhNode>(), dSize.as<int32_t>(), dRoot.as<float>());
+                       dStarts.as<uint32_t>(), nTreelets, n, maxPrims, dScratch.as<LbvhNode>(), dSize.as<int32_t>(), dRoot.as<float>(), dBiggest.as<uint32_t>());
+    uint32_t biggestLeaf = 0;   // 0, or the size of the largest leaf beyond kMaxLeafPrims
+    HB_CHK(hipMemcpy(&biggestLeaf, dBiggest.p, 4, hipMemcpyDeviceToHost));
+    if (biggestLeaf) {
+        g_hlbvhErr = "BVH: a leaf would hold " + std::to_string(biggestLeaf) + " primitives that share one Morton code; more than " +
+                     std::to_string(kMaxLeafPrims) + " do not fit a node's 16-bit count";
+        return MI_ERR_UNSUPPORTED;
+    }
     std::vector<int32_t> sizes(nTreelets), offsets(nTreelets);
     std::vector<float> roots((size_t)nTreelets * 6);
     HB_CHK(hipMemcpy(sizes.data(), dSize.p, (size_t)nTreelets * 4, hipMemcpyDeviceToHost));

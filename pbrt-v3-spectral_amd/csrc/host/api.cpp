@@ -961,19 +961,26 @@ void Api::WorldEnd() {
         std::vector<Bounds3> bounds(pending.size());
         for (size_t i = 0; i < pending.size(); ++i) bounds[i] = pending[i].bounds;
         std::vector<int> order;
+        // a build that refuses its input (a leaf beyond a node's 16-bit count) is an error of the scene, which is then left
+        // without a tree and without primitives: reported, never a wrapped count and never another builder's tree instead
+        bool accelOk = true;
+        std::string accelErr;
         const auto tb0 = std::chrono::steady_clock::now();
         if (method == SplitMethod::HLBVH) {
             // on the device when there is one (mi_bvh_build_hlbvh); the host restatement builds the same tree, node for node
             std::string why;
             double secs = 0;
             const char *where = getenv("MIPT_HLBVH");   // "host": do not try the device
-            bool onDevice = !(where && std::string(where) == "host") &&
-                            BuildHLBVHOnDevice(bounds, maxPrims, 0, &scene->nodes, &order, &scene->stats.interiorNodes, &scene->stats.leafNodes, &secs, &why);
-            if (!onDevice) BuildHLBVH(bounds, maxPrims, &scene->nodes, &order, &scene->stats.interiorNodes, &scene->stats.leafNodes);
+            DeviceBuild dev = DeviceBuild::Unavailable;
+            if (!(where && std::string(where) == "host"))
+                dev = BuildHLBVHOnDevice(bounds, maxPrims, 0, &scene->nodes, &order, &scene->stats.interiorNodes, &scene->stats.leafNodes, &secs, &why);
+            const bool onDevice = dev == DeviceBuild::Built;
+            if (dev == DeviceBuild::Failed) { accelOk = false; accelErr = "Accelerator \"bvh\" \"hlbvh\" (device build): " + why; }
+            else if (!onDevice) accelOk = BuildHLBVH(bounds, maxPrims, &scene->nodes, &order, &scene->stats.interiorNodes, &scene->stats.leafNodes, &accelErr);
             scene->hlbvhOnDevice = onDevice;
             if (getenv("MIPT_TIMING")) fprintf(stderr, "[mipt] HLBVH on the %s%s%s\n", onDevice ? "device" : "host", onDevice ? "" : ": ", onDevice ? "" : why.c_str());
         } else
-            BuildBVH(bounds, maxPrims, method, &scene->nodes, &order, &scene->stats.interiorNodes, &scene->stats.leafNodes);
+            accelOk = BuildBVH(bounds, maxPrims, method, &scene->nodes, &order, &scene->stats.interiorNodes, &scene->stats.leafNodes, &accelErr);
         if (getenv("MIPT_TIMING"))
             fprintf(stderr, "[mipt] BVH build over %zu primitives: %.3f s\n", bounds.size(),
                     std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count());
@@ -991,14 +998,15 @@ void Api::WorldEnd() {
         // appended to the node and primitive arrays with absolute offsets; then the instances that point at them
         for (const std::string &name : objectOrder) {
             ObjectDef &od = objectDefs[name];
-            if (od.prims.empty()) continue;
+            if (od.prims.empty() || !accelOk) continue;
             std::vector<Bounds3> ob(od.prims.size());
             for (size_t i = 0; i < od.prims.size(); ++i) ob[i] = od.prims[i].bounds;
             std::vector<mi_bvh_node> onodes;
             std::vector<int> oorder;
             int oi = 0, ol = 0;
-            if (method == SplitMethod::HLBVH) BuildHLBVH(ob, maxPrims, &onodes, &oorder, &oi, &ol);
-            else BuildBVH(ob, maxPrims, method, &onodes, &oorder, &oi, &ol);
+            accelOk = method == SplitMethod::HLBVH ? BuildHLBVH(ob, maxPrims, &onodes, &oorder, &oi, &ol, &accelErr)
+                                                   : BuildBVH(ob, maxPrims, method, &onodes, &oorder, &oi, &ol, &accelErr);
+            if (!accelOk) break;
             const int baseNode = (int)scene->nodes.size(), basePrim = (int)scene->prims.size();
             for (mi_bvh_node &n : onodes) n.offset += (n.n_prims > 0) ? basePrim : baseNode;
             scene->nodes.insert(scene->nodes.end(), onodes.begin(), onodes.end());
@@ -1012,7 +1020,15 @@ void Api::WorldEnd() {
             scene->stats.interiorNodes += oi;
             scene->stats.leafNodes += ol;
         }
+        if (!accelOk) {
+            Err(accelErr);
+            scene->nodes.clear();
+            scene->prims.clear();
+            scene->hlbvhOnDevice = false;
+            scene->stats.interiorNodes = scene->stats.leafNodes = 0;
+        }
         for (const InstanceRec &ir : instanceRecs) {
+            if (!accelOk) break;
             mi_instance mi{};
             std::memcpy(mi.i2w, ir.i2w.m.m, sizeof(float) * 16);
             std::memcpy(mi.w2i, ir.i2w.mInv.m, sizeof(float) * 16);

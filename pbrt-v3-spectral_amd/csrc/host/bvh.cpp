@@ -43,6 +43,7 @@ struct Builder {
     int *ordered;            // [nPrims], written at explicit offsets
     int orderedNext = 0;     // offset of the next leaf in depth-first order
     int interior = 0, leaves = 0, total = 0;
+    int biggestLeaf = 0;     // a leaf's count must fit LinearBVHNode's 16 bits (checked before the flatten pass)
     int grain = 0;           // > 0: ranges of at most this many primitives are deferred to tasks
     std::vector<DeferredSubtree> *deferred = nullptr;
 
@@ -56,6 +57,7 @@ struct Builder {
         for (int i = start; i < end; ++i) ordered[orderedNext++] = (int)info[i].primitiveNumber;
         node->firstPrimOffset = first;
         node->nPrimitives = end - start;
+        biggestLeaf = std::max(biggestLeaf, end - start);
         node->bounds = b;
         ++leaves;
     }
@@ -173,6 +175,15 @@ int Flatten(const BuildNode *node, std::vector<mi_bvh_node> &nodes, int *offset)
 }
 
 }  // namespace
+
+// LinearBVHNode keeps a leaf's count in 16 bits; the reference CHECKs larger leaves away (CHECK_LT(node->nPrimitives, 65536),
+// bvh.cpp:646). Here such a leaf is an error of the build, never a wrapped count.
+static bool LeafFits(int nPrims, std::string *err) {
+    if (nPrims <= kMaxLeafPrims) return true;
+    if (err) *err = "BVH: a leaf would hold " + std::to_string(nPrims) + " primitives that the split method cannot separate (one centre, or one Morton code); more than " +
+                    std::to_string(kMaxLeafPrims) + " do not fit a node's 16-bit count";
+    return false;
+}
 
 // ------------------------------------------------------------------ HLBVH (BVHAccel::HLBVHBuild, src/accelerators/bvh.cpp:404-638)
 // Morton codes of the centroids (10 bits per axis), a stable radix sort, one LBVH treelet per run of equal top 12 bits
@@ -346,12 +357,12 @@ int BuildUpperSAH(uint32_t nTreelets, const float *rootBounds, const int32_t *tr
     return ub.next;
 }
 
-void BuildHLBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, std::vector<mi_bvh_node> *nodes,
-                std::vector<int> *orderedPrims, int *interior, int *leaves) {
+bool BuildHLBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, std::vector<mi_bvh_node> *nodes,
+                std::vector<int> *orderedPrims, int *interior, int *leaves, std::string *err) {
     nodes->clear();
     orderedPrims->clear();
     *interior = *leaves = 0;
-    if (primBounds.empty()) return;
+    if (primBounds.empty()) return true;
     std::vector<uint32_t> codes;
     MortonCodesAndOrder(primBounds, &codes, orderedPrims);
     const int n = (int)primBounds.size();
@@ -367,6 +378,8 @@ void BuildHLBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, std:
             for (int a = 0; a < 3; ++a) roots.push_back(rb.pMin[a]);
             for (int a = 0; a < 3; ++a) roots.push_back(rb.pMax[a]);
             sizes.push_back((int32_t)treelets.back().size());
+            for (const LbvhNode &ln : treelets.back())
+                if (!LeafFits(ln.nPrims, err)) { orderedPrims->clear(); return false; }
             start = end;
         }
     }
@@ -388,14 +401,15 @@ void BuildHLBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, std:
         }
     }
     for (const mi_bvh_node &ln : *nodes) (ln.n_prims > 0 ? *leaves : *interior)++;
+    return true;
 }
 
-void BuildBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, SplitMethod method,
-              std::vector<mi_bvh_node> *nodes, std::vector<int> *orderedPrims, int *interior, int *leaves) {
+bool BuildBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, SplitMethod method,
+              std::vector<mi_bvh_node> *nodes, std::vector<int> *orderedPrims, int *interior, int *leaves, std::string *err) {
     nodes->clear();
     orderedPrims->clear();
     *interior = *leaves = 0;
-    if (primBounds.empty()) return;
+    if (primBounds.empty()) return true;
     std::vector<PrimInfo> info(primBounds.size());
     for (size_t i = 0; i < primBounds.size(); ++i) {
         info[i].primitiveNumber = i;
@@ -418,7 +432,7 @@ void BuildBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, SplitM
     const auto t0 = std::chrono::steady_clock::now();
     top.Child(&root, info, 0, n);
     const auto t1 = std::chrono::steady_clock::now();
-    int total = top.total, nInterior = top.interior, nLeaves = top.leaves;
+    int total = top.total, nInterior = top.interior, nLeaves = top.leaves, biggestLeaf = top.biggestLeaf;
     std::vector<std::unique_ptr<Builder>> workers(nThreads);   // one per thread (its nodes must outlive the flatten pass)
     if (!deferred.empty()) {
         std::atomic<size_t> next{0};
@@ -437,9 +451,10 @@ void BuildBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, SplitM
         for (unsigned t = 1; t < nThreads; ++t) pool.emplace_back(run, t);
         run(0);
         for (std::thread &t : pool) t.join();
-        for (const auto &w : workers) if (w) { total += w->total; nInterior += w->interior; nLeaves += w->leaves; }
+        for (const auto &w : workers) if (w) { total += w->total; nInterior += w->interior; nLeaves += w->leaves; biggestLeaf = std::max(biggestLeaf, w->biggestLeaf); }
     }
     const auto t2 = std::chrono::steady_clock::now();
+    if (!LeafFits(biggestLeaf, err)) { orderedPrims->clear(); return false; }
     nodes->resize(total);
     int offset = 0;
     Flatten(root, *nodes, &offset);
@@ -450,6 +465,7 @@ void BuildBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, SplitM
     }
     *interior = nInterior;
     *leaves = nLeaves;
+    return true;
 }
 
 }  // namespace mipt

@@ -163,4 +163,45 @@ int mi_integrator_render(const mi_scene *s, int device_ordinal, const char *outf
     });
 }
 
+// The host builders on raw bounds (bvh.cpp): what the front end builds for a scene's primitives, without a scene.
+int mi_bvh_build_host(const float *prim_bounds, uint32_t n, int32_t max_prims_in_node, int32_t split_method, mi_bvh_node *nodes_out,
+                      uint32_t nodes_capacity, uint32_t *n_nodes, int32_t *ordered_out) {
+    if (!prim_bounds || !nodes_out || !n_nodes || !ordered_out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (split_method < MI_BVH_SPLIT_SAH || split_method > MI_BVH_SPLIT_HLBVH) { g_err = "unknown split method"; return MI_ERR_INVALID; }
+    *n_nodes = 0;
+    return Guarded([&]() -> int {
+        static_assert(sizeof(Bounds3) == 6 * sizeof(float), "Bounds3 is {min xyz, max xyz}");
+        std::vector<Bounds3> bounds(n);
+        if (n) memcpy((void *)bounds.data(), prim_bounds, (size_t)n * sizeof(Bounds3));
+        std::vector<mi_bvh_node> nodes;
+        std::vector<int> order;
+        int interior = 0, leaves = 0;
+        std::string err;
+        const bool ok = split_method == MI_BVH_SPLIT_HLBVH
+                            ? BuildHLBVH(bounds, max_prims_in_node, &nodes, &order, &interior, &leaves, &err)
+                            : BuildBVH(bounds, max_prims_in_node, split_method == MI_BVH_SPLIT_SAH ? SplitMethod::SAH : split_method == MI_BVH_SPLIT_MIDDLE ? SplitMethod::Middle : SplitMethod::EqualCounts,
+                                       &nodes, &order, &interior, &leaves, &err);
+        if (!ok) { g_err = err; return MI_ERR_UNSUPPORTED; }
+        if (nodes.size() > nodes_capacity) { g_err = "node capacity too small"; return MI_ERR_INVALID; }
+        if (!nodes.empty()) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(mi_bvh_node));
+        for (size_t i = 0; i < order.size(); ++i) ordered_out[i] = order[i];
+        *n_nodes = (uint32_t)nodes.size();
+        return MI_OK;
+    });
+}
+
+int mi_bvh_upper_sah(void *, uint32_t n_treelets, const float *root_bounds, const int32_t *treelet_sizes, mi_bvh_node *upper_nodes,
+                     int32_t *upper_index, uint32_t *n_upper, uint32_t *n_total, int32_t *treelet_offset) {
+    return Guarded([&]() -> int {
+        std::vector<mi_bvh_node> nodes;
+        std::vector<int> index;
+        const int total = BuildUpperSAH(n_treelets, root_bounds, treelet_sizes, &nodes, &index, treelet_offset);
+        if (nodes.size() > n_treelets) return MI_ERR_INVALID;   // (a binary tree over k leaves has k - 1 interior nodes)
+        for (size_t k = 0; k < nodes.size(); ++k) { upper_nodes[k] = nodes[k]; upper_index[k] = index[k]; }
+        *n_upper = (uint32_t)nodes.size();
+        *n_total = (uint32_t)total;
+        return MI_OK;
+    });
+}
+
 }  // extern "C"

@@ -77,18 +77,24 @@ bool LoopSubdivide(int nLevels, const std::vector<int> &indices, const std::vect
 // SAH BVH2 build + depth-first flatten, src/accelerators/bvh.cpp:183-402,640-658.
 struct BuildPrim { Bounds3 bounds; };
 enum class SplitMethod { SAH, Middle, EqualCounts, HLBVH };
-void BuildBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, SplitMethod method,
+// A leaf's count is 16 bits of the node: a leaf of more than kMaxLeafPrims primitives (that many share one centre, or one
+// Morton code) makes the builders return false with a message in *err and no tree (the reference CHECKs it away).
+constexpr int kMaxLeafPrims = 65535;
+bool BuildBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, SplitMethod method,
               std::vector<mi_bvh_node> *nodes, std::vector<int> *orderedPrims, int *interior,
-              int *leaves);
+              int *leaves, std::string *err);
 
 // HLBVH, src/accelerators/bvh.cpp:404-638, in the order one thread builds it (bvh.cpp in this directory). The pieces are
 // exposed because the device build (mi_bvh_build_hlbvh) shares the upper SAH tree and is tested against the host tree.
-void BuildHLBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, std::vector<mi_bvh_node> *nodes,
-                std::vector<int> *orderedPrims, int *interior, int *leaves);
+bool BuildHLBVH(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, std::vector<mi_bvh_node> *nodes,
+                std::vector<int> *orderedPrims, int *interior, int *leaves, std::string *err);
 int BuildUpperSAH(uint32_t nTreelets, const float *rootBounds, const int32_t *treeletSizes, std::vector<mi_bvh_node> *upperNodes,
                   std::vector<int> *upperIndex, int32_t *treeletOffset);   // returns the total node count
-// The same tree built by libmipt_hip.so's kernels (hlbvh_device.cpp); false (with `why`) when no device / library is there.
-bool BuildHLBVHOnDevice(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, int device, std::vector<mi_bvh_node> *nodes,
+// The same tree built by libmipt_hip.so's kernels (hlbvh_device.cpp). Built: the tree is there. Unavailable (with `why`): no
+// library or no device, the caller builds on the host. Failed (with `why`): the device build ran and refused the input or
+// met an error -- that is the scene's error, not a reason to build elsewhere.
+enum class DeviceBuild { Built, Unavailable, Failed };
+DeviceBuild BuildHLBVHOnDevice(const std::vector<Bounds3> &primBounds, int maxPrimsInNode, int device, std::vector<mi_bvh_node> *nodes,
                         std::vector<int> *orderedPrims, int *interior, int *leaves, double *seconds, std::string *why);
 
 // Halton tables, src/core/lowdiscrepancy.cpp:2490-2504 (+ rng.h PCG32, sampling.h Shuffle).
