@@ -201,14 +201,20 @@ struct Pool {
     uint32_t *shadeQ;          // slots to shade: MAX_CLASSES queues of n entries, one per shading class
     uint32_t *ovfQ;            // rays whose list of postponed quadrics overflowed: 3 queues of n entries (extend / shadow / MIS)
     uint32_t n;
-    DEV float &F(int plane, uint32_t slot) const { return f[(size_t)plane * n + slot]; }
+    // where (plane, slot) lies in f / i, in q and in r: the host reads single slots back through these (mi_pt_debug_path)
+    __host__ __device__ __forceinline__ size_t ScalarIndex(int plane, uint32_t slot) const { return (size_t)plane * n + slot; }
     // a slot's 8 quads of one spectrum are one 128-B line: [spectrum][slot][quad] ([slot][spectrum][quad], the
     // spectra of a slot in one page, measured the same)
-    DEV float4 &Q(int plane, uint32_t slot) const { return q[(((size_t)(plane >> 3) * n + slot) << 3) + (plane & 7)]; }
-    DEV float4 &R(int plane, uint32_t slot) const {
-        return plane < R_HIT ? r[(((size_t)(plane >> 1) * n + slot) << 1) + (plane & 1)] : r[(size_t)plane * n + slot];
+    __host__ __device__ __forceinline__ size_t QuadIndex(int plane, uint32_t slot) const { return (((size_t)(plane >> 3) * n + slot) << 3) + (plane & 7); }
+    __host__ __device__ __forceinline__ size_t RecordIndex(int plane, uint32_t slot) const {
+        return plane < R_HIT ? (((size_t)(plane >> 1) * n + slot) << 1) + (plane & 1) : (size_t)plane * n + slot;
     }
-    DEV int &I(int plane, uint32_t slot) const { return i[(size_t)plane * n + slot]; }
+    DEV float &F(int plane, uint32_t slot) const { return f[ScalarIndex(plane, slot)]; }
+    DEV float4 &Q(int plane, uint32_t slot) const { return q[QuadIndex(plane, slot)]; }
+    // (the choice is made here once more, between two references: with it inside the index alone k_trav<2>, k_trav<3> and
+    // k_shade come out with other register assignments and one to six instructions more or fewer)
+    DEV float4 &R(int plane, uint32_t slot) const { return plane < R_HIT ? r[RecordIndex(plane, slot)] : r[ScalarIndex(plane, slot)]; }
+    DEV int &I(int plane, uint32_t slot) const { return i[ScalarIndex(plane, slot)]; }
 };
 
 // Statistics are striped: STAT_STRIPES copies, each on its own 128-B line, picked by block
@@ -1067,21 +1073,10 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
 // (P_TENC*), and this replays the reference's sequence: quadric j is tested against min(that tMax, the closest quadric
 // accepted before it); a triangle hit that the traversal found AFTER the last accepted quadric survives only if it is
 // closer than that quadric. (Shadow rays: tMax never changes, the order does not matter.) On overflow the ray is
-// re-traversed by the reference-order routine with inline quadric tests.
-// OVF: the instance of k_resolve_overflow. The resolve kernels proper are compiled without the re-traversal (it cost
-// them 40-56 VGPRs and all but 650 of 12 000 instructions): they hand a ray whose list overflowed to that kernel.
-template <bool ANY, bool INST, bool OVF = false>
-DEV bool ResolveQuadrics(const DScene &s, const Pool &pool, uint32_t slot, const V3 &ro, const V3 &rd, float tMaxIn,
-                         Hit *h, bool foundTri, unsigned &nodes, unsigned &tris, int npGiven = -1) {
-    const int np = npGiven >= 0 ? npGiven : pool.I(I_NPEND, slot);
-    if constexpr (OVF) {
-        Hit h2;
-        h2.prim = -1; h2.t = 0; h2.b0 = h2.b1 = h2.b2 = 0;
-        unsigned n2 = 0, t2 = 0;  // statistics were already counted by k_trav
-        const bool found = Traverse<ANY, INST>(s, ro, rd, tMaxIn, &h2, n2, t2);
-        if (found) *h = h2;
-        return found;
-    }
+// re-traversed by the reference-order routine with inline quadric tests (Retraverse), in k_resolve_overflow alone: the
+// resolve kernels proper are compiled without it (it cost them 40-56 VGPRs and all but 650 of 12 000 instructions).
+template <bool ANY>
+DEV bool ResolveQuadrics(const DScene &s, const Pool &pool, uint32_t slot, const V3 &ro, const V3 &rd, float tMaxIn, Hit *h, bool foundTri, int np) {
     if (ANY) {
         for (int j = 0; j < (np & 0xff); ++j) {
             const int prim = pool.I(I_PEND0 + j, slot);
@@ -1103,6 +1098,27 @@ DEV bool ResolveQuadrics(const DScene &s, const Pool &pool, uint32_t slot, const
     h->prim = primBest; h->t = tBest; h->b0 = h->b1 = h->b2 = 0; h->inst = -1;
     return true;
 }
+// (*h is written only when something is hit)
+template <bool ANY, bool INST>
+DEV bool Retraverse(const DScene &s, const V3 &ro, const V3 &rd, float tMax, Hit *h) {
+    Hit h2;
+    h2.prim = -1; h2.t = 0; h2.b0 = h2.b1 = h2.b2 = 0;
+    unsigned n2 = 0, t2 = 0;  // statistics were already counted by k_trav
+    const bool found = Traverse<ANY, INST>(s, ro, rd, tMax, &h2, n2, t2);
+    if (found) *h = h2;
+    return found;
+}
+
+// A shadow or MIS ray in its two records: origin, direction (r1.z: the end of the light's span, MIS rays only)
+DEV V3 PackedRayO(const float4 &r0) { return V3(r0.x, r0.y, r0.z); }
+DEV V3 PackedRayD(const float4 &r0, const float4 &r1) { return V3(r0.w, r1.x, r1.y); }
+// Hit <-> the R_HIT record
+DEV float4 HitRecord(const Hit &h) { return make_float4(h.t, h.b0, h.b1, h.b2); }
+DEV void SetHitRecord(Hit *h, const float4 &hr) { h->t = hr.x; h->b0 = hr.y; h->b1 = hr.z; h->b2 = hr.w; }
+// The shading class of a hit primitive (mi_pt_create packs it into primTri[3 * prim].w); a miss has a class of its own.
+DEV int ClassOfPrim(const float4 *__restrict__ primTri, int prim) {
+    return (prim >= 0) ? (int)((__float_as_uint(primTri[3 * prim].w) >> PRIM_CLASS_SHIFT) & (unsigned)(MAX_CLASSES - 1)) : MISS_CLASS;
+}
 
 // Slots per block of the kernels that walk the whole pool (k_generate, k_resolve_extend): SLOT_CHUNKS x 256. Every block
 // ends in a returning atomicAdd on a queue cursor, and one word takes ~88 of those per microsecond whoever issues them
@@ -1119,6 +1135,14 @@ constexpr int SLOT_CHUNKS = MIPT_SLOT_CHUNKS;
 // builds benched after it in that call). The tuning macros are checked where they are defined.
 static_assert(SLOT_CHUNKS >= 1 && SLOT_CHUNKS <= 8, "MIPT_SLOT_CHUNKS: 1..8 (rank words of k_resolve_extend, chunk masks of k_generate)");
 static_assert(SLOT_CHUNKS * BLOCK / 2 + SLOT_CHUNKS * BLOCK / 4 <= BLOCK * 33, "k_generate: the free-slot list and its flags live in the flush rows");
+// The per-(chunk, wave) counts of a block, cnt[(ch * BLOCK / 64 + w) * stride], become their exclusive prefix in place; returns
+// the total, which the caller reserves on its queue cursor in one add. Run by one thread between two barriers.
+DEV unsigned ChunkWavePrefix(unsigned *cnt, int stride) {
+    unsigned tot = 0;
+    for (int ch = 0; ch < SLOT_CHUNKS; ++ch)
+        for (int w = 0; w < BLOCK / 64; ++w) { unsigned &e = cnt[(ch * (BLOCK / 64) + w) * stride]; const unsigned n = e; e = tot; tot += n; }
+    return tot;
+}
 
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, DevCounters *ctr) {
@@ -1131,13 +1155,9 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
     __shared__ unsigned short sPend[SLOT_CHUNKS * BLOCK];
     __shared__ unsigned sPendCount;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    unsigned nodes = 0, tris = 0;
     if (threadIdx.x == 0) sPendCount = 0;
     __syncthreads();
     const float4 *__restrict__ primTri = s.primTri;   // (by value: a reference to the kernel argument would move it to scratch)
-    auto classOf = [primTri](int prim) -> int {
-        return (prim >= 0) ? (int)((__float_as_uint(primTri[3 * prim].w) >> PRIM_CLASS_SHIFT) & (unsigned)(MAX_CLASSES - 1)) : MISS_CLASS;
-    };
     // ---- phase A: every slot's hit primitive; rays with a quadric list go onto the block's list
 #pragma unroll 1
     for (int ch = 0; ch < SLOT_CHUNKS; ++ch) {
@@ -1147,7 +1167,7 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
             const int npend = pool.I(I_NPEND, slot);
             if (npend & PEND_OVERFLOW) pool.ovfQ[atomicAdd(&ctr->ovfCount[0].v, 1u)] = slot;   // k_resolve_overflow commits this one
             else if (npend != 0) sPend[atomicAdd(&sPendCount, 1u)] = (unsigned short)(ch * BLOCK + threadIdx.x);
-            else cc = (unsigned char)(0x80 | classOf(pool.I(I_HITPRIM, slot)));
+            else cc = (unsigned char)(0x80 | ClassOfPrim(primTri, pool.I(I_HITPRIM, slot)));
         }
         sCls[ch][threadIdx.x] = cc;
     }
@@ -1162,14 +1182,14 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
         const float4 r0 = pool.R(R_RAY0, slot), r1 = pool.R(R_RAY1, slot), hr = pool.R(R_HIT, slot);
         V3 ro(r0.x, r0.y, r0.z), rd(r1.x, r1.y, r1.z);
         Hit h;
-        h.prim = prim; h.t = hr.x; h.b0 = hr.y; h.b1 = hr.z; h.b2 = hr.w;
+        h.prim = prim; SetHitRecord(&h, hr);
         if (INST) h.inst = pool.I(I_HITINST, slot);
-        const bool found = ResolveQuadrics<false, INST>(s, pool, slot, ro, rd, r0.w, &h, prim >= 0, nodes, tris);
+        const bool found = ResolveQuadrics<false>(s, pool, slot, ro, rd, r0.w, &h, prim >= 0, pool.I(I_NPEND, slot));
         prim = found ? h.prim : -1;
         pool.I(I_HITPRIM, slot) = prim;
-        pool.R(R_HIT, slot) = make_float4(h.t, h.b0, h.b1, h.b2);
+        pool.R(R_HIT, slot) = HitRecord(h);
         if (INST) pool.I(I_HITINST, slot) = h.inst;
-        sCls[e / BLOCK][e % BLOCK] = (unsigned char)(0x80 | classOf(prim));
+        sCls[e / BLOCK][e % BLOCK] = (unsigned char)(0x80 | ClassOfPrim(primTri, prim));
     }
     __syncthreads();
     // ---- phase C: ranks within (chunk, wave, class), the block's range of each class queue, the queue entries
@@ -1190,10 +1210,8 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
     }
     __syncthreads();
     if (threadIdx.x < MAX_CLASSES && ((s.classMask >> threadIdx.x) & 1)) {
-        const int c = threadIdx.x;   // exclusive prefix over (chunk, wave), then the block's range of queue c in one add
-        unsigned tot = 0;
-        for (int ch = 0; ch < SLOT_CHUNKS; ++ch)
-            for (int w = 0; w < BLOCK / 64; ++w) { const unsigned n = sCnt[ch][w][c]; sCnt[ch][w][c] = tot; tot += n; }
+        const int c = threadIdx.x;   // the block's range of queue c in one add
+        const unsigned tot = ChunkWavePrefix(&sCnt[0][0][c], MAX_CLASSES);
         sBase[c] = tot ? atomicAdd(&ctr->shadeCount[c].v, tot) : 0;
     }
     __syncthreads();
@@ -1208,10 +1226,22 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
     }
 }
 
+// A shadow ray's verdict on its slot's flags. L += contribution: the candidate line holds the sum already (F_CAND, written by
+// k_shade), an unoccluded ray makes it the path's L; an occluded one leaves L where it is. With a MIS ray pending
+// k_resolve_mis closes the estimate, else it ends here.
+DEV int CommitShadowVerdict(int flags, bool occluded, unsigned &zero) {
+    const bool added = !occluded && (flags & F_NEE_NZ);
+    if (!occluded) flags = (flags ^ F_L_IN_B) & ~F_L_ZERO;
+    flags &= ~(F_SHADOW | F_CAND | F_NEE_NZ);
+    if (flags & F_MIS) { if (added) flags |= F_A_ADDED; }
+    else { if (!added) ++zero; flags &= ~(F_NEE | F_A_ADDED); }
+    return flags;
+}
+
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_resolve_shadow(DScene s, Pool pool, DevCounters *ctr) {
     const uint32_t qi = blockIdx.x * BLOCK + threadIdx.x;
-    unsigned zero = 0, nodes = 0, tris = 0;
+    unsigned zero = 0;
     int myFlags = 0;
     uint32_t mySlot = 0;
     bool valid = false, doAdd = false;
@@ -1225,98 +1255,94 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_shadow(DScene s, Pool pool, D
         else {
             if (npend != 0) {
                 const float4 r0 = pool.R(R_SH0, slot), r1 = pool.R(R_SH1, slot);
-                V3 ro(r0.x, r0.y, r0.z), rd(r0.w, r1.x, r1.y);
                 Hit h;
-                occluded = ResolveQuadrics<true, INST>(s, pool, slot, ro, rd, 1 - kShadowEpsilon, &h, false, nodes, tris, npend);
+                occluded = ResolveQuadrics<true>(s, pool, slot, PackedRayO(r0), PackedRayD(r0, r1), 1 - kShadowEpsilon, &h, false, npend);
             }
             myFlags = flags; mySlot = slot; valid = true; doAdd = !occluded;
         }
     }
-    // L += contribution: the candidate line holds the sum already (F_CAND, written by k_shade), an unoccluded ray makes it the
-    // path's L; an occluded one leaves L where it is
-    if (valid) {
-        int flags = myFlags;
-        const bool added = doAdd && (flags & F_NEE_NZ);
-        if (doAdd) flags = (flags ^ F_L_IN_B) & ~F_L_ZERO;
-        flags &= ~(F_SHADOW | F_CAND | F_NEE_NZ);
-        if (flags & F_MIS) { if (added) flags |= F_A_ADDED; }   // k_resolve_mis closes the estimate
-        else { if (!added) ++zero; flags &= ~(F_NEE | F_A_ADDED); }
-        pool.I(I_FLAGS, mySlot) = flags;
-    }
+    if (valid) pool.I(I_FLAGS, mySlot) = CommitShadowVerdict(myFlags, !doAdd, zero);
     CountAdd(&Stats(ctr).zeroRadiancePaths, zero);
 }
 
+// L += the pending MIS contribution (Q_LMIS, written by k_shade); returns whether a bin of it was non-zero.
+DEV bool AddMisContribution(const Pool &pool, uint32_t slot, int &flags) {
+    bool added = false;
+    const bool lZero = (flags & F_L_ZERO) != 0;
+    for (int c = 0; c < NQ; ++c) {
+        const float4 a = pool.Q(Q_LMIS + c, slot);
+        added |= (a.x != 0.f) | (a.y != 0.f) | (a.z != 0.f) | (a.w != 0.f);
+        float4 l = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!lZero) l = pool.Q(LPlane(flags) + c, slot);
+        l.x += a.x; l.y += a.y; l.z += a.z; l.w += a.w;
+        pool.Q(LPlane(flags) + c, slot) = l;
+    }
+    flags &= ~F_L_ZERO;
+    return added;
+}
+// The MIS ray closes its vertex's direct-lighting estimate: zero radiance if neither it nor the light sample (F_A_ADDED) added.
+DEV void CloseMisEstimate(const Pool &pool, uint32_t slot, int flags, bool added, unsigned &zero) {
+    if (!added && !(flags & F_A_ADDED)) ++zero;
+    pool.I(I_FLAGS, slot) = flags & ~(F_NEE | F_MIS | F_A_ADDED | F_MIS_DARK);
+}
+
+// A MIS ray and the record of the hit k_trav<2> found for it (h.prim comes with the queue entry). They are fetched only by the
+// few rays that need them: postponed quadrics, or a hit on the sampled light whose facing has to be tested (most MIS rays hit
+// something else: 48 B of scattered reads saved)
+DEV void LoadMisRay(const Pool &pool, uint32_t slot, V3 &ro, V3 &rd, Hit &h, bool &have) {
+    if (have) return;
+    const float4 r0 = pool.R(R_MI0, slot), r1 = pool.R(R_MI1, slot), hr = pool.R(R_HIT, slot);
+    ro = PackedRayO(r0); rd = PackedRayD(r0, r1);
+    if (h.prim >= 0) SetHitRecord(&h, hr);
+    have = true;
+}
+// The closest hit of a MIS ray after its quadrics (h, when found). OVF: the list overflowed, the ray is traversed again.
+template <bool INST, bool OVF>
+DEV bool MisClosestHit(const DScene &s, const Pool &pool, uint32_t slot, int npend, V3 &ro, V3 &rd, Hit &h, bool &haveRay) {
+    bool found = h.prim >= 0;
+    if (npend != 0) {
+        LoadMisRay(pool, slot, ro, rd, h, haveRay);
+        if constexpr (OVF) found = Retraverse<false, INST>(s, ro, rd, kInfinity, &h);
+        else found = ResolveQuadrics<false>(s, pool, slot, ro, rd, kInfinity, &h, found, npend);
+    }
+    return found;
+}
 
 // One MIS ray's commit. OVF = false (k_resolve_mis): a ray whose quadric list overflowed goes to k_resolve_overflow, which
 // runs this again with OVF = true.
 template <bool INST, bool OVF>
 DEV void ResolveMisSlot(const DScene &s, const Pool &pool, DevCounters *ctr, uint32_t slot, int hitPrim, int npend, unsigned &zero) {
-    unsigned nodes = 0, tris = 0;
     int flags = pool.I(I_FLAGS, slot);
-    // the ray and the hit record are fetched only by the few rays that need them: postponed quadrics, or a hit on the
-    // sampled light whose facing has to be tested (most MIS rays hit something else: 48 B of scattered reads saved)
     V3 ro, rd;
     Hit h;
     h.prim = hitPrim; h.t = 0.f; h.b0 = h.b1 = h.b2 = 0.f;
     bool haveRay = false;
-    auto loadRay = [&]() {
-        if (haveRay) return;
-        const float4 r0 = pool.R(R_MI0, slot), r1 = pool.R(R_MI1, slot), hr = pool.R(R_HIT, slot);
-        ro = V3(r0.x, r0.y, r0.z); rd = V3(r0.w, r1.x, r1.y);
-        if (h.prim >= 0) { h.t = hr.x; h.b0 = hr.y; h.b1 = hr.z; h.b2 = hr.w; }
-        haveRay = true;
-    };
-    bool found = h.prim >= 0;
     if (!OVF && (npend & PEND_OVERFLOW)) { pool.ovfQ[2 * (size_t)pool.n + atomicAdd(&ctr->ovfCount[2].v, 1u)] = slot; return; }
-    if (npend != 0) { loadRay(); found = ResolveQuadrics<false, INST, OVF>(s, pool, slot, ro, rd, kInfinity, &h, found, nodes, tris, npend); }
+    const bool found = MisClosestHit<INST, OVF>(s, pool, slot, npend, ro, rd, h, haveRay);
     bool added = false;
     const int misLight = s.nLights > 1 ? pool.I(I_MISLIGHT, slot) : 0;
-    if (!found && s.lights[misLight].type == MI_LIGHT_INFINITE) {   // Li = light.Le(ray), integrator.cpp:204
-        const bool lZero = (flags & F_L_ZERO) != 0;
-        for (int c = 0; c < NQ; ++c) {
-            const float4 a = pool.Q(Q_LMIS + c, slot);
-            added |= (a.x != 0.f) | (a.y != 0.f) | (a.z != 0.f) | (a.w != 0.f);
-            float4 l = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!lZero) l = pool.Q(LPlane(flags) + c, slot);
-            l.x += a.x; l.y += a.y; l.z += a.z; l.w += a.w;
-            pool.Q(LPlane(flags) + c, slot) = l;
-        }
-        flags &= ~F_L_ZERO;
-    }
+    if (!found && s.lights[misLight].type == MI_LIGHT_INFINITE) added |= AddMisContribution(pool, slot, flags);   // Li = light.Le(ray), integrator.cpp:204
     if (found) {
         const int lightNum = misLight;
         if (s.prims[h.prim].area_light == lightNum && !(flags & F_MIS_DARK)) {   // (dark: cannot happen, the bounds are conservative)
             const mi_light &l = s.lights[lightNum];
             bool emit = l.two_sided != 0;
             if (!emit) {
-                loadRay();
+                LoadMisRay(pool, slot, ro, rd, h, haveRay);
                 SurfaceInteraction li;
                 HitInteraction(s, h.prim, ro, rd, h.b0, h.b1, h.b2, &li);
                 emit = Dot(li.n, -rd) > 0;
             }
-            if (emit) {
-                const bool lZero = (flags & F_L_ZERO) != 0;
-                for (int c = 0; c < NQ; ++c) {
-                    const float4 a = pool.Q(Q_LMIS + c, slot);
-                    added |= (a.x != 0.f) | (a.y != 0.f) | (a.z != 0.f) | (a.w != 0.f);
-                    float4 l = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (!lZero) l = pool.Q(LPlane(flags) + c, slot);
-                    l.x += a.x; l.y += a.y; l.z += a.z; l.w += a.w;
-                    pool.Q(LPlane(flags) + c, slot) = l;
-                }
-                flags &= ~F_L_ZERO;
-            }
+            if (emit) added |= AddMisContribution(pool, slot, flags);
         }
     }
-    if (!added && !(flags & F_A_ADDED)) ++zero;
-    pool.I(I_FLAGS, slot) = flags & ~(F_NEE | F_MIS | F_A_ADDED | F_MIS_DARK);
+    CloseMisEstimate(pool, slot, flags, added, zero);
 }
 // The commit of a MIS ray that k_trav<3> answered as a visibility query (DScene::misAny). word0: an occluder's primitive,
 // -1 (nothing accepted up to the end of the light's span) or -2 (something accepted inside the span). A ray that is
 // ambiguous, met a quadric on its way to an area light, or reaches a sphere whose root the reference could reject against a
 // hit beyond the span, goes to k_resolve_overflow: the closest-hit routine in the reference's order, then ResolveMisSlot.
 DEV void ResolveMisVisibility(const DScene &s, const Pool &pool, DevCounters *ctr, uint32_t slot, int word0, int npend, unsigned &zero) {
-    unsigned nodes = 0, tris = 0;
     int flags = pool.I(I_FLAGS, slot);
     const bool dark = (flags & F_MIS_DARK) != 0;   // (nothing reads the ray's answer)
     bool exact = !dark && (npend & PEND_OVERFLOW) != 0, add = false;
@@ -1328,14 +1354,14 @@ DEV void ResolveMisVisibility(const DScene &s, const Pool &pool, DevCounters *ct
             if (!found && (npend & 0xff)) {
                 const float4 r0 = pool.R(R_MI0, slot), r1 = pool.R(R_MI1, slot);
                 Hit h;
-                found = ResolveQuadrics<true, false, false>(s, pool, slot, V3(r0.x, r0.y, r0.z), V3(r0.w, r1.x, r1.y), kInfinity, &h, false, nodes, tris, npend);
+                found = ResolveQuadrics<true>(s, pool, slot, PackedRayO(r0), PackedRayD(r0, r1), kInfinity, &h, false, npend);
             }
             add = !found;
         } else if (word0 >= 0) {}           // a primitive in front of the light's span
         else if (word0 == -2 || (npend & 0xff)) exact = true;
         else {                              // nothing up to the end of the span: the light's shape, if the ray meets it, is the closest hit
             const float4 r0 = pool.R(R_MI0, slot), r1 = pool.R(R_MI1, slot);
-            const V3 ro(r0.x, r0.y, r0.z), rd(r0.w, r1.x, r1.y);
+            const V3 ro = PackedRayO(r0), rd = PackedRayD(r0, r1);
             if (l.shape < 0) {
                 const mi_sphere &sp = s.spheres[~l.shape];
                 SurfaceInteraction li;
@@ -1357,21 +1383,8 @@ DEV void ResolveMisVisibility(const DScene &s, const Pool &pool, DevCounters *ct
         }
     }
     if (exact) { pool.ovfQ[2 * (size_t)pool.n + atomicAdd(&ctr->ovfCount[2].v, 1u)] = slot; return; }
-    bool added = false;
-    if (add) {
-        const bool lZero = (flags & F_L_ZERO) != 0;
-        for (int c = 0; c < NQ; ++c) {
-            const float4 a = pool.Q(Q_LMIS + c, slot);
-            added |= (a.x != 0.f) | (a.y != 0.f) | (a.z != 0.f) | (a.w != 0.f);
-            float4 lq = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!lZero) lq = pool.Q(LPlane(flags) + c, slot);
-            lq.x += a.x; lq.y += a.y; lq.z += a.z; lq.w += a.w;
-            pool.Q(LPlane(flags) + c, slot) = lq;
-        }
-        flags &= ~F_L_ZERO;
-    }
-    if (!added && !(flags & F_A_ADDED)) ++zero;
-    pool.I(I_FLAGS, slot) = flags & ~(F_NEE | F_MIS | F_A_ADDED | F_MIS_DARK);
+    const bool added = add && AddMisContribution(pool, slot, flags);
+    CloseMisEstimate(pool, slot, flags, added, zero);
 }
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_resolve_mis(DScene s, Pool pool, DevCounters *ctr) {
@@ -1393,31 +1406,25 @@ constexpr int OVERFLOW_GRID = 512;
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool, DevCounters *ctr, int mode) {
     const unsigned count = ctr->ovfCount[mode].v;
-    unsigned zero = 0, nodes = 0, tris = 0;
+    unsigned zero = 0;
     for (unsigned qi = blockIdx.x * BLOCK + threadIdx.x; qi < count; qi += gridDim.x * BLOCK) {
         const uint32_t slot = pool.ovfQ[(size_t)mode * pool.n + qi];
         if (mode == 0) {
             const float4 r0 = pool.R(R_RAY0, slot), r1 = pool.R(R_RAY1, slot);
             Hit h;
             h.prim = -1; h.t = 0.f; h.b0 = h.b1 = h.b2 = 0.f;
-            const bool found = ResolveQuadrics<false, INST, true>(s, pool, slot, V3(r0.x, r0.y, r0.z), V3(r1.x, r1.y, r1.z), r0.w, &h, false, nodes, tris);
+            const bool found = Retraverse<false, INST>(s, V3(r0.x, r0.y, r0.z), V3(r1.x, r1.y, r1.z), r0.w, &h);
             const int prim = found ? h.prim : -1;
             pool.I(I_HITPRIM, slot) = prim;
-            pool.R(R_HIT, slot) = make_float4(h.t, h.b0, h.b1, h.b2);
+            pool.R(R_HIT, slot) = HitRecord(h);
             if (INST) pool.I(I_HITINST, slot) = h.inst;
-            const int cls = (prim >= 0) ? (int)((__float_as_uint(s.primTri[3 * prim].w) >> PRIM_CLASS_SHIFT) & (unsigned)(MAX_CLASSES - 1)) : MISS_CLASS;
+            const int cls = ClassOfPrim(s.primTri, prim);
             pool.shadeQ[(size_t)cls * pool.n + atomicAdd(&ctr->shadeCount[cls].v, 1u)] = slot;
         } else if (mode == 1) {
             const float4 r0 = pool.R(R_SH0, slot), r1 = pool.R(R_SH1, slot);
             Hit h;
-            const bool occluded = ResolveQuadrics<true, INST, true>(s, pool, slot, V3(r0.x, r0.y, r0.z), V3(r0.w, r1.x, r1.y), 1 - kShadowEpsilon, &h, false, nodes, tris);
-            int flags = pool.I(I_FLAGS, slot);
-            bool added = false;
-            if (!occluded) { added = (flags & F_NEE_NZ) != 0; flags = (flags ^ F_L_IN_B) & ~F_L_ZERO; }   // the candidate becomes L (k_resolve_shadow)
-            flags &= ~(F_SHADOW | F_CAND | F_NEE_NZ);
-            if (flags & F_MIS) { if (added) flags |= F_A_ADDED; }
-            else { if (!added) ++zero; flags &= ~(F_NEE | F_A_ADDED); }
-            pool.I(I_FLAGS, slot) = flags;
+            const bool occluded = Retraverse<true, INST>(s, PackedRayO(r0), PackedRayD(r0, r1), 1 - kShadowEpsilon, &h);
+            pool.I(I_FLAGS, slot) = CommitShadowVerdict(pool.I(I_FLAGS, slot), occluded, zero);
         } else
             ResolveMisSlot<INST, true>(s, pool, ctr, slot, -1, PEND_OVERFLOW, zero);   // (re-traversed from scratch)
     }
@@ -1514,19 +1521,12 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {   // exclusive prefix over (chunk, wave) and the block's range of the work list in one add
-        unsigned tot = 0;
-        for (int ch = 0; ch < SLOT_CHUNKS; ++ch)
-            for (int w = 0; w < BLOCK / 64; ++w) { const unsigned n = sWant[ch][w]; sWant[ch][w] = tot; tot += n; }
+    if (threadIdx.x == 0) {   // the block's range of the work list in one add
+        const unsigned tot = ChunkWavePrefix(&sWant[0][0], 1);
         sWorkBase = tot ? atomicAdd(&ctr->nextWork, (unsigned long long)tot) : ~0ull;
         sTotWant = tot;
     }
-    if (threadIdx.x == 64) {
-        unsigned tot = 0;
-        for (int ch = 0; ch < SLOT_CHUNKS; ++ch)
-            for (int w = 0; w < BLOCK / 64; ++w) { const unsigned n = sFinCnt[ch][w]; sFinCnt[ch][w] = tot; tot += n; }
-        sTotFin = tot;
-    }
+    if (threadIdx.x == 64) sTotFin = ChunkWavePrefix(&sFinCnt[0][0], 1);
     __syncthreads();
 #pragma unroll 1
     for (int ch = 0; ch < SLOT_CHUNKS; ++ch) {
@@ -1813,10 +1813,7 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
     }
     __syncthreads();
     if (threadIdx.x < 2) {
-        unsigned (*cnt)[BLOCK / 64] = threadIdx.x == 0 ? sPrim : sCont;
-        unsigned tot = 0;
-        for (int ch = 0; ch < SLOT_CHUNKS; ++ch)
-            for (int w = 0; w < BLOCK / 64; ++w) { const unsigned n = cnt[ch][w]; cnt[ch][w] = tot; tot += n; }
+        const unsigned tot = ChunkWavePrefix(threadIdx.x == 0 ? &sPrim[0][0] : &sCont[0][0], 1);
         const unsigned base = tot ? atomicAdd(threadIdx.x == 0 ? &ctr->primCount.v : &ctr->contCount.v, tot) : 0;
         if (threadIdx.x == 0) sPrimBase = base; else sContBase = base;
     }
@@ -2832,8 +2829,8 @@ __global__ void __launch_bounds__(BLOCK) k_trace_raw(Pool pool, uint32_t n, int 
     extra[4 * (size_t)i + 3] = __int_as_float(pool.I(I_HITPRIM, i));
 }
 // The committed answer. Mode 0: the planes as k_resolve_extend / k_resolve_overflow left them. Mode 1: k_resolve_shadow's
-// verdict (see k_trace_load). Mode 2: k_resolve_mis consumes its hit in place (ResolveMisSlot), so the quadric step is run
-// here with the same device function and arguments it uses.
+// verdict (see k_trace_load). Mode 2: k_resolve_mis consumes its hit in place (ResolveMisSlot), so its quadric step
+// (MisClosestHit) is run here.
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_trace_read(DScene s, Pool pool, uint32_t n, int mode, float *hits, float *extra) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
@@ -2844,18 +2841,16 @@ __global__ void __launch_bounds__(BLOCK) k_trace_read(DScene s, Pool pool, uint3
     else if (mode == 1) prim = (pool.I(I_FLAGS, i) & F_L_ZERO) ? 0 : -1;
     else if (mode == 3) {}   // (k_trav<3>'s verdict as it stands: an occluder, -1, -2 = ambiguous; -3 = never answered)
     else {
-        const float4 r0 = pool.R(R_MI0, i), r1 = pool.R(R_MI1, i);
-        const V3 ro(r0.x, r0.y, r0.z), rd(r0.w, r1.x, r1.y);
-        hr = pool.R(R_HIT, i);
+        V3 ro, rd;
         Hit h;
-        h.prim = prim; h.t = hr.x; h.b0 = hr.y; h.b1 = hr.z; h.b2 = hr.w;
-        bool found = prim >= 0;
-        unsigned nodes = 0, tris = 0;
+        h.prim = prim; h.t = 0.f; h.b0 = h.b1 = h.b2 = 0.f;
+        bool haveRay = false;
+        LoadMisRay(pool, i, ro, rd, h, haveRay);   // (at once: the hit is recorded here whether it has quadrics or not)
         const int npend = (int)pool.misQ[pool.n + 2 * (size_t)i + 1];
-        if (npend & PEND_OVERFLOW) found = ResolveQuadrics<false, INST, true>(s, pool, i, ro, rd, kInfinity, &h, found, nodes, tris);
-        else if (npend != 0) found = ResolveQuadrics<false, INST, false>(s, pool, i, ro, rd, kInfinity, &h, found, nodes, tris, npend);
+        const bool found = (npend & PEND_OVERFLOW) ? MisClosestHit<INST, true>(s, pool, i, npend, ro, rd, h, haveRay)
+                                                   : MisClosestHit<INST, false>(s, pool, i, npend, ro, rd, h, haveRay);
         prim = found ? h.prim : -1;
-        hr = make_float4(h.t, h.b0, h.b1, h.b2);
+        hr = HitRecord(h);
         inst = h.inst;
     }
     const bool rec = prim >= 0 && mode != 1 && mode != 3;
@@ -3047,6 +3042,11 @@ int Alloc(mi_pt *pt, size_t bytes, T **dst, const char *what) {
     *dst = (T *)p;
     return MI_OK;
 }
+
+// Spectral quad planes of a path slot: spectralpath keeps one set more, the stitched spectrum of the camera sample (Q_LCA).
+int QuadPlanes(const DScene &s) { return Q_COUNT + (s.nBands > 1 ? NQ : 0); }
+// Samples per pixel of one pass.
+long long PassSpp(const mi_pt *pt, const mi_render_params *rp) { return rp->spp_override > 0 ? rp->spp_override : pt->spp; }
 
 // Device bytes of one path slot: planes, records, spectra and its entries in the queues.
 size_t PoolSlotBytes(int nQuadPlanes) {
@@ -3907,7 +3907,7 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
     wd.shardIndex = rp->shard_index + rp->shard_count * subIndex;
     wd.shardCount = rp->shard_count * subCount;
     wd.nTilesShard = (wd.shardIndex < nTiles) ? (nTiles - wd.shardIndex + wd.shardCount - 1) / wd.shardCount : 0;
-    wd.spp = rp->spp_override > 0 ? rp->spp_override : pt->spp;
+    wd.spp = PassSpp(pt, rp);
     wd.sampleBegin = rp->sample_begin;
     wd.totalWork = (unsigned long long)wd.nTilesShard * 256ull * (unsigned long long)wd.spp;
     int runCap = 256;  // (round 3, with the dense film flush: 64 -> 256 takes 5 % off k_generate, killeroo +0.9 %, the 10M-triangle scene
@@ -3947,18 +3947,18 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
             const size_t budget = (size_t)(0.65 * (double)(freeB + sub.poolBytes)) / (size_t)subCount;
-            const size_t fit = budget / PoolSlotBytes(Q_COUNT + (s.nBands > 1 ? NQ : 0)) / BLOCK * BLOCK;
+            const size_t fit = budget / PoolSlotBytes(QuadPlanes(s)) / BLOCK * BLOCK;
             if (fit < poolN) poolN = (uint32_t)std::max<size_t>(fit, (size_t)BLOCK);
         } else (void)hipGetLastError();
     }
     if (wd.totalWork < poolN) poolN = (uint32_t)((wd.totalWork + BLOCK - 1) / BLOCK * BLOCK);
     if (poolN < BLOCK) poolN = BLOCK;
-    int rc = EnsurePool(sub, poolN, Q_COUNT + (s.nBands > 1 ? NQ : 0));
+    int rc = EnsurePool(sub, poolN, QuadPlanes(s));
     // the default size is a preference, not a requirement: on a device that cannot hold it the render goes on with half,
     // a quarter, ... (an explicit mi_render_params.path_pool is taken at its word and fails)
     while (rc == MI_ERR_NOMEM && rp->path_pool == 0 && poolN > (1u << 22)) {
         poolN = poolN / 2 / BLOCK * BLOCK;
-        rc = EnsurePool(sub, poolN, Q_COUNT + (s.nBands > 1 ? NQ : 0));
+        rc = EnsurePool(sub, poolN, QuadPlanes(s));
     }
     if (rc != MI_OK) return rc;
     HIPCHK(hipMemsetAsync(sub.pool.i + (size_t)I_FLAGS * poolN, 0, (size_t)poolN * sizeof(int), st));
@@ -4026,21 +4026,21 @@ int mi_pt_render(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *
     if (!pt || !rp) { g_err = "null argument"; return MI_ERR_INVALID; }
     if (rp->shard_count < 1 || rp->shard_index < 0 || rp->shard_index >= rp->shard_count) { g_err = "bad shard"; return MI_ERR_INVALID; }
     {   // sample numbers are ints in the path state (I_SAMPLE) and in the oracle: [sample_begin, sample_begin + spp) stays below 2^31 - 1
-        const long long passSpp = rp->spp_override > 0 ? rp->spp_override : pt->spp;
+        const long long passSpp = PassSpp(pt, rp);
         if (rp->sample_begin < 0 || rp->sample_begin > 0x7fffffffll || passSpp > 0x7fffffffll - rp->sample_begin) {
             g_err = "sample numbers out of range: sample_begin >= 0 and sample_begin + spp <= 2^31 - 1";
             return MI_ERR_INVALID;
         }
     }
     if (pt->scene.samplerType >= MI_SAMPLER_ZEROTWO &&
-        (rp->sample_begin < 0 || rp->sample_begin + (rp->spp_override > 0 ? rp->spp_override : pt->spp) > pt->spp)) {
+        (rp->sample_begin < 0 || rp->sample_begin + PassSpp(pt, rp) > pt->spp)) {
         g_err = "a pixel sampler (02sequence / stratified) has tables for samples_per_pixel samples: the pass asks for sample numbers beyond them";
         return MI_ERR_INVALID;
     }
     HIPCHK(hipSetDevice(pt->device));
     {   // what this pass lets the kernels leave out (DScene::index32 / storePixelSample)
         DScene &sc = pt->scene;
-        const unsigned long long lastSample = (unsigned long long)rp->sample_begin + (unsigned long long)(rp->spp_override > 0 ? rp->spp_override : pt->spp);
+        const unsigned long long lastSample = (unsigned long long)rp->sample_begin + (unsigned long long)PassSpp(pt, rp);
         sc.index32 = (sc.samplerType == MI_SAMPLER_HALTON && (lastSample + 1ull) * (unsigned long long)std::max(1, sc.sampleStride) < (1ull << 32)) ? 1 : 0;
         sc.storePixelSample = (sc.samplerType >= MI_SAMPLER_RANDOM || sc.nBands > 1 || (pt->nTextures > 0 && sc.camera.lens_radius > 0)) ? 1 : 0;
     }
@@ -4190,7 +4190,7 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
     wd.sampleBegin = sample;
     wd.totalWork = 256;
     const uint32_t poolN = BLOCK;
-    int rc = EnsurePool(sub, poolN, Q_COUNT + (s.nBands > 1 ? NQ : 0));
+    int rc = EnsurePool(sub, poolN, QuadPlanes(s));
     if (rc != MI_OK) return rc;
     HIPCHK(hipMemsetAsync(sub.pool.i + (size_t)I_FLAGS * poolN, 0, (size_t)poolN * sizeof(int), st));
     HIPCHK(hipMemsetAsync(sub.ctr, 0, sizeof(DevCounters), st));
@@ -4198,14 +4198,11 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
     const dim3 grid(1), block(BLOCK), travGrid(1);
     const Pool &pool = sub.pool;
     std::vector<int> flags(poolN);
-    auto F4 = [&](int plane, uint32_t slot, float *dst) {   // Pool::R
-        const float4 *src = plane < R_HIT ? pool.r + ((((size_t)(plane >> 1) * poolN + slot) << 1) + (plane & 1)) : pool.r + (size_t)plane * poolN + slot;
-        return hipMemcpy(dst, src, 16, hipMemcpyDeviceToHost);
-    };
-    auto I1 = [&](int plane, uint32_t slot, int *dst) { return hipMemcpy(dst, pool.i + (size_t)plane * poolN + slot, 4, hipMemcpyDeviceToHost); };
+    auto F4 = [&](int plane, uint32_t slot, float *dst) { return hipMemcpy(dst, pool.r + pool.RecordIndex(plane, slot), 16, hipMemcpyDeviceToHost); };
+    auto I1 = [&](int plane, uint32_t slot, int *dst) { return hipMemcpy(dst, pool.i + pool.ScalarIndex(plane, slot), 4, hipMemcpyDeviceToHost); };
     auto Spec = [&](int set, uint32_t slot, float *dst31) {
         float line[32];
-        hipError_t e = hipMemcpy(line, pool.q + (((size_t)(set >> 3) * poolN + slot) << 3), 128, hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(line, pool.q + pool.QuadIndex(set, slot), 128, hipMemcpyDeviceToHost);
         memcpy(dst31, line, 31 * sizeof(float));
         return e;
     };
@@ -4315,7 +4312,7 @@ int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, fl
     hipStream_t st = sub.stream;
     const DScene &s = pt->scene;
     const uint32_t poolN = (n + SLOT_CHUNKS * BLOCK - 1) / (SLOT_CHUNKS * BLOCK) * (SLOT_CHUNKS * BLOCK);
-    int rc = EnsurePool(sub, poolN, Q_COUNT + (s.nBands > 1 ? NQ : 0));
+    int rc = EnsurePool(sub, poolN, QuadPlanes(s));
     if (rc != MI_OK) return rc;
     struct PoolGuard { SubRenderer &sub; ~PoolGuard() { FreePool(sub.pool); sub.poolQuadPlanes = 0; } } guard{sub};   // the next render sizes its own
     DevBuf dr, dh, dx;

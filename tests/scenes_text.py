@@ -511,15 +511,20 @@ WorldEnd
 """
 
 
-def sphere_row_scene(res=48, spp=16, depth=12):
+def sphere_row_scene(res=48, spp=16, depth=12, instanced=False):
     """Rays that meet more quadrics than the traversal kernel's per-ray list holds (MAX_PEND = 4): a row of spheres
-    along the view axis, glass ones in front (the path goes on through them), partial ones (phimax) among them."""
+    along the view axis, glass ones in front (the path goes on through them), partial ones (phimax) among them.
+    instanced: the same row once more as an object instance beside it. The traversal tests an instance's quadrics inline,
+    so the world-level row still overflows the lists, now in the kernels compiled for scenes with instances."""
     row = []
     for i in range(9):
         mat = 'Material "glass" "float index" [1.3]' if i < 6 else 'Material "matte" "rgb Kd" [.2 .6 .3]'
         extra = ' "float phimax" [300]' if i in (2, 5) else ""
         row.append('AttributeBegin\n  %s\n  Translate %.2f 1 %.1f\n  Shape "sphere" "float radius" [.7]%s\nAttributeEnd' % (mat, 0.05 * i, -4 + 2.0 * i, extra))
-    return SPHERE_ROW_SCENE % dict(res=res, spp=spp, depth=depth, row="\n".join(row))
+    row = "\n".join(row)
+    if instanced:
+        row += '\nObjectBegin "row"\n%s\nObjectEnd\nAttributeBegin\n  Translate 1.6 0 0.5\n  ObjectInstance "row"\nAttributeEnd' % row
+    return SPHERE_ROW_SCENE % dict(res=res, spp=spp, depth=depth, row=row)
 
 
 ROUGHNESS_SCENE = """

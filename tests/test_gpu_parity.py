@@ -670,14 +670,20 @@ def test_a_pool_that_cannot_be_allocated_is_an_error_and_leaves_the_renderer_usa
     assert all(c[k] == o[k] for k in ("camera_rays", "regular_rays", "shadow_rays", "total_paths"))
 
 
-def test_rays_with_more_quadrics_than_the_pending_list_holds(pt, ob):
+@pytest.mark.parametrize("instanced", [False, True], ids=["world", "instanced"])
+def test_rays_with_more_quadrics_than_the_pending_list_holds(pt, ob, instanced):
     """k_trav postpones the quadrics a ray meets (four per ray); a ray that meets more is handed to k_resolve_overflow, which
     re-traverses it in the reference's order with inline quadric tests and commits it like the resolve kernel would have:
     closest-hit, shadow and MIS rays. Exact-mode parity on a row of nine spheres along the view axis, and equal recorded
-    rays along that axis."""
-    s = pt.Scene(text=st.sphere_row_scene())
-    assert s.errors == [] and s.desc.n_spheres == 10
-    film, weight, integ, ofilm, oweight, oc = _parity(pt, ob, s, "sphere row (quadric list overflow)")
+    rays along that axis. With the row once more as an object instance beside it, the same through the kernels compiled for
+    scenes with instances (only world-level quadrics are postponed: those of an instance are tested inline)."""
+    if instanced:
+        s = pt.Scene(text=st.sphere_row_scene(res=24, spp=8, instanced=True))
+        assert s.errors == [] and s.desc.n_spheres == 19 and s.desc.n_instances == 1
+    else:
+        s = pt.Scene(text=st.sphere_row_scene())
+        assert s.errors == [] and s.desc.n_spheres == 10
+    film, weight, integ, ofilm, oweight, oc = _parity(pt, ob, s, "sphere row (quadric list overflow)" + (", instance beside it" if instanced else ""))
     rng = np.random.default_rng(9)
     n = 3000
     o = np.tile(np.array([0, 1, -9], np.float32), (n, 1)) + rng.normal(0, .05, (n, 3)).astype(np.float32)
