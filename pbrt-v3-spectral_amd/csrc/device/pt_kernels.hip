@@ -1120,6 +1120,19 @@ DEV int ClassOfPrim(const float4 *__restrict__ primTri, int prim) {
     return (prim >= 0) ? (int)((__float_as_uint(primTri[3 * prim].w) >> PRIM_CLASS_SHIFT) & (unsigned)(MAX_CLASSES - 1)) : MISS_CLASS;
 }
 
+// A vertex at which the path ends with nothing to shade and no emitted light to look up (path.cpp:91-101 looks for emitted
+// light only at the camera ray's vertex and after a specular bounce): the ray escaped and there is no environment light or
+// no look-up is owed, or it hit something at the depth limit and no look-up is owed. A third of killeroo's path rays end so:
+// the resolve step finishes their slots itself (FinishedWord) and the shading queues never see them.
+DEV bool EndsUnshaded(int word, int prim, int maxDepth, int nInfiniteLights) {
+    const int bounces = StateBounces(word);
+    const bool emitCheck = bounces == 0 || (word & F_SPECULAR);
+    return prim < 0 ? (!emitCheck || nInfiniteLights == 0) : (bounces >= maxDepth && !emitCheck);
+}
+// The state word of a path that ends with no estimate pending: which line holds L and what is still implicit are carried
+// over, bounces (ReportValue(pathLength, bounces)) and the sampler dimension stay.
+DEV int FinishedWord(int word) { return StateWord(F_FINISHED | (word & (F_L_IN_B | F_L_ZERO | F_BETA_ONE)), StateBounces(word), StateDim(word)); }
+
 // Slots per block of the kernels that walk the whole pool (k_generate, k_resolve_extend): SLOT_CHUNKS x 256. Every block
 // ends in a returning atomicAdd on a queue cursor, and one word takes ~88 of those per microsecond whoever issues them
 // (MI355X_MICROARCH.md, "dequeue"): with one 256-slot chunk per block a 32M-slot pool sent 131k adds to each cursor per
@@ -1155,6 +1168,7 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
     __shared__ unsigned short sPend[SLOT_CHUNKS * BLOCK];
     __shared__ unsigned sPendCount;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned pathLen = 0;   // bounces of the paths that end here
     if (threadIdx.x == 0) sPendCount = 0;
     __syncthreads();
     const float4 *__restrict__ primTri = s.primTri;   // (by value: a reference to the kernel argument would move it to scratch)
@@ -1163,11 +1177,16 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
     for (int ch = 0; ch < SLOT_CHUNKS; ++ch) {
         const uint32_t slot = (blockIdx.x * SLOT_CHUNKS + ch) * BLOCK + threadIdx.x;
         unsigned char cc = 0;
-        if (slot < pool.n && (pool.I(I_FLAGS, slot) & F_ALIVE)) {
+        const int word = slot < pool.n ? pool.I(I_FLAGS, slot) : 0;
+        if (word & F_ALIVE) {
             const int npend = pool.I(I_NPEND, slot);
             if (npend & PEND_OVERFLOW) pool.ovfQ[atomicAdd(&ctr->ovfCount[0].v, 1u)] = slot;   // k_resolve_overflow commits this one
             else if (npend != 0) sPend[atomicAdd(&sPendCount, 1u)] = (unsigned short)(ch * BLOCK + threadIdx.x);
-            else cc = (unsigned char)(0x80 | ClassOfPrim(primTri, pool.I(I_HITPRIM, slot)));
+            else {
+                const int prim = pool.I(I_HITPRIM, slot);
+                if (EndsUnshaded(word, prim, s.maxDepth, s.nInfiniteLights)) { pool.I(I_FLAGS, slot) = FinishedWord(word); pathLen += (unsigned)StateBounces(word); }
+                else cc = (unsigned char)(0x80 | ClassOfPrim(primTri, prim));
+            }
         }
         sCls[ch][threadIdx.x] = cc;
     }
@@ -1189,7 +1208,9 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
         pool.I(I_HITPRIM, slot) = prim;
         pool.R(R_HIT, slot) = HitRecord(h);
         if (INST) pool.I(I_HITINST, slot) = h.inst;
-        sCls[e / BLOCK][e % BLOCK] = (unsigned char)(0x80 | ClassOfPrim(primTri, prim));
+        const int word = pool.I(I_FLAGS, slot);
+        if (EndsUnshaded(word, prim, s.maxDepth, s.nInfiniteLights)) { pool.I(I_FLAGS, slot) = FinishedWord(word); pathLen += (unsigned)StateBounces(word); }   // (sCls stays 0)
+        else sCls[e / BLOCK][e % BLOCK] = (unsigned char)(0x80 | ClassOfPrim(primTri, prim));
     }
     __syncthreads();
     // ---- phase C: ranks within (chunk, wave, class), the block's range of each class queue, the queue entries
@@ -1224,6 +1245,7 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_extend(DScene s, Pool pool, D
         const uint32_t slot = (blockIdx.x * SLOT_CHUNKS + ch) * BLOCK + threadIdx.x;
         pool.shadeQ[(size_t)cls * pool.n + sBase[cls] + sCnt[ch][wave][cls] + rank] = slot;
     }
+    CountAdd(&Stats(ctr).pathLengthSum, pathLen);
 }
 
 // A shadow ray's verdict on its slot's flags. L += contribution: the candidate line holds the sum already (F_CAND, written by
@@ -1240,28 +1262,23 @@ DEV int CommitShadowVerdict(int flags, bool occluded, unsigned &zero) {
 
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_resolve_shadow(DScene s, Pool pool, DevCounters *ctr) {
-    const uint32_t qi = blockIdx.x * BLOCK + threadIdx.x;
+    // (the grid is sized by what is resident, LaunchResolve: each block walks the queue in steps of the grid)
+    const unsigned count = ctr->shadowCount.v;
     unsigned zero = 0;
-    int myFlags = 0;
-    uint32_t mySlot = 0;
-    bool valid = false, doAdd = false;
-    if (qi < ctr->shadowCount.v) {
+    for (uint32_t qi = blockIdx.x * BLOCK + threadIdx.x; qi < count; qi += gridDim.x * BLOCK) {
         const uint32_t slot = pool.shadowQ[qi];
-        int flags = pool.I(I_FLAGS, slot);
+        const int flags = pool.I(I_FLAGS, slot);
         const unsigned verdict = pool.shadowQ[pool.n + qi];   // k_trav<1>'s answer, in queue order
         bool occluded = (verdict >> 31) != 0u;
         const int npend = occluded ? 0 : (int)(verdict & 0x7fffffffu);
-        if (npend & PEND_OVERFLOW) pool.ovfQ[(size_t)pool.n + atomicAdd(&ctr->ovfCount[1].v, 1u)] = slot;   // k_resolve_overflow commits this one
-        else {
-            if (npend != 0) {
-                const float4 r0 = pool.R(R_SH0, slot), r1 = pool.R(R_SH1, slot);
-                Hit h;
-                occluded = ResolveQuadrics<true>(s, pool, slot, PackedRayO(r0), PackedRayD(r0, r1), 1 - kShadowEpsilon, &h, false, npend);
-            }
-            myFlags = flags; mySlot = slot; valid = true; doAdd = !occluded;
+        if (npend & PEND_OVERFLOW) { pool.ovfQ[(size_t)pool.n + atomicAdd(&ctr->ovfCount[1].v, 1u)] = slot; continue; }   // k_resolve_overflow commits this one
+        if (npend != 0) {
+            const float4 r0 = pool.R(R_SH0, slot), r1 = pool.R(R_SH1, slot);
+            Hit h;
+            occluded = ResolveQuadrics<true>(s, pool, slot, PackedRayO(r0), PackedRayD(r0, r1), 1 - kShadowEpsilon, &h, false, npend);
         }
+        pool.I(I_FLAGS, slot) = CommitShadowVerdict(flags, occluded, zero);
     }
-    if (valid) pool.I(I_FLAGS, mySlot) = CommitShadowVerdict(myFlags, !doAdd, zero);
     CountAdd(&Stats(ctr).zeroRadiancePaths, zero);
 }
 
@@ -1388,9 +1405,9 @@ DEV void ResolveMisVisibility(const DScene &s, const Pool &pool, DevCounters *ct
 }
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_resolve_mis(DScene s, Pool pool, DevCounters *ctr) {
-    const uint32_t qi = blockIdx.x * BLOCK + threadIdx.x;
+    const unsigned count = ctr->misCount.v;   // (a resident-sized grid walks the queue, as in k_resolve_shadow)
     unsigned zero = 0;
-    if (qi < ctr->misCount.v) {
+    for (uint32_t qi = blockIdx.x * BLOCK + threadIdx.x; qi < count; qi += gridDim.x * BLOCK) {
         const uint2 v = *reinterpret_cast<const uint2 *>(pool.misQ + pool.n + 2 * (size_t)qi);   // k_trav<2>'s / k_trav<3>'s answer, in queue order
         if (!INST && s.misAny) ResolveMisVisibility(s, pool, ctr, pool.misQ[qi], (int)v.x, (int)v.y, zero);
         else ResolveMisSlot<INST, false>(s, pool, ctr, pool.misQ[qi], (int)v.x, (int)v.y, zero);
@@ -1406,7 +1423,7 @@ constexpr int OVERFLOW_GRID = 512;
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool, DevCounters *ctr, int mode) {
     const unsigned count = ctr->ovfCount[mode].v;
-    unsigned zero = 0;
+    unsigned zero = 0, pathLen = 0;
     for (unsigned qi = blockIdx.x * BLOCK + threadIdx.x; qi < count; qi += gridDim.x * BLOCK) {
         const uint32_t slot = pool.ovfQ[(size_t)mode * pool.n + qi];
         if (mode == 0) {
@@ -1418,8 +1435,12 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool,
             pool.I(I_HITPRIM, slot) = prim;
             pool.R(R_HIT, slot) = HitRecord(h);
             if (INST) pool.I(I_HITINST, slot) = h.inst;
-            const int cls = ClassOfPrim(s.primTri, prim);
-            pool.shadeQ[(size_t)cls * pool.n + atomicAdd(&ctr->shadeCount[cls].v, 1u)] = slot;
+            const int word = pool.I(I_FLAGS, slot);
+            if (EndsUnshaded(word, prim, s.maxDepth, s.nInfiniteLights)) { pool.I(I_FLAGS, slot) = FinishedWord(word); pathLen += (unsigned)StateBounces(word); }
+            else {
+                const int cls = ClassOfPrim(s.primTri, prim);
+                pool.shadeQ[(size_t)cls * pool.n + atomicAdd(&ctr->shadeCount[cls].v, 1u)] = slot;
+            }
         } else if (mode == 1) {
             const float4 r0 = pool.R(R_SH0, slot), r1 = pool.R(R_SH1, slot);
             Hit h;
@@ -1429,6 +1450,7 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool,
             ResolveMisSlot<INST, true>(s, pool, ctr, slot, -1, PEND_OVERFLOW, zero);   // (re-traversed from scratch)
     }
     CountAdd(&Stats(ctr).zeroRadiancePaths, zero);
+    CountAdd(&Stats(ctr).pathLengthSum, pathLen);
 }
 
 // ------------------------------------------------------------------ generate
@@ -1958,7 +1980,8 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
         const bool found = prim >= 0;
         auto loadBeta = [&](int c) -> float4 { return LoadBeta(pool, c, slot, betaOne); };
         // the ray and the interaction are needed by vertices that will be shaded or may show emitted light; an escaped
-        // ray without environment lights and a path at its last vertex need neither (a third of the queue entries)
+        // ray without environment lights and a path at its last vertex need neither (k_resolve_extend ends those itself and
+        // does not queue them, EndsUnshaded: what this kernel writes for one, below, is FinishedWord)
         const bool emitCheck = bounces == 0 || (flags & F_SPECULAR);
         const bool needIsect = found && (bounces < s.maxDepth || emitCheck);
         const bool needRay = needIsect || (!found && emitCheck && TM_LIGHT(TM, MI_LIGHT_INFINITE) && s.nInfiniteLights > 0);
@@ -2997,6 +3020,10 @@ struct mi_pt {
     bool hasInfiniteLight = false;   // picks the kernels compiled with the environment-light code
     unsigned shadeClasses[N_SHADE_INSTANCES] = {0};   // per k_shade instance: the shading classes it runs (ShadeInstanceOf)
     int numCUs = 256;
+    // k_resolve_shadow and k_resolve_mis walk their queues on grids sized by what the device holds at once (QueueGrid):
+    // resident blocks per CU of each, from the occupancy query at create
+    int resolveBlocksPerCU[3] = {0};    // [1]: k_resolve_shadow, [2]: k_resolve_mis ([0], k_resolve_extend, walks the pool)
+    unsigned queueBlocksCap = 0;        // MIPT_QUEUE_BLOCKS (tests): at most so many blocks for those kernels, 0 = unset
 };
 
 namespace {
@@ -3837,15 +3864,44 @@ void LaunchTraversal(mi_pt *pt, SubRenderer &sub, int mode, dim3 travGrid, bool 
     hipLaunchKernelGGL(k, travGrid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr);
 }
 
+// The grid of a kernel that walks a queue in steps of the grid (k_resolve_shadow, k_resolve_mis): QUEUE_GRID_RESIDENT times the
+// blocks the device holds at once, at most the `poolBlocks` that cover the longest queue there can be. A block that finds
+// its queue ended is not free, and a pool-sized grid has 390 k of them (0.18 ms per launch, however short the queue).
+// MIPT_QUEUE_BLOCKS (read at every render; for tests) caps the grid.
+#ifndef MIPT_QUEUE_GRID_RESIDENT
+#define MIPT_QUEUE_GRID_RESIDENT 4
+#endif
+constexpr unsigned QUEUE_GRID_RESIDENT = MIPT_QUEUE_GRID_RESIDENT;
+static_assert(QUEUE_GRID_RESIDENT >= 1 && QUEUE_GRID_RESIDENT <= 64, "MIPT_QUEUE_GRID_RESIDENT: 1..64");
+dim3 QueueGrid(const mi_pt *pt, int blocksPerCU, unsigned poolBlocks) {
+    unsigned want = (unsigned)pt->numCUs * (unsigned)std::max(1, blocksPerCU) * QUEUE_GRID_RESIDENT;
+    if (pt->queueBlocksCap) want = std::min(want, pt->queueBlocksCap);
+    return dim3(std::max(1u, std::min(want, poolBlocks)));
+}
+void ReadQueueBlocksCap(mi_pt *pt) {
+    const char *e = getenv("MIPT_QUEUE_BLOCKS");
+    pt->queueBlocksCap = e ? (unsigned)std::max(0, atoi(e)) : 0u;
+}
 // The resolve kernels of the three ray classes, by [class][instanced].
 const SceneKernel kResolve[3][2] = {{k_resolve_extend<false>, k_resolve_extend<true>},
                                     {k_resolve_shadow<false>, k_resolve_shadow<true>},
                                     {k_resolve_mis<false>, k_resolve_mis<true>}};
 
+// Resident blocks per CU of the two resolve kernels that walk a queue.
+int QueryQueueOccupancy(mi_pt *pt) {
+    for (int mode = 1; mode < 3; ++mode) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kResolve[mode][pt->hasInstances ? 1 : 0], BLOCK, 0) != hipSuccess || nb < 1) { g_err = "occupancy query failed"; return MI_ERR_HIP; }
+        pt->resolveBlocksPerCU[mode] = nb;
+    }
+    return MI_OK;
+}
+
 // What follows the traversal of ray class `mode` (0: path rays, 1: shadow rays, 2: MIS rays): its resolve kernel on `grid`,
 // then k_resolve_overflow for the rays that the quadric lists or the visibility queries (MODE 3) handed over.
 void LaunchResolve(mi_pt *pt, SubRenderer &sub, int mode, dim3 grid) {
     const bool inst = pt->hasInstances;
+    if (mode != 0) grid = QueueGrid(pt, pt->resolveBlocksPerCU[mode], grid.x);   // (k_resolve_extend takes the pool's slots, not a queue)
     hipLaunchKernelGGL(kResolve[mode][inst ? 1 : 0], grid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr);
     if (pt->hasQuadrics || (mode == 2 && pt->scene.misAny))
         hipLaunchKernelGGL((inst ? k_resolve_overflow<true> : k_resolve_overflow<false>), dim3(OVERFLOW_GRID), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, mode);
@@ -3883,6 +3939,7 @@ int mi_pt_create(const mi_scene_desc *d, int device_ordinal, mi_pt **out) {
     rc = UploadScene(pt, d, h);
     if (rc == MI_OK) rc = BuildDeviceTables(pt, d);
     if (rc == MI_OK) rc = CreateRenderState(pt, d);
+    if (rc == MI_OK) rc = QueryQueueOccupancy(pt);
     if (rc != MI_OK) {   // the one exit of a failed create: whatever was built is registered in pt
         mi_pt_destroy(pt);
         return rc;
@@ -4038,6 +4095,7 @@ int mi_pt_render(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *
         return MI_ERR_INVALID;
     }
     HIPCHK(hipSetDevice(pt->device));
+    ReadQueueBlocksCap(pt);
     {   // what this pass lets the kernels leave out (DScene::index32 / storePixelSample)
         DScene &sc = pt->scene;
         const unsigned long long lastSample = (unsigned long long)rp->sample_begin + (unsigned long long)PassSpp(pt, rp);
@@ -4171,6 +4229,7 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
     if (!pt || !records || !n_records || max_records < 1) { g_err = "null argument"; return MI_ERR_INVALID; }
     *n_records = 0;
     HIPCHK(hipSetDevice(pt->device));
+    ReadQueueBlocksCap(pt);
     const DScene saved = pt->scene;
     struct Restore { mi_pt *pt; DScene s; ~Restore() { pt->scene = s; } } restore{pt, saved};
     DScene &s = pt->scene;
@@ -4308,6 +4367,7 @@ int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, fl
         }
     }
     HIPCHK(hipSetDevice(pt->device));
+    ReadQueueBlocksCap(pt);
     SubRenderer &sub = pt->subs[0];
     hipStream_t st = sub.stream;
     const DScene &s = pt->scene;
