@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define MI_NSPEC 31
-#define MI_ABI_VERSION 10
+#define MI_ABI_VERSION 11
 #define MI_MAX_BXDFS 8 /* BSDF::MaxBxDFs, src/core/reflection.h:196 */
 
 typedef enum mi_status {
@@ -362,7 +362,30 @@ typedef struct mi_integrator {
                                * paths per camera sample on consecutive sampler dimensions, band s supplying
                                * spectrum bins [round(31/n)*s, min(round(31/n)*(s+1), 31))
                                * (src/integrators/spectralpath.cpp:258-318, 366) */
+    /* ABI v11 -- Integrator "metadata" (src/integrators/metadata.cpp:52-111): one closest-hit query per camera sample, the
+     * answer written into every bin of the sample's spectrum. mi_pt_render renders radiance whatever `kind` says; the maps
+     * are rendered by mi_pt_render_metadata. */
+    int32_t kind;              /* mi_integrator_kind */
+    int32_t metadata_strategy; /* mi_metadata_strategy: the scene file's "string strategy" */
 } mi_integrator;
+typedef enum mi_integrator_kind { MI_INTEGRATOR_PATH = 0 /* "path" / "spectralpath" */, MI_INTEGRATOR_METADATA = 1 } mi_integrator_kind;
+typedef enum mi_metadata_strategy {
+    MI_METADATA_DEPTH = 0,      /* all bins: (isect.p - ray.o).Length(), metadata.cpp:62-66 */
+    MI_METADATA_MATERIAL = 1,   /* all bins: isect.materialId */
+    MI_METADATA_MESH = 2,       /* all bins: isect.instanceId */
+    MI_METADATA_COORDINATES = 3 /* bins 0, 1, 2: isect.p.x, .y, .z (world); the other bins 0 */
+} mi_metadata_strategy;
+
+/* ABI v11 -- the identifiers the reference's SurfaceInteraction carries, one entry per mi_prim (parallel to
+ * mi_scene_desc.prims; mi_prim itself stays 16 bytes). material_id: the construction number of the primitive's Material
+ * object (material.h:54: the counter starts at 1; in a `pbrt scene.pbrt` process the scene's default matte is number 2);
+ * 0 for a primitive without a material (the reference dereferences a null pointer there, primitive.cpp:125).
+ * instance_id: the 1-based number of the ObjectInstance call the primitive was created by (api.cpp:1589-1614,
+ * primitive.cpp:89), 0 outside instances -- and 0 in every entry of a scene whose instances are TransformedPrimitives
+ * (mi_instance): there the id is the hit's instance + 1. */
+typedef struct mi_prim_meta {
+    uint32_t material_id, instance_id;
+} mi_prim_meta;
 
 typedef struct mi_scene_desc {
     uint32_t abi_version; /* MI_ABI_VERSION */
@@ -388,6 +411,7 @@ typedef struct mi_scene_desc {
     uint32_t n_textures; const mi_texture *textures;   /* ABI v5 */
     uint32_t n_mipmaps;  const mi_mipmap *mipmaps;
     uint32_t n_instances; const mi_instance *instances; /* ABI v7 */
+    const mi_prim_meta *prim_meta; /* ABI v11: [n_prims], may be NULL (then mi_pt_render_metadata refuses) */
 } mi_scene_desc;
 
 /* Counters with the reference's STAT names (src/core/integrator.cpp:48,
@@ -431,6 +455,18 @@ int mi_pt_create(const mi_scene_desc *scene, int device_ordinal, mi_pt **out);
  * Either may be NULL. Blocks until done. */
 int mi_pt_render(mi_pt *pt, const mi_render_params *params, float *film_sum,
                  float *weight_sum, mi_counters *counters);
+/* Integrator "metadata" (src/integrators/metadata.cpp:52-89 inside SamplerIntegrator::Render, integrator.cpp:277-323): one
+ * closest-hit query per camera sample of the pass, its answer by `strategy` (mi_metadata_strategy) in the sample's spectrum,
+ * which then passes the same guards (a NaN, y() < -1e-5 or an infinite y() blackens the sample and counts as bad; a
+ * `coordinates` sample at negative x, y or z is not one of them: SampledSpectrum::y() clamps its weighted sum at 0,
+ * spectrum.h:418, so the sample keeps its value, as in the reference) and the same filter as a radiance sample. A miss is
+ * L = 0. Film buffers, flags, shards, sample ranges, pool size and stream as in mi_pt_render; the strategy is an argument of
+ * the render, so one created renderer serves the radiance render and all four maps (mi_scene_desc.prim_meta goes to the
+ * device at the first call). Counters: camera_rays = regular_rays = samples; shadow_rays, total_paths,
+ * zero_radiance_paths, path_length_sum = 0; bad_samples = samples the guards blackened. Not with "spectralpath" bands:
+ * the pass traces one ray per camera sample. */
+int mi_pt_render_metadata(mi_pt *pt, const mi_render_params *params, int strategy, float *film_sum, float *weight_sum,
+                          mi_counters *counters);
 /* Device pointer of the resident film (layout [H*W][32]: 31 bins + weight) so a
  * collective can reduce in place; element count returned through n_floats. */
 int mi_pt_device_film(mi_pt *pt, void **dev_ptr, uint64_t *n_floats);

@@ -44,6 +44,17 @@ void mi_scene_get_stats(const mi_scene *s, mi_scene_stats *out);
 /* i-th warning (kind 0) / error (kind 1) message, NULL past the end. */
 const char *mi_scene_message(const mi_scene *s, int kind, int i);
 const char *mi_scene_film_filename(const mi_scene *s);
+/* Integrator "metadata": the names behind the ids of the `mesh` and `material` maps.
+ * mi_scene_instance_name: the object name of the i-th ObjectInstance call in file order (instance id i + 1), NULL past the end.
+ * mi_scene_named_material: the i-th MakeNamedMaterial name in the order the reference iterates them (std::map order) and,
+ * through *id, its material id; NULL past the end.
+ * mi_scene_write_metadata_names: what the reference writes at WorldEnd beside the film file `film_filename`
+ * (api.cpp:1640-1686) -- strategy `mesh`: "<stem>_mesh.txt", one line "<k> <instance name>" per instance, k from 1;
+ * strategy `material`: "<stem>_materials.txt", one line "<id> <name>" per named material; other strategies and other
+ * integrators: nothing. <stem> is film_filename up to its last '.'. */
+const char *mi_scene_instance_name(const mi_scene *s, int i);
+const char *mi_scene_named_material(const mi_scene *s, int i, uint32_t *id);
+int mi_scene_write_metadata_names(const mi_scene *s, const char *film_filename);
 void mi_scene_free(mi_scene *s);
 const char *mi_scene_last_error(void);
 
@@ -73,7 +84,9 @@ int mi_film_read_dat(const char *filename, int *w, int *h, float *data, uint64_t
 
 /* Integrator-shaped entry: what `integrator->Render(*scene)` (src/core/api.cpp:1707)
  * does for Integrator "path": dlopen()s libmipt_hip.so, creates the device
- * renderer, renders all tiles and writes the film file. Fails loudly
+ * renderer, renders all tiles and writes the film file. A scene with Integrator "metadata"
+ * (mi_integrator.kind) gets its name file first, then the map of the file's strategy
+ * (mi_pt_render_metadata) through the same film writers. Fails loudly
  * (MI_ERR_NO_DEVICE / MI_ERR_HIP) when the HIP library or a GPU is missing --
  * there is no CPU fallback. */
 int mi_integrator_render(const mi_scene *s, int device_ordinal, const char *outfile, mi_counters *counters);

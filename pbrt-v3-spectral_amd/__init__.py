@@ -120,7 +120,11 @@ class Sampler(C.Structure):
 
 class Integrator(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("rr_threshold", C.c_float), ("pixel_bounds", C.c_int32 * 4),
-                ("n_ca_bands", C.c_int32)]
+                ("n_ca_bands", C.c_int32), ("kind", C.c_int32), ("metadata_strategy", C.c_int32)]
+
+
+class PrimMeta(C.Structure):
+    _fields_ = [("material_id", C.c_uint32), ("instance_id", C.c_uint32)]
 
 
 class SceneDesc(C.Structure):
@@ -139,7 +143,8 @@ class SceneDesc(C.Structure):
                 ("n_envmaps", C.c_uint32), ("envmaps", C.POINTER(EnvMap)), ("rgb_illum", (C.c_float * NSPEC) * 7),
                 ("n_textures", C.c_uint32), ("textures", C.POINTER(Texture)),
                 ("n_mipmaps", C.c_uint32), ("mipmaps", C.POINTER(MipMap)),
-                ("n_instances", C.c_uint32), ("instances", C.POINTER(Instance))]
+                ("n_instances", C.c_uint32), ("instances", C.POINTER(Instance)),
+                ("prim_meta", C.POINTER(PrimMeta))]
 
 
 class Counters(C.Structure):
@@ -169,6 +174,9 @@ class SceneStats(C.Structure):
                                           "n_lights", "n_materials", "n_warnings", "n_errors", "accel_on_device")]
 
 
+INTEGRATOR_PATH, INTEGRATOR_METADATA = 0, 1
+METADATA_STRATEGIES = ("depth", "material", "mesh", "coordinates")   # mi_metadata_strategy 0..3
+
 RENDER_FILM_ON_DEVICE = 1
 RENDER_ACCUMULATE = 2
 
@@ -197,6 +205,11 @@ def host_lib():
         lib.mi_scene_message.restype = C.c_char_p
         lib.mi_scene_film_filename.argtypes = [C.c_void_p]
         lib.mi_scene_film_filename.restype = C.c_char_p
+        lib.mi_scene_instance_name.argtypes = [C.c_void_p, C.c_int]
+        lib.mi_scene_instance_name.restype = C.c_char_p
+        lib.mi_scene_named_material.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]
+        lib.mi_scene_named_material.restype = C.c_char_p
+        lib.mi_scene_write_metadata_names.argtypes = [C.c_void_p, C.c_char_p]
         lib.mi_scene_free.argtypes = [C.c_void_p]
         lib.mi_scene_last_error.restype = C.c_char_p
         lib.mi_film_write_dat.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float]
@@ -217,6 +230,8 @@ def hip_lib():
         lib.mi_pt_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_void_p)]
         lib.mi_pt_render.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      C.POINTER(Counters)]
+        lib.mi_pt_render_metadata.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float), C.POINTER(Counters)]
         lib.mi_pt_device_film.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         lib.mi_pt_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
         lib.mi_pt_pool_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -303,6 +318,33 @@ class Scene:
         return host_lib().mi_scene_film_filename(self._h).decode()
 
     @property
+    def instance_names(self):
+        """Object names of the ObjectInstance calls in file order: the `mesh` map's id k + 1 is instance_names[k]."""
+        out = []
+        while True:
+            m = host_lib().mi_scene_instance_name(self._h, len(out))
+            if m is None:
+                return out
+            out.append(m.decode())
+
+    @property
+    def named_material_ids(self):
+        """[(name, material id)] of the MakeNamedMaterial names, in the order the reference lists them (sorted by name)."""
+        out = []
+        while True:
+            mid = C.c_uint32()
+            m = host_lib().mi_scene_named_material(self._h, len(out), C.byref(mid))
+            if m is None:
+                return out
+            out.append((m.decode(), int(mid.value)))
+
+    def write_metadata_names(self, film_filename):
+        """The name file the reference writes beside the film of an Integrator "metadata" scene: <stem>_mesh.txt (strategy
+        mesh) or <stem>_materials.txt (strategy material); nothing for the other strategies (mi_scene_write_metadata_names)."""
+        if host_lib().mi_scene_write_metadata_names(self._h, os.fsencode(film_filename)) != 0:
+            raise RuntimeError("metadata name file: %s" % host_lib().mi_scene_last_error().decode())
+
+    @property
     def film_size(self):
         cb = self.desc.film.cropped_bounds
         return cb[2] - cb[0], cb[3] - cb[1]
@@ -342,24 +384,41 @@ class PathIntegrator:
         """Render sample numbers [sample_begin, sample_begin+spp) of this shard's tiles.
         film_out / weight_out: optional device pointers (ints) that receive the film sums
         (e.g. torch CUDA tensors' data_ptr()) instead of a host download."""
+        return self._render(None, shard_index, shard_count, spp, path_pool, download, accumulate, sample_begin, film_out,
+                            weight_out)
+
+    def RenderMetadata(self, strategy, shard_index=0, shard_count=1, spp=0, path_pool=0, download=True, accumulate=False,
+                       sample_begin=0, film_out=None, weight_out=None):
+        """One map of Integrator "metadata" on this renderer's uploaded scene (mi_pt_render_metadata): `strategy` is
+        "depth", "material", "mesh" or "coordinates" (or its number). The other arguments and the returned film sums are
+        Render()'s; metadata_image() turns them into the map."""
+        return self._render(_strategy_number(strategy), shard_index, shard_count, spp, path_pool, download, accumulate,
+                            sample_begin, film_out, weight_out)
+
+    def _render(self, strategy, shard_index, shard_count, spp, path_pool, download, accumulate, sample_begin, film_out,
+                weight_out):
+        lib = hip_lib()
+
+        def call(rp, film, weight):
+            if strategy is None:
+                name, rc = "mi_pt_render", lib.mi_pt_render(self._h, C.byref(rp), film, weight, C.byref(self.counters))
+            else:
+                name, rc = "mi_pt_render_metadata", lib.mi_pt_render_metadata(self._h, C.byref(rp), strategy, film, weight,
+                                                                             C.byref(self.counters))
+            if rc != 0:
+                raise RuntimeError("%s failed (%d): %s" % (name, rc, lib.mi_pt_last_error().decode()))
+
         if film_out is not None:
             rp = RenderParams(shard_index, shard_count, (RENDER_ACCUMULATE if accumulate else 0) | RENDER_FILM_ON_DEVICE,
                               path_pool, spp, sample_begin, None)
-            rc = hip_lib().mi_pt_render(self._h, C.byref(rp), C.cast(film_out, C.POINTER(C.c_float)),
-                                        C.cast(weight_out, C.POINTER(C.c_float)) if weight_out else None,
-                                        C.byref(self.counters))
-            if rc != 0:
-                raise RuntimeError("mi_pt_render failed (%d): %s" % (rc, hip_lib().mi_pt_last_error().decode()))
+            call(rp, C.cast(film_out, C.POINTER(C.c_float)), C.cast(weight_out, C.POINTER(C.c_float)) if weight_out else None)
             return None, None
         w, h = self.scene.film_size
         film = np.zeros((h, w, NSPEC), np.float32) if download else None
         weight = np.zeros((h, w), np.float32) if download else None
         rp = RenderParams(shard_index, shard_count, RENDER_ACCUMULATE if accumulate else 0, path_pool, spp,
                           sample_begin, None)
-        rc = hip_lib().mi_pt_render(self._h, C.byref(rp), _fptr(film) if download else None,
-                                    _fptr(weight) if download else None, C.byref(self.counters))
-        if rc != 0:
-            raise RuntimeError("mi_pt_render failed (%d): %s" % (rc, hip_lib().mi_pt_last_error().decode()))
+        call(rp, _fptr(film) if download else None, _fptr(weight) if download else None)
         return film, weight
 
     def timings(self):
@@ -443,8 +502,49 @@ def math_probe(op, x, y=None, device=0):
     return out
 
 
+def _strategy_number(strategy):
+    if isinstance(strategy, str):
+        if strategy not in METADATA_STRATEGIES:
+            raise ValueError("metadata strategy %r: one of %s" % (strategy, ", ".join(METADATA_STRATEGIES)))
+        return METADATA_STRATEGIES.index(strategy)
+    if int(strategy) not in range(len(METADATA_STRATEGIES)):
+        raise ValueError("metadata strategy %r out of range" % (strategy,))
+    return int(strategy)
+
+
+class MetadataIntegrator(PathIntegrator):
+    """Host mirror of ``MetadataIntegrator`` for ``Integrator "metadata"`` (src/integrators/metadata.cpp): ``Render()``
+    gives the film sums of one map -- depth, material id, instance id or world coordinates of each camera sample's closest
+    hit. ``strategy=None`` renders the scene file's strategy."""
+
+    def Render(self, shard_index=0, shard_count=1, spp=0, path_pool=0, download=True, accumulate=False,
+               sample_begin=0, film_out=None, weight_out=None, strategy=None):
+        if strategy is None:
+            strategy = int(self.scene.desc.integrator.metadata_strategy)
+        return self.RenderMetadata(strategy, shard_index, shard_count, spp, path_pool, download, accumulate, sample_begin,
+                                   film_out, weight_out)
+
+
+def metadata_image(film, weight, strategy):
+    """The map of a metadata render: film sums divided by the filter-weight sums (0 where no sample fell). [H, W] for
+    depth, material and mesh (every bin holds the value: bin 0 is taken), [H, W, 3] for coordinates (bins 0, 1, 2)."""
+    k = _strategy_number(strategy)
+    film = np.asarray(film, np.float32)
+    w = np.asarray(weight, np.float32)[..., None]
+    img = np.divide(film[..., :3], w, out=np.zeros_like(film[..., :3]), where=w != 0)
+    return img if METADATA_STRATEGIES[k] == "coordinates" else img[..., 0]
+
+
 def CreatePathIntegrator(scene, device=0):
     """Factory named after the reference's (src/integrators/path.h:69-71)."""
+    return PathIntegrator(scene, device)
+
+
+def CreateIntegrator(scene, device=0):
+    """The integrator the scene file names (MakeIntegrator, src/core/api.cpp:1750-1800): MetadataIntegrator for
+    Integrator "metadata", PathIntegrator otherwise."""
+    if int(scene.desc.integrator.kind) == INTEGRATOR_METADATA:
+        return MetadataIntegrator(scene, device)
     return PathIntegrator(scene, device)
 
 

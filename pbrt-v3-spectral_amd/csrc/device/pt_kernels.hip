@@ -2892,6 +2892,87 @@ __global__ void k_film_split(const float *film32, float *filmSum, float *weightS
     if (b < 31) { if (filmSum) filmSum[pix * 31 + b] = v; }
     else if (weightSum) weightSum[pix] = v;
 }
+
+// ------------------------------------------------------------------ metadata
+// Integrator "metadata" (MetadataIntegrator::Li, src/integrators/metadata.cpp:52-89): a pass is k_generate -> k_trav<0> ->
+// k_resolve_extend (+ k_resolve_overflow) -> this kernel, and the camera ray's closest hit is the whole answer. Every slot
+// that is still alive after the resolve step -- a hit, or a miss that an environment light kept in the miss class -- ends
+// here: a hit gets its value by `strategy` (mi_metadata_strategy) in the line that holds the path's L, a miss keeps L = 0
+// (F_L_ZERO), and the state word is FinishedWord's, so the next k_generate flushes the slot through the guards of
+// SamplerIntegrator::Render and the filter like any radiance (integrator.cpp:277-323; the ray weight of the perspective
+// camera is 1). isect.p is rebuilt by the routines k_shade uses -- HitInteraction with the ray of the space the hit lies in,
+// InteractionToWorld for a hit inside an instance -- so it is the point shading sees, bit for bit. `primMeta`: the ids of
+// every primitive, parallel to DScene::prims (mi_prim_meta); the instance id of a hit reached through a
+// TransformedPrimitive is that instance's number + 1 (primitive.cpp:89).
+//
+// Stores: the pool is walked densely and a slot's spectrum is one 128-B line. A lane that stores its own eight quads issues
+// eight instructions of 64 scattered 16-B pieces (measured: 1.77 ms per launch on 31 M slots); here the lanes park their
+// values in LDS (four words say what all 32 are) and the wave stores eight lanes per line, every instruction covering whole
+// lines (SpectrumTile's pattern in k_shade): 1.09 ms. DESIGN.md 5b has the measurement.
+// Quad c of the spectrum {a, b, c, rest, rest, ..., rest} (bin 31 is padding and stays 0), given as v = (a, b, c, rest).
+DEV float4 MetadataQuad(const float4 &v, int c) {
+    if (c == 0) return v;
+    return make_float4(v.w, v.w, v.w, c == NQ - 1 ? 0.f : v.w);
+}
+template <bool INST>
+__global__ void __launch_bounds__(BLOCK) k_commit_metadata(DScene s, Pool pool, const mi_prim_meta *__restrict__ primMeta, int strategy) {
+    const uint32_t slot = blockIdx.x * BLOCK + threadIdx.x;
+    const int word = slot < pool.n ? pool.I(I_FLAGS, slot) : 0;
+    bool wrote = false;
+    float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
+    if ((word & F_ALIVE) && !(word & F_FINISHED)) {
+        const int prim = pool.I(I_HITPRIM, slot);
+        if (prim >= 0 && (uint32_t)prim < s.nPrims) {
+            if (strategy == MI_METADATA_MATERIAL || strategy == MI_METADATA_MESH) {
+                unsigned id = strategy == MI_METADATA_MATERIAL ? primMeta[prim].material_id : primMeta[prim].instance_id;
+                if (INST && strategy == MI_METADATA_MESH) {
+                    const int inst = pool.I(I_HITINST, slot);
+                    if (inst >= 0) id = (unsigned)inst + 1u;
+                }
+                const float v = (float)id;   // L = Spectrum(isect.materialId) / Spectrum(isect.instanceId), metadata.cpp:71-75
+                val = make_float4(v, v, v, v);
+            } else {
+                const float4 ray0 = pool.R(R_RAY0, slot), ray1 = pool.R(R_RAY1, slot), hr = pool.R(R_HIT, slot);
+                const V3 ro(ray0.x, ray0.y, ray0.z), rd(ray1.x, ray1.y, ray1.z);
+                int inst = -1;
+                V3 roS = ro, rdS = rd;   // the ray in the space the hit shape was intersected in (as in k_shade)
+                if (INST) {
+                    inst = pool.I(I_HITINST, slot);
+                    if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
+                }
+                SurfaceInteraction isect;
+                HitInteraction(s, prim, roS, rdS, hr.y, hr.z, hr.w, &isect);
+                if (INST) { if (inst >= 0) InteractionToWorld(s.instances[inst], &isect); }
+                if (strategy == MI_METADATA_DEPTH) {
+                    const V3 toIntersect = isect.p - ro;   // metadata.cpp:68-69
+                    const float v = toIntersect.Length();
+                    val = make_float4(v, v, v, v);
+                } else
+                    val = make_float4(isect.p.x, isect.p.y, isect.p.z, 0.f);   // L[0..2] = isect.p, metadata.cpp:79-81
+            }
+            wrote = true;
+        }
+        pool.I(I_FLAGS, slot) = FinishedWord(wrote ? word & ~F_L_ZERO : word);
+    }
+    const int lPlane = LPlane(word);
+    __shared__ float4 sVal[BLOCK];
+    __shared__ uint32_t sLine[BLOCK];   // the line of the slot's L: its first quad is pool.q[line * NQ]
+    const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
+    const unsigned long long wmask = __ballot(wrote);
+    const int nW = __popcll(wmask);
+    if (wrote) {
+        const int rw = __popcll(wmask & ((1ull << lane) - 1ull));
+        sVal[wbase + rw] = val;
+        sLine[wbase + rw] = (uint32_t)(pool.QuadIndex(lPlane, slot) >> 3);
+    }
+    // (the exchange stays inside the wave, whose LDS accesses complete in order: the fence only keeps the compiler from moving them)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int c = lane & 7;
+    for (int e = lane >> 3; e < nW; e += 8)   // eight lanes per path: one store instruction covers eight whole lines
+        pool.q[((size_t)sLine[wbase + e] << 3) + c] = MetadataQuad(sVal[wbase + e], c);
+}
+
 #endif   // MIPT_HAS_MAIN
 
 // Every k_shade instance, in launch order (LaunchShade): X(part, NL, TM). The part is the MIPT_PART that compiles the
@@ -3024,6 +3105,12 @@ struct mi_pt {
     // resident blocks per CU of each, from the occupancy query at create
     int resolveBlocksPerCU[3] = {0};    // [1]: k_resolve_shadow, [2]: k_resolve_mis ([0], k_resolve_extend, walks the pool)
     unsigned queueBlocksCap = 0;        // MIPT_QUEUE_BLOCKS (tests): at most so many blocks for those kernels, 0 = unset
+    // Integrator "metadata" (mi_pt_render_metadata): the ids of the primitives as create copied them, their device copy
+    // (made by the first metadata pass: a renderer that only renders radiance holds none) and, during such a pass, its
+    // strategy (-1: a radiance render)
+    std::vector<mi_prim_meta> primMetaHost;
+    const mi_prim_meta *primMeta = nullptr;
+    int metaStrategy = -1;
 };
 
 namespace {
@@ -3717,6 +3804,7 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     pt->nTextures = d->n_textures;
     for (uint32_t i = 0; i < d->n_textures; ++i) pt->textureTypes.push_back(d->textures[i].type);
     pt->spp = d->sampler.samples_per_pixel;
+    if (d->prim_meta) pt->primMetaHost.assign(d->prim_meta, d->prim_meta + d->n_prims);
 }
 
 // The description's arrays and the host tables into device memory. Environment maps and image pyramids go as their
@@ -3907,6 +3995,12 @@ void LaunchResolve(mi_pt *pt, SubRenderer &sub, int mode, dim3 grid) {
         hipLaunchKernelGGL((inst ? k_resolve_overflow<true> : k_resolve_overflow<false>), dim3(OVERFLOW_GRID), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, mode);
 }
 
+// The last stage of a metadata pass (instead of LaunchShade and the shadow and MIS stages): every slot, one per thread.
+void LaunchMetadataCommit(mi_pt *pt, SubRenderer &sub, dim3 grid) {
+    hipLaunchKernelGGL((pt->hasInstances ? k_commit_metadata<true> : k_commit_metadata<false>), grid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool,
+                       pt->primMeta, pt->metaStrategy);
+}
+
 void LaunchShade(mi_pt *pt, SubRenderer &sub, dim3 grid) {
     const dim3 shadeGrid(grid.x + MAX_CLASSES);
     for (int i = 0; i < N_SHADE_INSTANCES; ++i)
@@ -4060,14 +4154,21 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         HIPCHK(hipEventRecord(ev[6], st));
         LaunchResolve(pt, sub, 0, chunkGrid);
         HIPCHK(hipEventRecord(ev[2], st));
-        LaunchShade(pt, sub, grid);
-        HIPCHK(hipEventRecord(ev[3], st));
-        LaunchTraversal(pt, sub, 1, travGrid);
-        LaunchResolve(pt, sub, 1, grid);
-        HIPCHK(hipEventRecord(ev[4], st));
-        LaunchTraversal(pt, sub, 2, travGrid);
-        LaunchResolve(pt, sub, 2, grid);
-        HIPCHK(hipEventRecord(ev[5], st));
+        if (pt->metaStrategy >= 0) {   // a metadata pass: the hit is the answer (its commit is timed as the shade class; no shadow or MIS rays)
+            LaunchMetadataCommit(pt, sub, grid);
+            HIPCHK(hipEventRecord(ev[3], st));
+            HIPCHK(hipEventRecord(ev[4], st));
+            HIPCHK(hipEventRecord(ev[5], st));
+        } else {
+            LaunchShade(pt, sub, grid);
+            HIPCHK(hipEventRecord(ev[3], st));
+            LaunchTraversal(pt, sub, 1, travGrid);
+            LaunchResolve(pt, sub, 1, grid);
+            HIPCHK(hipEventRecord(ev[4], st));
+            LaunchTraversal(pt, sub, 2, travGrid);
+            LaunchResolve(pt, sub, 2, grid);
+            HIPCHK(hipEventRecord(ev[5], st));
+        }
         HIPCHK(hipGetLastError());   // a launch of this iteration that was refused (bad configuration) stops the render here
         havePrev = true; prevFull = true;
         set ^= 1;
@@ -4079,7 +4180,9 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
     return MI_OK;
 }
 
-int mi_pt_render(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *weight_sum, mi_counters *counters) {
+// One frame (or pass, or shard) into the film and out to the caller: the body shared by mi_pt_render and mi_pt_render_metadata,
+// which differ in pt->metaStrategy and in the DScene the pass sees.
+static int RenderFrame(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *weight_sum, mi_counters *counters) {
     if (!pt || !rp) { g_err = "null argument"; return MI_ERR_INVALID; }
     if (rp->shard_count < 1 || rp->shard_index < 0 || rp->shard_index >= rp->shard_count) { g_err = "bad shard"; return MI_ERR_INVALID; }
     {   // sample numbers are ints in the path state (I_SAMPLE) and in the oracle: [sample_begin, sample_begin + spp) stays below 2^31 - 1
@@ -4172,6 +4275,29 @@ int mi_pt_render(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *
         }
     }
     return MI_OK;
+}
+
+int mi_pt_render(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *weight_sum, mi_counters *counters) {
+    return RenderFrame(pt, rp, film_sum, weight_sum, counters);
+}
+
+int mi_pt_render_metadata(mi_pt *pt, const mi_render_params *rp, int strategy, float *film_sum, float *weight_sum, mi_counters *counters) {
+    if (!pt || !rp) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (strategy < MI_METADATA_DEPTH || strategy > MI_METADATA_COORDINATES) { g_err = "mi_pt_render_metadata: unknown strategy"; return MI_ERR_INVALID; }
+    if (pt->primMetaHost.size() != pt->scene.nPrims) { g_err = "mi_pt_render_metadata: the scene description came without prim_meta"; return MI_ERR_INVALID; }
+    HIPCHK(hipSetDevice(pt->device));
+    if (!pt->primMeta) {   // the first metadata pass of this renderer
+        const int rc = Upload(pt, pt->primMetaHost.data(), pt->primMetaHost.size(), &pt->primMeta);
+        if (rc != MI_OK) { pt->primMeta = nullptr; return rc; }
+    }
+    // the pass's own view of the scene, as mi_pt_debug_path takes one: no depth limit ends a hit before the commit
+    // (EndsUnshaded), one ray per camera sample whatever "spectralpath" asks for
+    struct Restore { mi_pt *pt; DScene s; ~Restore() { pt->scene = s; pt->metaStrategy = -1; } } restore{pt, pt->scene};
+    pt->scene.maxDepth = 255;
+    pt->scene.nBands = 1;
+    pt->scene.bandDelta = MI_NSPEC;
+    pt->metaStrategy = strategy;
+    return RenderFrame(pt, rp, film_sum, weight_sum, counters);
 }
 
 int mi_pt_device_film(mi_pt *pt, void **dev_ptr, uint64_t *n_floats) {

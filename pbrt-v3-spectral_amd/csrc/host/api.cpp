@@ -107,6 +107,7 @@ double ParseNumber(const std::string &s, bool *ok) {  // parser.cpp:322-368
 struct MaterialInstance {
     std::string name;  // material type
     int material = -1; // index into HostScene::materials, -1 = none
+    uint32_t id = 0;   // Material::materialId of the reference's object (Api::materialCounter), 0 = none
     ParamSet params;
 };
 
@@ -125,6 +126,7 @@ struct PendingPrim {
     int light;
     Bounds3 bounds;
     int instance = 0;   // k + 1: the TransformedPrimitive of instance k
+    uint32_t materialId = 0, instanceId = 0;   // mi_prim_meta
 };
 
 struct Api {
@@ -149,7 +151,7 @@ struct Api {
     // object and InstanceToWorld; the object's primitives get a BVH of their own at WorldEnd. (MIPT_INSTANCES=expand
     // re-creates the recorded shapes under InstanceToWorld * (their CTM) instead -- round 1's world-space copies: the same
     // surfaces, hit points that differ from the reference's in rounding.)
-    struct RecordedShape { std::string name; ParamSet params; Transform ctm; GraphicsState gs; };
+    struct RecordedShape { std::string name; ParamSet params; Transform ctm; GraphicsState gs; uint32_t materialId; };
     std::map<std::string, std::vector<RecordedShape>> instances;
     std::vector<RecordedShape> *currentInstance = nullptr;
     struct ObjectDef { std::vector<PendingPrim> prims; Bounds3 bounds; bool created = false; int root = -1; };
@@ -157,7 +159,15 @@ struct Api {
     std::vector<std::string> objectOrder;                 // objects in the order they were first instanced
     struct InstanceRec { std::string object; Transform i2w; };
     std::vector<InstanceRec> instanceRecs;
+    std::vector<std::string> instanceNames;   // one per ObjectInstance call that created something, in file order
     bool expandInstances = false;
+    // Material::materialId (material.h:54): every Material object the reference constructs takes the next number of a counter
+    // that starts at 1. In a `pbrt scene.pbrt` process the matte of the static GraphicsState is number 1 (api.cpp:382,
+    // 214-222) and the matte of pbrtInit's fresh GraphicsState number 2 (api.cpp:902): the scene's default material, made
+    // by the constructor below. Then one number per MakeMaterial call that returns a material (api.cpp:552-625). Identical
+    // mi_material records are shared (MakeMaterial below), so the number belongs to the primitive (mi_prim_meta).
+    uint32_t materialCounter = 1, lastMaterialId = 0;
+    uint32_t expandingInstance = 0;   // MIPT_INSTANCES=expand: the ObjectInstance call whose copies are being created
     std::map<std::string, std::shared_ptr<PLYMeshData>> plyCache;   // an instanced plymesh is read once
     std::map<std::string, Spectrum> cachedSpectra;                  // paramset.cpp:48, SPD files by name
     bool worldEnded = false;
@@ -174,9 +184,13 @@ struct Api {
         gs.currentMaterial = std::make_shared<MaterialInstance>();
         gs.currentMaterial->name = "matte";
         gs.currentMaterial->material = MakeMaterial("matte", empty, empty);
+        gs.currentMaterial->id = lastMaterialId;
     }
 
-    int MakeMaterial(const std::string &name, const ParamSet &geom, const ParamSet &mat) {
+    // `count`: the call stands for a MakeMaterial call of the reference and takes the next material id (lastMaterialId; 0 for
+    // "none"); false when a recorded shape is re-created, whose id was taken where the reference took it (Shape).
+    int MakeMaterial(const std::string &name, const ParamSet &geom, const ParamSet &mat, bool count = true) {
+        if (count) lastMaterialId = 0;
         if (name == "" || name == "none") return -1;
         TextureParams mp(geom, mat, gs.textures, &scene->errors);
         mi_material m;
@@ -197,6 +211,7 @@ struct Api {
                 const std::string nm = mp.FindString(param, "");
                 auto it = gs.namedMaterials.find(nm);
                 if (it == gs.namedMaterials.end() || it->second->material < 0) {
+                    if (count && it == gs.namedMaterials.end()) ++materialCounter;   // the fallback matte is a MakeMaterial call of its own, before the mix (api.cpp:577-591)
                     Err("Named material \"" + nm + "\" undefined.  Using \"matte\"");
                     mi_material mm;
                     std::vector<std::string> e2;
@@ -217,11 +232,22 @@ struct Api {
             TextureParams mp2(e1, e2, gs.textures, &scene->errors);
             CompileMaterial("matte", mp2, &m, &scene->warnings, &errs);
         }
+        if (count) lastMaterialId = ++materialCounter;
         // de-duplicate identical records (a loopsubdiv shape re-creates its material, api.cpp:1502-1513)
         for (size_t i = 0; i < scene->materials.size(); ++i)
             if (std::memcmp(&scene->materials[i], &m, sizeof(m)) == 0) return (int)i;
         scene->materials.push_back(m);
         return (int)scene->materials.size() - 1;
+    }
+
+    // The numbers MakeMaterial(name, geom, mat) takes, without making the material: for a shape recorded inside ObjectBegin,
+    // whose material this front end compiles when the object is first instanced. Returns the material's id.
+    uint32_t TakeMaterialIds(const std::string &name, const ParamSet &geom, const ParamSet &mat) {
+        if (name == "" || name == "none") return 0;
+        if (name == "mix")   // the fallback mattes of undefined named materials come first (api.cpp:577-591)
+            for (const char *param : {"namedmaterial1", "namedmaterial2"})
+                if (!gs.namedMaterials.count(geom.FindOneString(param, mat.FindOneString(param, "")))) ++materialCounter;
+        return ++materialCounter;
     }
 
     // ---- shapes
@@ -316,7 +342,7 @@ struct Api {
         return (int)scene->lights.size() - 1;
     }
 
-    void AddPrims(int firstTri, int nTris, int material) {
+    void AddPrims(int firstTri, int nTris, int material, uint32_t materialId) {
         for (int t = 0; t < nTris; ++t) {
             int tri = firstTri + t;
             const int32_t *v = &scene->triIndices[3 * tri];
@@ -324,6 +350,7 @@ struct Api {
             PendingPrim pp;
             pp.shape = tri;
             pp.material = material;
+            pp.materialId = materialId; pp.instanceId = expandingInstance;
             pp.light = -1;
             if (gs.areaLight != "") {
                 float area = 0.5 * Cross(p1 - p0, p2 - p0).Length();  // Triangle::Area, triangle.cpp:575-581
@@ -334,11 +361,19 @@ struct Api {
         }
     }
 
-    void Shape(const std::string &name, const ParamSet &params) {
+    // `recorded`: the shape of an object is being re-created at an ObjectInstance; *recorded is the material id it took
+    // where it was declared.
+    void Shape(const std::string &name, const ParamSet &params, const uint32_t *recorded = nullptr) {
         if (state != World) { Err("Scene description must be inside world block; \"Shape\" not allowed. Ignoring."); return; }
         if (currentInstance) {   // api.cpp:1431-1435
             if (gs.areaLight != "") Warn("Area lights not supported with object instancing");
-            RecordedShape r{name, params, ctm, gs};
+            // the reference creates the shape and its material here (GetMaterialForShape, api.cpp:1378), so the id is taken here
+            // (after MakeShapes has made something, api.cpp:1370-1378: judged here by the shape's name, the shapes this front end
+            // builds; a shape whose parameters turn out unusable at the ObjectInstance has taken its number all the same)
+            uint32_t id = gs.currentMaterial->id;
+            const bool built = name == "trianglemesh" || name == "plymesh" || name == "loopsubdiv" || name == "sphere";
+            if (built && ShapeMaySetMaterialParameters(params)) id = TakeMaterialIds(gs.currentMaterial->name, params, gs.currentMaterial->params);
+            RecordedShape r{name, params, ctm, gs, id};
             r.gs.areaLight = "";
             currentInstance->push_back(std::move(r));
             return;
@@ -432,15 +467,19 @@ struct Api {
         }
         // material (api.cpp:1378, GetMaterialForShape 1502-1513)
         int material;
-        if (ShapeMaySetMaterialParameters(params))
-            material = MakeMaterial(gs.currentMaterial->name, params, gs.currentMaterial->params);
-        else
+        uint32_t materialId = gs.currentMaterial->id;
+        if (ShapeMaySetMaterialParameters(params)) {
+            material = MakeMaterial(gs.currentMaterial->name, params, gs.currentMaterial->params, recorded == nullptr);
+            materialId = lastMaterialId;
+        } else
             material = gs.currentMaterial->material;
+        if (recorded) materialId = *recorded;
         if (sphereIdx >= 0) {
             const mi_sphere &s = scene->spheres[sphereIdx];
             PendingPrim pp;
             pp.shape = ~sphereIdx;
             pp.material = material;
+            pp.materialId = materialId; pp.instanceId = expandingInstance;
             pp.light = -1;
             if (gs.areaLight != "") {
                 float area = s.phi_max * s.radius * (s.z_max - s.z_min);  // Sphere::Area, sphere.cpp:217
@@ -451,7 +490,7 @@ struct Api {
             pp.bounds = ctm.Bounds(ob);  // Shape::WorldBound, shape.cpp:54
             pending.push_back(pp);
         } else
-            AddPrims(firstTri, nTris, material);
+            AddPrims(firstTri, nTris, material, materialId);
         std::vector<std::string> unused;
         params.ReportUnused(&unused);
         for (auto &u : unused) Warn("Parameter \"" + u + "\" not used");
@@ -478,11 +517,15 @@ struct Api {
         const Transform instanceToWorld = ctm;
         const GraphicsState saved = gs;
         if (expandInstances) {
+            if (it->second.empty()) return;   // api.cpp:1588
+            instanceNames.push_back(name);
+            expandingInstance = (uint32_t)instanceNames.size();   // the copies carry the instance id themselves
             for (const RecordedShape &r : it->second) {
                 ctm = instanceToWorld * r.ctm;
                 gs = r.gs;
-                Shape(r.name, r.params);
+                Shape(r.name, r.params, &r.materialId);
             }
+            expandingInstance = 0;
             ctm = instanceToWorld;
             gs = saved;
             return;
@@ -496,7 +539,7 @@ struct Api {
             for (const RecordedShape &r : it->second) {
                 ctm = r.ctm;
                 gs = r.gs;
-                Shape(r.name, r.params);
+                Shape(r.name, r.params, &r.materialId);
             }
             od.prims.swap(pending);
             pending.swap(world);
@@ -506,6 +549,7 @@ struct Api {
         }
         if (od.prims.empty()) return;   // api.cpp:1580
         instanceRecs.push_back(InstanceRec{name, instanceToWorld});
+        instanceNames.push_back(name);   // nObjectInstancesUsed / renderOptions->instanceNames, api.cpp:1589, 1614
         PendingPrim pp;
         pp.shape = 0;
         pp.material = -1;
@@ -902,10 +946,21 @@ void Api::WorldEnd() {
     // ---- integrator (CreatePathIntegrator, path.cpp:190-213)
     {
         scene->integratorName = integratorName;
-        if (integratorName != "path" && integratorName != "spectralpath")
+        if (integratorName != "path" && integratorName != "spectralpath" && integratorName != "metadata")
             Err("Integrator \"" + integratorName + "\" is outside the hot-path scope (SURVEY 2 row 7); using path.");
         mi_integrator &it = d.integrator;
         it.n_ca_bands = 1;
+        it.kind = MI_INTEGRATOR_PATH;
+        it.metadata_strategy = MI_METADATA_DEPTH;
+        if (integratorName == "metadata") {  // CreateMetadataIntegrator, metadata.cpp:91-111
+            it.kind = MI_INTEGRATOR_METADATA;
+            const std::string st = integratorParams.FindOneString("strategy", "depth");
+            if (st == "depth") it.metadata_strategy = MI_METADATA_DEPTH;
+            else if (st == "material") it.metadata_strategy = MI_METADATA_MATERIAL;
+            else if (st == "mesh") it.metadata_strategy = MI_METADATA_MESH;
+            else if (st == "coordinates") it.metadata_strategy = MI_METADATA_COORDINATES;
+            else Warn("Strategy \"" + st + "\" for metadata unknown. Using \"depth\".");
+        }
         if (integratorName == "spectralpath") {  // CreateSpectralPathIntegrator, spectralpath.cpp:342-376
             it.n_ca_bands = integratorParams.FindOneInt("numCABands", 4);
             if (it.n_ca_bands < 1) { Err("\"numCABands\" must be at least 1."); it.n_ca_bands = 1; }
@@ -993,6 +1048,7 @@ void Api::WorldEnd() {
             p.area_light = pp.light;
             p.instance = pp.instance;
             scene->prims[i] = p;
+            scene->primMeta.push_back(mi_prim_meta{pp.materialId, pp.instanceId});
         }
         // the objects' own BVHs (MakeAccelerator over the object's primitives at its first ObjectInstance, api.cpp:1583-1590),
         // appended to the node and primitive arrays with absolute offsets; then the instances that point at them
@@ -1015,6 +1071,7 @@ void Api::WorldEnd() {
                 mi_prim p{};
                 p.shape = pp.shape; p.material = pp.material; p.area_light = pp.light; p.instance = 0;
                 scene->prims.push_back(p);
+                scene->primMeta.push_back(mi_prim_meta{pp.materialId, 0u});   // (the instance id is the hit's instance + 1)
             }
             od.root = baseNode;
             scene->stats.interiorNodes += oi;
@@ -1024,6 +1081,7 @@ void Api::WorldEnd() {
             Err(accelErr);
             scene->nodes.clear();
             scene->prims.clear();
+            scene->primMeta.clear();
             scene->hlbvhOnDevice = false;
             scene->stats.interiorNodes = scene->stats.leafNodes = 0;
         }
@@ -1055,6 +1113,10 @@ void Api::WorldEnd() {
             Warn("No light sources defined in scene; rendering a black image.");
         BuildLightDistribution(scene, scene->lightStrategy);
     }
+    // the names behind the ids (written at WorldEnd by the reference, api.cpp:1654-1681: the instance names in file order, the
+    // named materials of the graphics state WorldEnd finds, in std::map order)
+    scene->instanceNames = instanceNames;
+    for (const auto &nm : gs.namedMaterials) { scene->namedMaterialNames.push_back(nm.first); scene->namedMaterialIds.push_back(nm.second->id); }
     scene->stats.nLights = (int)scene->lights.size();
     scene->stats.nMaterials = (int)scene->materials.size();
     const float *Y = Spectrum::CIE_Y();
@@ -1454,6 +1516,7 @@ bool Parser::Run() {
                 auto mi = std::make_shared<MaterialInstance>();
                 mi->name = name; mi->params = ps;
                 mi->material = a.MakeMaterial(name, ps, empty);
+                mi->id = a.lastMaterialId;
                 a.gs.currentMaterial = mi;
             } else if (tok == "MakeNamedMaterial") {
                 if (!needWorld("MakeNamedMaterial")) continue;
@@ -1463,6 +1526,7 @@ bool Parser::Run() {
                 auto mi = std::make_shared<MaterialInstance>();
                 mi->name = matName; mi->params = ps;
                 mi->material = a.MakeMaterial(matName, ps, empty);
+                mi->id = a.lastMaterialId;
                 if (a.gs.namedMaterials.count(name)) a.Warn("Named material \"" + name + "\" redefined.");
                 a.gs.namedMaterials[name] = mi;
             } else if (tok == "NamedMaterial") {
@@ -1524,6 +1588,7 @@ void HostScene::Finalize() {
     d.n_materials = (uint32_t)materials.size(); d.materials = materials.data();
     d.n_lights = (uint32_t)lights.size(); d.lights = lights.data();
     d.n_instances = (uint32_t)instances.size(); d.instances = instances.empty() ? nullptr : instances.data();
+    d.prim_meta = primMeta.size() == prims.size() && !primMeta.empty() ? primMeta.data() : nullptr;
     d.light_distrib.func = ldFunc.empty() ? nullptr : ldFunc.data();
     d.light_distrib.cdf = ldCdf.empty() ? nullptr : ldCdf.data();
     d.light_distrib.func_int = ldFuncInt.empty() ? nullptr : ldFuncInt.data();

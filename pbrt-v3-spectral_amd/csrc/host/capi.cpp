@@ -108,6 +108,26 @@ const char *mi_scene_message(const mi_scene *s, int kind, int i) {
 
 const char *mi_scene_film_filename(const mi_scene *s) { return s ? s->hs->filmFilename.c_str() : nullptr; }
 
+const char *mi_scene_instance_name(const mi_scene *s, int i) {
+    if (!s || i < 0 || i >= (int)s->hs->instanceNames.size()) return nullptr;
+    return s->hs->instanceNames[i].c_str();
+}
+
+const char *mi_scene_named_material(const mi_scene *s, int i, uint32_t *id) {
+    if (!s || i < 0 || i >= (int)s->hs->namedMaterialNames.size() || i >= (int)s->hs->namedMaterialIds.size()) return nullptr;
+    if (id) *id = s->hs->namedMaterialIds[i];
+    return s->hs->namedMaterialNames[i].c_str();
+}
+
+int mi_scene_write_metadata_names(const mi_scene *s, const char *film_filename) {
+    if (!s || !film_filename) { g_err = "null argument"; return MI_ERR_INVALID; }
+    return Guarded([&]() -> int {
+        std::string err;
+        if (!WriteMetadataNames(*s->hs, film_filename, nullptr, &err)) { g_err = err; return MI_ERR_INVALID; }
+        return MI_OK;
+    });
+}
+
 void mi_scene_free(mi_scene *s) {
     if (!s) return;
     delete s->hs;

@@ -104,4 +104,24 @@ bool WriteRGBImage(const std::string &filename, int w, int h, const float *filmS
     return true;
 }
 
+// The metadata name files of pbrtWorldEnd (src/core/api.cpp:1631-1686): the stem is the film's file name up to its last
+// '.' (the whole name when it has none), the lines "<id> <name>\n".
+bool WriteMetadataNames(const HostScene &scene, const std::string &filmFilename, std::string *written, std::string *err) {
+    if (written) written->clear();
+    const mi_integrator &it = scene.desc.integrator;
+    if (it.kind != MI_INTEGRATOR_METADATA || (it.metadata_strategy != MI_METADATA_MESH && it.metadata_strategy != MI_METADATA_MATERIAL)) return true;
+    const bool mesh = it.metadata_strategy == MI_METADATA_MESH;
+    const std::string name = filmFilename.substr(0, filmFilename.find_last_of('.')) + (mesh ? "_mesh.txt" : "_materials.txt");
+    FILE *f = fopen(name.c_str(), "w");
+    if (!f) { *err = "cannot open " + name; return false; }
+    if (mesh)
+        for (size_t k = 0; k < scene.instanceNames.size(); ++k) fprintf(f, "%zu %s\n", k + 1, scene.instanceNames[k].c_str());   // InstanceIDs start at 1
+    else
+        for (size_t k = 0; k < scene.namedMaterialNames.size() && k < scene.namedMaterialIds.size(); ++k)
+            fprintf(f, "%u %s\n", scene.namedMaterialIds[k], scene.namedMaterialNames[k].c_str());
+    if (fclose(f) != 0) { *err = "short write to " + name; return false; }
+    if (written) *written = name;
+    return true;
+}
+
 }  // namespace mipt

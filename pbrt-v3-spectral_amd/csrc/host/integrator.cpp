@@ -12,6 +12,7 @@ struct HipApi {
     void *lib = nullptr;
     int (*create)(const mi_scene_desc *, int, mi_pt **) = nullptr;
     int (*render)(mi_pt *, const mi_render_params *, float *, float *, mi_counters *) = nullptr;
+    int (*render_metadata)(mi_pt *, const mi_render_params *, int, float *, float *, mi_counters *) = nullptr;
     void (*destroy)(mi_pt *) = nullptr;
     const char *(*last_error)(void) = nullptr;
     int (*timings)(mi_pt *, double *, int) = nullptr;
@@ -36,10 +37,11 @@ bool LoadHip(HipApi *api, std::string *err) {
     if (!api->lib) { *err = "HIP extension libmipt_hip.so not loadable (no CPU fallback exists):" + tried; return false; }
     api->create = (decltype(api->create))dlsym(api->lib, "mi_pt_create");
     api->render = (decltype(api->render))dlsym(api->lib, "mi_pt_render");
+    api->render_metadata = (decltype(api->render_metadata))dlsym(api->lib, "mi_pt_render_metadata");
     api->destroy = (decltype(api->destroy))dlsym(api->lib, "mi_pt_destroy");
     api->last_error = (decltype(api->last_error))dlsym(api->lib, "mi_pt_last_error");
     api->timings = (decltype(api->timings))dlsym(api->lib, "mi_pt_last_timings");
-    if (!api->create || !api->render || !api->destroy || !api->last_error) {
+    if (!api->create || !api->render || !api->render_metadata || !api->destroy || !api->last_error) {
         *err = "libmipt_hip.so does not export the mi_pt_* entry points";
         return false;
     }
@@ -50,6 +52,12 @@ bool LoadHip(HipApi *api, std::string *err) {
 int PathIntegrator::Render(const HostScene &scene, std::string *err) {
     HipApi api;
     if (!LoadHip(&api, err)) return MI_ERR_NO_DEVICE;
+    const std::string out = outfile.empty() ? scene.filmFilename : outfile;
+    const bool metadata = scene.desc.integrator.kind == MI_INTEGRATOR_METADATA;
+    if (metadata) {   // the name file first, as the reference writes it at WorldEnd before it renders (api.cpp:1631-1686)
+        std::string nerr;
+        if (!WriteMetadataNames(scene, out, nullptr, &nerr)) { *err = nerr; return MI_ERR_INVALID; }
+    }
     mi_pt *pt = nullptr;
     int rc = api.create(&scene.desc, device, &pt);
     if (rc != MI_OK) { *err = std::string("mi_pt_create: ") + api.last_error(); return rc; }
@@ -59,11 +67,11 @@ int PathIntegrator::Render(const HostScene &scene, std::string *err) {
     mi_render_params rp{};
     rp.shard_index = 0;
     rp.shard_count = 1;
-    rc = api.render(pt, &rp, film.data(), weight.data(), &counters);
-    if (rc != MI_OK) { *err = std::string("mi_pt_render: ") + api.last_error(); api.destroy(pt); return rc; }
+    rc = metadata ? api.render_metadata(pt, &rp, scene.desc.integrator.metadata_strategy, film.data(), weight.data(), &counters)
+                  : api.render(pt, &rp, film.data(), weight.data(), &counters);
+    if (rc != MI_OK) { *err = std::string(metadata ? "mi_pt_render_metadata: " : "mi_pt_render: ") + api.last_error(); api.destroy(pt); return rc; }
     if (api.timings) api.timings(pt, &seconds, 1);
     api.destroy(pt);
-    std::string out = outfile.empty() ? scene.filmFilename : outfile;
     std::string werr;
     if (!scene.spectralFlag) {  // Film::WriteImage, RGB branch (film.cpp:182-225)
         std::string written;

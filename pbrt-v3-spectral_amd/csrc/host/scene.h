@@ -49,6 +49,11 @@ struct HostScene {
     std::vector<mi_mipmap> mipmaps;
     std::vector<mi_texture> textures;
     std::vector<mi_instance> instances;   // ObjectInstance as TransformedPrimitive (their BVHs follow the world's in `nodes`)
+    // Integrator "metadata": the ids of every primitive (parallel to prims) and the names behind them
+    std::vector<mi_prim_meta> primMeta;
+    std::vector<std::string> instanceNames;        // ObjectInstance calls in file order: instance id k + 1
+    std::vector<std::string> namedMaterialNames;   // MakeNamedMaterial names in std::map order ...
+    std::vector<uint32_t> namedMaterialIds;        // ... and their material ids
     // light distribution
     std::vector<float> ldFunc, ldCdf, ldFuncInt;
     // sampler tables
@@ -148,5 +153,8 @@ HostScene *LoadSceneCache(const std::string &path, std::string *err);
 // Spectral film writer, src/core/film.cpp:226-308 (".dat": text header + 31 planes of float64).
 bool WriteSpectralDat(const std::string &filename, int w, int h, const float *filmSum, float scale,
                       std::string *err);
+// The name file of an Integrator "metadata" scene beside `filmFilename` (src/core/api.cpp:1631-1686): "<stem>_mesh.txt" for
+// strategy mesh, "<stem>_materials.txt" for material, nothing otherwise. *written: the file's name, "" when none was due.
+bool WriteMetadataNames(const HostScene &scene, const std::string &filmFilename, std::string *written, std::string *err);
 
 }  // namespace mipt

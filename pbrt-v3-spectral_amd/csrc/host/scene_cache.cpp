@@ -16,7 +16,7 @@
 namespace mipt {
 namespace {
 
-const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '5'};
+const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '6'};
 
 struct Out {
     FILE *f;
@@ -67,6 +67,7 @@ void Fields(IO &io, S &s) {   // the same walk writes and reads
     io.Vec(s.sobolMatrices); io.Vec(s.sobolVdc); io.Vec(s.sobolVdcInv);
     io.Str(s.filmFilename); io.Str(s.integratorName); io.Str(s.samplerName); io.Str(s.lightStrategy);
     io.Strs(s.warnings); io.Strs(s.errors);
+    io.Vec(s.primMeta); io.Strs(s.instanceNames); io.Strs(s.namedMaterialNames); io.Vec(s.namedMaterialIds);   // Integrator "metadata" (kind and strategy travel in desc)
 }
 
 }  // namespace
@@ -154,7 +155,8 @@ HostScene *LoadSceneCache(const std::string &path, std::string *err) {
                       s->UV.size() == 2ull * d.n_verts && s->meshes.size() == d.n_meshes && s->spheres.size() == d.n_spheres &&
                       s->materials.size() == d.n_materials && s->lights.size() == d.n_lights && s->textures.size() == d.n_textures && s->instances.size() == d.n_instances &&
                       s->envStore.size() == d.n_envmaps && s->mipStore.size() == d.n_mipmaps && d.sampler.n_dims >= 0 && (int)s->primes.size() == d.sampler.n_dims &&
-                      s->primeSums.size() == s->primes.size() && s->perms.size() == d.sampler.n_perms;
+                      s->primeSums.size() == s->primes.size() && s->perms.size() == d.sampler.n_perms &&
+                      (s->primMeta.empty() || s->primMeta.size() == d.n_prims) && s->namedMaterialIds.size() == s->namedMaterialNames.size();
     if (consistent) {   // light-selection tables (mi_lightdistrib): UNIFORM / POWER carry one distribution, SPATIAL none (built on the device)
         if (d.n_lights == 0 || d.light_distrib.type == MI_LD_SPATIAL) consistent = s->ldFunc.empty() && s->ldCdf.empty() && s->ldFuncInt.empty();
         else consistent = s->ldFunc.size() == d.n_lights && s->ldCdf.size() == (size_t)d.n_lights + 1 && s->ldFuncInt.size() == 1;
