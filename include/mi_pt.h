@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define MI_NSPEC 31
-#define MI_ABI_VERSION 11
+#define MI_ABI_VERSION 12
 #define MI_MAX_BXDFS 8 /* BSDF::MaxBxDFs, src/core/reflection.h:196 */
 
 typedef enum mi_status {
@@ -299,6 +299,18 @@ typedef struct mi_camera {
     float camera_to_world[16];
     float lens_radius, focal_distance;
     float shutter_open, shutter_close;
+    /* ABI v12 -- a moving camera: CameraToWorld as an AnimatedTransform (src/core/transform.cpp:396-411, 1103-1193).
+     * camera_to_world is the start transform (at times <= transform_start), camera_to_world_end the end transform (at times
+     * >= transform_end); a ray's time is Lerp(time sample, shutter_open, shutter_close) (perspective.cpp:89, 141). `animated`
+     * = actuallyAnimated: 0 when the two transforms are equal, and then the fields after it are 0 and every ray takes
+     * camera_to_world. Otherwise T, R, S are the two members taken apart by AnimatedTransform::Decompose: translation, the
+     * rotation as a quaternion {x, y, z, w} -- R[1] already negated where Dot(R[0], R[1]) < 0 -- and the upper 3x3 of the
+     * scale matrix, row major. Between the two times a ray is carried by
+     * Translate(Lerp T) * Slerp(dt, R[0], R[1]).ToTransform() * Lerp S with dt = (time - start) / (end - start). */
+    float camera_to_world_end[16];
+    float transform_start, transform_end;
+    int32_t animated;
+    float T[2][3], R[2][4], S[2][9];
 } mi_camera;
 
 /* ---- film + reconstruction filter (src/core/film.cpp:50-112, film.h:123-163) */
@@ -512,6 +524,11 @@ int mi_pt_trace(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hi
  * the hit primitive as the traversal kernel left it, before the quadric step (int32 bits; -2 = the ray was never answered;
  * mode 1, whose kernel keeps one answer word per queue entry: 0 = occluded, -1 = not)}. Host pointers; n <= 2^24. */
 int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra);
+
+/* Parity tool for the camera: sample i = {px, py, sample number} (three int32) goes through the device functions k_generate
+ * calls -- CameraSampleDims, then CameraRay -- and out receives 8 floats per sample: o[3], d[3], tMax, time. (time is
+ * shutter_open for a camera that does not move: such a camera's time sample is never evaluated.) Host pointers; n <= 2^24. */
+int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out);
 
 /* Parity tool for the scalar helpers under the shape and sampling code, each run on the device for n inputs (x, y: 2 floats per
  * element; out: 3 floats per element) -- the reference's own tests of them are restated over this entry point and the oracle's:

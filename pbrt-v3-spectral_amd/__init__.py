@@ -98,7 +98,9 @@ class LightDistrib(C.Structure):
 class Camera(C.Structure):
     _fields_ = [("raster_to_camera", C.c_float * 16), ("camera_to_world", C.c_float * 16),
                 ("lens_radius", C.c_float), ("focal_distance", C.c_float), ("shutter_open", C.c_float),
-                ("shutter_close", C.c_float)]
+                ("shutter_close", C.c_float),
+                ("camera_to_world_end", C.c_float * 16), ("transform_start", C.c_float), ("transform_end", C.c_float),
+                ("animated", C.c_int32), ("T", (C.c_float * 3) * 2), ("R", (C.c_float * 4) * 2), ("S", (C.c_float * 9) * 2)]
 
 
 class Film(C.Structure):
@@ -220,12 +222,27 @@ def host_lib():
     return _host
 
 
+def _start_torch_runtime_first():
+    """A process that uses torch beside this package (distributed.device_film_tensor, bench.py) runs two copies of the HIP
+    runtime: the one torch ships and the one libmipt_hip.so links. They share the GPU when torch's comes up first; in the other
+    order torch later finds no device ("No HIP GPUs are available"), whenever that later is -- so the order cannot be left to
+    the caller. Where torch is installed, its runtime is started before the library is loaded; without torch the package
+    works as before, less the torch hand-overs."""
+    try:
+        import torch
+        if torch.cuda.is_available() and torch.cuda.device_count() > 0:
+            torch.cuda.init()
+    except Exception:   # (no torch, or one without a usable GPU build: nothing to start, nothing here depends on it)
+        pass
+
+
 def hip_lib():
     """The HIP path (hand-written gfx950 kernels). Raises if it is not built / loadable."""
     global _hip
     if _hip is None:
         if not os.path.exists(HIP_LIB):
             raise RuntimeError("HIP extension %s is missing; the product path has no CPU fallback" % HIP_LIB)
+        _start_torch_runtime_first()
         lib = C.CDLL(HIP_LIB)
         lib.mi_pt_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_void_p)]
         lib.mi_pt_render.argtypes = [C.c_void_p, C.POINTER(RenderParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -238,6 +255,7 @@ def hip_lib():
         lib.mi_pt_destroy.argtypes = [C.c_void_p]
         lib.mi_pt_last_error.restype = C.c_char_p
         lib.mi_pt_trace.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(C.c_float)]
+        lib.mi_pt_camera_rays.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_float)]
         lib.mi_pt_math_probe.argtypes = [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_trace_wavefront.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_texture_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -446,6 +464,16 @@ class PathIntegrator:
         if rc != 0:
             raise RuntimeError("mi_pt_trace failed: %s" % hip_lib().mi_pt_last_error().decode())
         return hits
+
+    def camera_rays(self, samples):
+        """The camera rays k_generate would make (mi_pt_camera_rays): samples [n, 3] = (px, py, sample number) ->
+        [n, 8] = o, d, tMax, time."""
+        s = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
+        out = np.zeros((s.shape[0], 8), np.float32)
+        rc = hip_lib().mi_pt_camera_rays(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], _fptr(out))
+        if rc != 0:
+            raise RuntimeError("mi_pt_camera_rays failed: %s" % hip_lib().mi_pt_last_error().decode())
+        return out
 
     def trace_wavefront(self, rays, mode=0):
         """The rays through the render's own kernels (mi_pt_trace_wavefront): mode 0 path rays (k_trav<0> + resolve),

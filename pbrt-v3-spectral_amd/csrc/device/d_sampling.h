@@ -243,7 +243,11 @@ static DEV_CALL SobolCamera CameraSampleSobol(const uint32_t *__restrict__ matri
     return r;
 }
 // *dimAfter: the path's sampler dimension after the camera sample (5; a pixel sampler's packed table counters).
-DEV uint64_t CameraSampleDims(const DScene &s, int px, int py, long long sampleNum, float *u0, float *u1, float *lu, float *lv, int *dimAfter = nullptr) {
+// TIME (a moving camera only): *tu = CameraSample::time, the value GetCameraSample takes between pFilm and pLens -- dimension 2
+// of the index (HALTON, SOBOL), the third draw of the stream (RANDOM), the first 1D table entry (pixel samplers). A camera that
+// does not move never evaluates it: TIME = false leaves out the radical inverse and writes nothing.
+template <bool TIME = false>
+DEV uint64_t CameraSampleDims(const DScene &s, int px, int py, long long sampleNum, float *u0, float *u1, float *lu, float *lv, int *dimAfter = nullptr, float *tu = nullptr) {
     *lu = *lv = 0.f;
     if (dimAfter) *dimAfter = 5;
     if (IsPixelSampler(s)) {   // pFilm = Get2D(), time = Get1D(), pLens = Get2D()
@@ -251,7 +255,8 @@ DEV uint64_t CameraSampleDims(const DScene &s, int px, int py, long long sampleN
         ps.index = RandomStreamStart(PixelSampleStreamInc(s, px, py, sampleNum));
         ps.dim = 0;
         PixelGet2D(s, ps, px, py, sampleNum, u0, u1);
-        (void)PixelGet1D(s, ps, px, py, sampleNum);
+        const float t = PixelGet1D(s, ps, px, py, sampleNum);
+        if constexpr (TIME) *tu = t;
         PixelGet2D(s, ps, px, py, sampleNum, lu, lv);
         if (dimAfter) *dimAfter = ps.dim;
         return ps.index;
@@ -260,7 +265,8 @@ DEV uint64_t CameraSampleDims(const DScene &s, int px, int py, long long sampleN
         const uint64_t inc = RandomStreamInc(s, px, py, sampleNum);
         uint64_t state = RandomStreamStart(inc);
         *u0 = PcgFloat(state, inc); *u1 = PcgFloat(state, inc);
-        (void)PcgFloat(state, inc);   // time
+        const float t = PcgFloat(state, inc);   // time
+        if constexpr (TIME) *tu = t;
         *lu = PcgFloat(state, inc); *lv = PcgFloat(state, inc);
         return state;
     }
@@ -268,10 +274,12 @@ DEV uint64_t CameraSampleDims(const DScene &s, int px, int py, long long sampleN
         const SobolCamera r = CameraSampleSobol(s.sobolMatrices, s.sobolVdc, s.sobolVdcInv, s.sobolLog2Resolution, s.sobolResolution,
                                                 s.sampleBounds[0], s.sampleBounds[1], px, py, (uint64_t)sampleNum, s.camera.lens_radius > 0);
         *u0 = r.u0; *u1 = r.u1; *lu = r.lu; *lv = r.lv;
+        if constexpr (TIME) *tu = SobolSampleFloat(s.sobolMatrices, r.index, 2);
         return r.index;
     }
     const uint64_t index = HaltonPixelOffset(s, px, py) + (uint64_t)sampleNum * (uint64_t)s.sampleStride;
     *u0 = SampleDimension(s, index, 0); *u1 = SampleDimension(s, index, 1);
+    if constexpr (TIME) *tu = SampleDimension(s, index, 2);
     if (s.camera.lens_radius > 0) { *lu = SampleDimension(s, index, 3); *lv = SampleDimension(s, index, 4); }
     return index;
 }

@@ -74,6 +74,11 @@ struct DScene {
     int infiniteLights[4];         // indices of the MI_LIGHT_INFINITE lights (scene.infiniteLights), -1 = none
     int nInfiniteLights;
     mi_camera camera;
+    // The same record in device memory. The per-ray transform of a moving camera (MovingCameraToWorld) reads the two
+    // matrices and their decompositions from here: built from the by-value copy above, that code kept every image-textured
+    // k_shade instance's whole DScene in private memory (+1088 B of scratch per lane, a copy loop at kernel entry, also for
+    // cameras that do not move) -- the compiler note of DESIGN.md section 4. The address is uniform: the loads are scalar.
+    const mi_camera *cameraMotion;
     // film
     int croppedBounds[4], sampleBounds[4], pixelBounds[4];
     float filterRadius[2];
@@ -419,6 +424,68 @@ DEV Ray XfRay(const float *m, const Ray &r) {
         tMax -= dt;
     }
     return Ray(o, d, tMax);
+}
+
+// ------------------------------------------------------------------ the moving camera (ABI v12)
+// AnimatedTransform::Interpolate for the camera's CameraToWorld (src/core/transform.cpp:1144-1169) at a time strictly
+// between transform_start and transform_end: m = Translate(Lerp T) * Slerp(dt, R[0], R[1]).ToTransform() * Lerp S, row major,
+// in the reference's float operation order -- Slerp (quaternion.cpp:94-104) normalises its linear blend above cosTheta =
+// .9995 and turns R[0] towards the normalised perpendicular part of R[1] below it (acos, sin and cos through the correctly
+// rounded wrappers); a quaternion divided by a float multiplies its vector part by the reciprocal and divides w
+// (quaternion.h:87-97 over geometry.h:245-249); ToTransform's matrix is the transpose of the one it writes down
+// (quaternion.cpp:41-59). The two matrix products are written out without the terms that multiply an exact 0 or 1 of
+// Translate's and the scale's fourth row and column: the same values, up to the sign of a zero.
+DEV void InterpolateCameraToWorld(const mi_camera *__restrict__ cam, float time, float *m) {
+    const float dt = (time - cam->transform_start) / (cam->transform_end - cam->transform_start);
+    const float tx = (1 - dt) * cam->T[0][0] + dt * cam->T[1][0], ty = (1 - dt) * cam->T[0][1] + dt * cam->T[1][1],
+                tz = (1 - dt) * cam->T[0][2] + dt * cam->T[1][2];
+    const float ax = cam->R[0][0], ay = cam->R[0][1], az = cam->R[0][2], aw = cam->R[0][3];
+    const float bx = cam->R[1][0], by = cam->R[1][1], bz = cam->R[1][2], bw = cam->R[1][3];
+    const float cosTheta = (ax * bx + ay * by + az * bz) + aw * bw;
+    float x, y, z, w;
+    if (cosTheta > .9995f) {
+        x = ax * (1 - dt) + bx * dt; y = ay * (1 - dt) + by * dt; z = az * (1 - dt) + bz * dt; w = aw * (1 - dt) + bw * dt;
+        const float len = __builtin_sqrtf((x * x + y * y + z * z) + w * w), inv = 1.f / len;
+        x *= inv; y *= inv; z *= inv; w /= len;
+    } else {
+        const float theta = acosF(clampf(cosTheta, -1.f, 1.f));
+        const float thetap = theta * dt;
+        float px = bx - ax * cosTheta, py = by - ay * cosTheta, pz = bz - az * cosTheta, pw = bw - aw * cosTheta;
+        const float len = __builtin_sqrtf((px * px + py * py + pz * pz) + pw * pw), inv = 1.f / len;
+        px *= inv; py *= inv; pz *= inv; pw /= len;
+        const float c = cosF(thetap), sn = sinF(thetap);
+        x = ax * c + px * sn; y = ay * c + py * sn; z = az * c + pz * sn; w = aw * c + pw * sn;
+    }
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = x * w, wy = y * w, wz = z * w;
+    float r[9];   // the rotation, row major (the transpose of ToTransform's `m`)
+    r[0] = 1 - 2 * (yy + zz); r[1] = 2 * (xy - wz);     r[2] = 2 * (xz + wy);
+    r[3] = 2 * (xy + wz);     r[4] = 1 - 2 * (xx + zz); r[5] = 2 * (yz - wx);
+    r[6] = 2 * (xz - wy);     r[7] = 2 * (yz + wx);     r[8] = 1 - 2 * (xx + yy);
+    float sc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) sc[i] = lerpf(dt, cam->S[0][i], cam->S[1][i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) m[4 * i + j] = r[3 * i] * sc[j] + r[3 * i + 1] * sc[3 + j] + r[3 * i + 2] * sc[6 + j];
+    }
+    m[3] = tx; m[7] = ty; m[11] = tz;
+    m[12] = 0.f; m[13] = 0.f; m[14] = 0.f; m[15] = 1.f;
+}
+// CameraToWorld at a ray's time (AnimatedTransform::operator()(Ray), transform.cpp:1171-1181): the start transform up to
+// transform_start, the end transform from transform_end on, the interpolated one between them. cam: DScene::cameraMotion.
+// The time differs from lane to lane; the choice is made between values, entry by entry.
+DEV void MovingCameraToWorld(const mi_camera *__restrict__ cam, float time, float *m) {
+    const bool atStart = time <= cam->transform_start, atEnd = time >= cam->transform_end;
+    float mid[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mid[i] = 0.f;
+    if (!atStart && !atEnd) InterpolateCameraToWorld(cam, time, mid);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float a = cam->camera_to_world[i], b = cam->camera_to_world_end[i];
+        m[i] = atStart ? a : (atEnd ? b : mid[i]);
+    }
 }
 
 // ------------------------------------------------------------------ spheres

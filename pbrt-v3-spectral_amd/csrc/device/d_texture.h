@@ -16,8 +16,10 @@ struct CamDifferentials {  // RayDifferential's offset rays (geometry.h:897-931)
 };
 
 // PerspectiveCamera::GenerateRayDifferential (perspective.cpp:95-146) + ScaleDifferentials(s) (geometry.h:917-922)
-// for the camera sample (pFilm, lens) whose main ray is (o, d) in world space.
-DEV CamDifferentials CameraDifferentials(const DScene &s, float pFilmX, float pFilmY, float lensU, float lensV, const V3 &o, const V3 &d,
+// for the camera sample (pFilm, lens) whose main ray is (o, d) in world space. c2w: CameraToWorld at the ray's time -- the
+// camera's one matrix, or MovingCameraToWorld's for a moving camera (Transform::operator()(RayDifferential) carries the
+// offset rays with the transform that carried the main ray, transform.cpp:1183-1193).
+DEV CamDifferentials CameraDifferentials(const DScene &s, const float *c2w, float pFilmX, float pFilmY, float lensU, float lensV, const V3 &o, const V3 &d,
                                          float scale) {
     const mi_camera &cam = s.camera;
     const V3 pCamera = XfPoint(cam.raster_to_camera, V3(pFilmX, pFilmY, 0));
@@ -44,10 +46,10 @@ DEV CamDifferentials CameraDifferentials(const DScene &s, float pFilmX, float pF
         ryD = Normalize(pCamera + dyCamera);
     }
     CamDifferentials c;
-    c.rxOrigin = XfPoint(cam.camera_to_world, rxO);
-    c.ryOrigin = XfPoint(cam.camera_to_world, ryO);
-    c.rxDirection = XfVector(cam.camera_to_world, rxD);
-    c.ryDirection = XfVector(cam.camera_to_world, ryD);
+    c.rxOrigin = XfPoint(c2w, rxO);
+    c.ryOrigin = XfPoint(c2w, ryO);
+    c.rxDirection = XfVector(c2w, rxD);
+    c.ryDirection = XfVector(c2w, ryD);
     c.rxOrigin = o + (c.rxOrigin - o) * scale;
     c.ryOrigin = o + (c.ryOrigin - o) * scale;
     c.rxDirection = d + (c.rxDirection - d) * scale;

@@ -1454,7 +1454,11 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool,
 }
 
 // ------------------------------------------------------------------ generate
-DEV void CameraRay(const DScene &s, float pFilmX, float pFilmY, float lensU, float lensV, Ray *out) {
+// MOVING (mi_camera.animated, uniform over a launch): the ray's time is Lerp(timeU, shutterOpen, shutterClose)
+// (perspective.cpp:141) and CameraToWorld is the AnimatedTransform at that time (MovingCameraToWorld, d_scene.h). The
+// instance for a camera that does not move is the code it always was: no time, one matrix.
+template <bool MOVING = false>
+DEV void CameraRay(const DScene &s, float pFilmX, float pFilmY, float lensU, float lensV, Ray *out, float timeU = 0.f, float *timeOut = nullptr) {
     // PerspectiveCamera::GenerateRayDifferential, perspective.cpp:95-146 (differentials feed
     // only texture filtering; every texture on this path is constant)
     const mi_camera &cam = s.camera;
@@ -1470,7 +1474,14 @@ DEV void CameraRay(const DScene &s, float pFilmX, float pFilmY, float lensU, flo
         ray.o = V3(lx, ly, 0);
         ray.d = Normalize(pFocus - ray.o);
     }
-    *out = XfRay(cam.camera_to_world, ray);
+    if constexpr (MOVING) {
+        const float time = lerpf(timeU, cam.shutter_open, cam.shutter_close);
+        if (timeOut) *timeOut = time;
+        float m[16];
+        MovingCameraToWorld(s.cameraMotion, time, m);
+        *out = XfRay(m, ray);
+    } else
+        *out = XfRay(cam.camera_to_world, ray);
 }
 
 #if MIPT_HAS_MAIN
@@ -1491,6 +1502,7 @@ DEV void CameraRay(const DScene &s, float pFilmX, float pFilmY, float lensU, flo
 //   ------  one atomicAdd each on the two cursors of the extend work list;
 //   pass 3  write the work list: new camera rays from the front (consecutive samples of a pixel: the most coherent rays),
 //           continuing paths from the back.
+template <bool MOVING>   // the camera moves (mi_camera.animated): the camera sample's time is evaluated and the ray goes through the transform at that time
 __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *film, DevCounters *ctr, WorkDesc wd) {
     __shared__ float sL[BLOCK * 33];
     __shared__ float sFilter[256];  // the 16x16 filter table, one LDS copy per block
@@ -1795,16 +1807,17 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
             // GetCameraSample (sampler.cpp:46-52): pFilm = dims 0,1; time = dim 2; pLens = dims 3,4
             float u0, u1, lu, lv;
             int dimAfter;
-            const uint64_t index = CameraSampleDims(s, px, py, sampleNum, &u0, &u1, &lu, &lv, &dimAfter);
+            float tu = 0.f;
+            const uint64_t index = CameraSampleDims<MOVING>(s, px, py, sampleNum, &u0, &u1, &lu, &lv, &dimAfter, &tu);
             float pfx = (float)px + u0, pfy = (float)py + u1;
             Ray ray;
-            CameraRay(s, pfx, pfy, lu, lv, &ray);
+            CameraRay<MOVING>(s, pfx, pfy, lu, lv, &ray, tu);
             ++cam;
             pool.R(R_RAY0, slot) = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tMax);
             pool.R(R_RAY1, slot) = make_float4(ray.d.x, ray.d.y, ray.d.z, 1.f);   // etaScale = 1
             pool.F(P_FILMX, slot) = pfx; pool.F(P_FILMY, slot) = pfy;
 
-            if (s.storePixelSample) {
+            if (s.storePixelSample) {   // (a moving camera in front of textures: k_shade evaluates the sample's time again)
                 pool.I(I_PIXEL, slot) = (px & 0xffff) | (py << 16);
                 pool.I(I_SAMPLE, slot) = (int)sampleNum;
             }
@@ -2090,12 +2103,23 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                     td.dudx = td.dvdx = td.dudy = td.dvdy = 0;
                     if (flags & F_DIFF) {   // SurfaceInteraction::ComputeDifferentials, interaction.cpp:99-143
                         float lu = 0.f, lv = 0.f;
-                        if (s.camera.lens_radius > 0) {   // the camera sample's lens position again
+                        // CameraToWorld for the offset rays: one call of CameraDifferentials on one local array
+                        float c2w[16];
+                        if (s.camera.animated) {   // (uniform) the camera sample's time and lens position again, and the transform at that time
                             const int pixw = pool.I(I_PIXEL, slot);
-                            float cu0, cu1;
-                            CameraSampleDims(s, (int)(short)(pixw & 0xffff), pixw >> 16, (long long)pool.I(I_SAMPLE, slot), &cu0, &cu1, &lu, &lv);
+                            float cu0, cu1, tu;
+                            CameraSampleDims<true>(s, (int)(short)(pixw & 0xffff), pixw >> 16, (long long)pool.I(I_SAMPLE, slot), &cu0, &cu1, &lu, &lv, nullptr, &tu);
+                            MovingCameraToWorld(s.cameraMotion, lerpf(tu, s.camera.shutter_open, s.camera.shutter_close), c2w);
+                        } else {
+                            if (s.camera.lens_radius > 0) {   // the camera sample's lens position again
+                                const int pixw = pool.I(I_PIXEL, slot);
+                                float cu0, cu1;
+                                CameraSampleDims(s, (int)(short)(pixw & 0xffff), pixw >> 16, (long long)pool.I(I_SAMPLE, slot), &cu0, &cu1, &lu, &lv);
+                            }
+#pragma unroll
+                            for (int i = 0; i < 16; ++i) c2w[i] = s.camera.camera_to_world[i];
                         }
-                        const CamDifferentials cd = CameraDifferentials(s, pool.F(P_FILMX, slot), pool.F(P_FILMY, slot), lu, lv, ro, rd, s.invSqrtSpp);
+                        const CamDifferentials cd = CameraDifferentials(s, c2w, pool.F(P_FILMX, slot), pool.F(P_FILMY, slot), lu, lv, ro, rd, s.invSqrtSpp);
                         td = ComputeDifferentials(isect.p, isect.n, isect.dpdu, tsh.dpdv, cd);
                     }
                     if (mat->bump_tex >= 0) Bump(s, mat->bump_tex, u, v, td, tsh, &isect);   // `if (bumpMap) Bump(bumpMap, si)`
@@ -2751,6 +2775,21 @@ __global__ void k_pixel_tables(DScene s, float *tab1, float *tab2, unsigned long
 }
 
 // ------------------------------------------------------------------ texture lookups on their own (mi_pt_texture_lookup)
+// mi_pt_camera_rays: CameraSampleDims and CameraRay as k_generate calls them, one listed sample per thread.
+template <bool MOVING>
+__global__ void k_camera_rays(DScene s, const int32_t *__restrict__ samples, uint32_t n, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int px = samples[3 * i], py = samples[3 * i + 1];
+    const long long sampleNum = samples[3 * i + 2];
+    float u0, u1, lu, lv, tu = 0.f, time = s.camera.shutter_open;
+    CameraSampleDims<MOVING>(s, px, py, sampleNum, &u0, &u1, &lu, &lv, nullptr, &tu);
+    Ray ray;
+    CameraRay<MOVING>(s, (float)px + u0, (float)py + u1, lu, lv, &ray, tu, &time);
+    float *o = out + 8 * (size_t)i;
+    o[0] = ray.o.x; o[1] = ray.o.y; o[2] = ray.o.z; o[3] = ray.d.x; o[4] = ray.d.y; o[5] = ray.d.z; o[6] = ray.tMax; o[7] = time;
+}
+
 __global__ void k_texture_lookup(DScene s, int tex, const float *q, uint32_t n, float *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -3830,6 +3869,7 @@ int UploadScene(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     up(d->spheres, d->n_spheres, s.spheres);
     up(d->materials, d->n_materials, s.materials);
     up(d->lights, d->n_lights, s.lights);
+    up(&d->camera, 1, s.cameraMotion);
     up(h.lightBounds.data(), h.lightBounds.size(), s.lightBounds);
     up(h.lightPrim.data(), h.lightPrim.size(), s.lightPrim);
     up(d->sampler.primes, d->sampler.n_dims, s.primes);
@@ -4139,7 +4179,7 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         hipEvent_t *ev = sub.evIter[set];
         HIPCHK(hipMemsetAsync(&sub.ctr->alive, 0, ITER_CLEAR_BYTES, st));
         HIPCHK(hipEventRecord(ev[0], st));
-        hipLaunchKernelGGL(k_generate, chunkGrid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
+        hipLaunchKernelGGL((s.camera.animated ? k_generate<true> : k_generate<false>), chunkGrid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
         HIPCHK(hipEventRecord(ev[1], st));
         HIPCHK(hipMemcpyAsync(&alive, &sub.ctr->alive.v, sizeof(unsigned), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(&drawn, &sub.ctr->nextWork, sizeof(drawn), hipMemcpyDeviceToHost, st));
@@ -4203,7 +4243,7 @@ static int RenderFrame(mi_pt *pt, const mi_render_params *rp, float *film_sum, f
         DScene &sc = pt->scene;
         const unsigned long long lastSample = (unsigned long long)rp->sample_begin + (unsigned long long)PassSpp(pt, rp);
         sc.index32 = (sc.samplerType == MI_SAMPLER_HALTON && (lastSample + 1ull) * (unsigned long long)std::max(1, sc.sampleStride) < (1ull << 32)) ? 1 : 0;
-        sc.storePixelSample = (sc.samplerType >= MI_SAMPLER_RANDOM || sc.nBands > 1 || (pt->nTextures > 0 && sc.camera.lens_radius > 0)) ? 1 : 0;
+        sc.storePixelSample = (sc.samplerType >= MI_SAMPLER_RANDOM || sc.nBands > 1 || (pt->nTextures > 0 && (sc.camera.lens_radius > 0 || sc.camera.animated))) ? 1 : 0;
     }
     hipStream_t st = (hipStream_t)rp->stream;
     if (!(rp->flags & MI_RENDER_ACCUMULATE)) HIPCHK(hipMemsetAsync(pt->film, 0, pt->nPix * 32 * sizeof(float), st));
@@ -4337,6 +4377,32 @@ int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *querie
     return MI_OK;
 }
 
+int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out) {
+    if (!pt || !samples || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_camera_rays: more than 2^24 samples"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const DScene &s = pt->scene;
+    for (uint32_t i = 0; i < n; ++i) {   // the pixel indexes per-pixel tables (Halton offsets, a pixel sampler's tables): inside the sample bounds
+        const int px = samples[3 * i], py = samples[3 * i + 1];
+        if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3] || samples[3 * i + 2] < 0 ||
+            (s.samplerType >= MI_SAMPLER_ZEROTWO && samples[3 * i + 2] >= pt->spp)) {
+            g_err = "mi_pt_camera_rays: a sample lies outside the sample bounds (or beyond a pixel sampler's tables)";
+            return MI_ERR_INVALID;
+        }
+    }
+    HIPCHK(hipSetDevice(pt->device));
+    DevBuf ds, dout;
+    HIPCHK(ds.alloc((size_t)n * 3 * sizeof(int32_t)));
+    HIPCHK(dout.alloc((size_t)n * 8 * sizeof(float)));
+    HIPCHK(hipMemcpy(ds.p, samples, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL((s.camera.animated ? k_camera_rays<true> : k_camera_rays<false>), dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, s,
+                       ds.as<int32_t>(), n, dout.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
 int mi_pt_light_distribution(mi_pt *pt, float *func, float *func_int, uint64_t capacity_voxels) {
     if (!pt) { g_err = "null argument"; return MI_ERR_INVALID; }
     const DScene &s = pt->scene;
@@ -4394,7 +4460,7 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
     int slot = -1;
     for (int it = 0; it < 4096; ++it) {
         HIPCHK(hipMemsetAsync(&sub.ctr->alive, 0, ITER_CLEAR_BYTES, st));
-        hipLaunchKernelGGL(k_generate, grid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
+        hipLaunchKernelGGL((s.camera.animated ? k_generate<true> : k_generate<false>), grid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipMemcpy(flags.data(), pool.i + (size_t)I_FLAGS * poolN, poolN * sizeof(int), hipMemcpyDeviceToHost));
         slot = -1;

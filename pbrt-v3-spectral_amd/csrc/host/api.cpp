@@ -134,17 +134,23 @@ struct Api {
     LoadOverrides ov;
     std::string baseDir;
     enum { Uninit, Options, World } state = Options;
-    Transform ctm;
-    std::vector<Transform> transformStack;
+    // The CTM is a pair (TransformSet, api.cpp:158-190): `ctm` its start member, which everything but the camera is built
+    // with, `ctmEnd` its end member. A CTM directive applies to the members whose bit is set in activeBits (ActiveTransform
+    // StartTime = 1, EndTime = 2, All = 3; FOR_ACTIVE_TRANSFORMS, api.cpp:426-430); the bits are pushed and popped with the pair.
+    Transform ctm, ctmEnd;
+    uint32_t activeBits = 3;
+    float transformStart = 0.f, transformEnd = 1.f;   // TransformTimes (RenderOptions, api.cpp:168-169)
+    struct PushedTransform { Transform start, end; uint32_t bits; };
+    std::vector<PushedTransform> transformStack;
     std::vector<GraphicsState> gsStack;
     std::vector<char> pushKinds;
     GraphicsState gs;
-    std::map<std::string, Transform> namedCoordSys;
+    std::map<std::string, std::pair<Transform, Transform>> namedCoordSys;
     // render options (api.cpp:168-196 defaults)
     std::string filterName = "box", filmName = "image", samplerName = "halton", accelName = "bvh",
                 integratorName = "path", cameraName = "perspective";
     ParamSet filterParams, filmParams, samplerParams, accelParams, integratorParams, cameraParams;
-    Transform cameraToWorld;
+    Transform cameraToWorld, cameraToWorldEnd;
     std::vector<PendingPrim> pending;
     // Object instancing (api.cpp:1544-1615). As in the reference, an object's primitives are created once, in the space they
     // were declared in, and every ObjectInstance is a TransformedPrimitive in the world's BVH: the world-space box of the
@@ -176,6 +182,21 @@ struct Api {
 
     void Warn(const std::string &m) { scene->warnings.push_back(m); }
     void Err(const std::string &m) { scene->errors.push_back(m); }
+
+    template <typename F> void ForActiveTransforms(F f) {
+        if (activeBits & 1u) ctm = f(ctm);
+        if (activeBits & 2u) ctmEnd = f(ctmEnd);
+    }
+    void PushTransform(char kind) { transformStack.push_back(PushedTransform{ctm, ctmEnd, activeBits}); pushKinds.push_back(kind); }
+    void PopTransform() {
+        ctm = transformStack.back().start; ctmEnd = transformStack.back().end; activeBits = transformStack.back().bits;
+        transformStack.pop_back(); pushKinds.pop_back();
+    }
+    bool CtmIsAnimated() const { return ctm != ctmEnd; }   // TransformSet::IsAnimated, api.cpp:158-163
+    void WarnIfAnimated(const char *func) {                // WARN_IF_ANIMATED_TRANSFORM, api.cpp:431-438
+        if (CtmIsAnimated())
+            Warn(std::string("Animated transformations set; ignoring for \"") + func + "\" and using the start transform only");
+    }
 
     Api(HostScene *s, const LoadOverrides &o) : scene(s), ov(o) {
         if (const char *e = getenv("MIPT_INSTANCES")) expandInstances = std::string(e) == "expand";
@@ -365,6 +386,9 @@ struct Api {
     // where it was declared.
     void Shape(const std::string &name, const ParamSet &params, const uint32_t *recorded = nullptr) {
         if (state != World) { Err("Scene description must be inside world block; \"Shape\" not allowed. Ignoring."); return; }
+        // (the reference wraps such a shape in a TransformedPrimitive with an AnimatedTransform, api.cpp:1363-1430: moving
+        // primitives need per-ray times in traversal and are outside this path's scope)
+        if (CtmIsAnimated() && !recorded) Err("Shape \"" + name + "\": animated transforms of shapes are outside the hot-path scope; using the start transform");
         if (currentInstance) {   // api.cpp:1431-1435
             if (gs.areaLight != "") Warn("Area lights not supported with object instancing");
             // the reference creates the shape and its material here (GetMaterialForShape, api.cpp:1378), so the id is taken here
@@ -497,7 +521,7 @@ struct Api {
     }
 
     void ObjectBegin(const std::string &name) {  // api.cpp:1544-1553
-        gsStack.push_back(gs); transformStack.push_back(ctm); pushKinds.push_back('a');
+        gsStack.push_back(gs); PushTransform('a');
         if (currentInstance) Err("ObjectBegin called inside of instance definition");
         instances[name] = std::vector<RecordedShape>();
         currentInstance = &instances[name];
@@ -507,13 +531,14 @@ struct Api {
         currentInstance = nullptr;
         if (gsStack.empty()) { Err("Unmatched AttributeEnd encountered. Ignoring it."); return; }
         gs = gsStack.back(); gsStack.pop_back();
-        ctm = transformStack.back(); transformStack.pop_back();
-        pushKinds.pop_back();
+        PopTransform();
     }
     void ObjectInstance(const std::string &name) {  // api.cpp:1570-1615
         if (currentInstance) { Err("ObjectInstance can't be called inside instance definition"); return; }
         auto it = instances.find(name);
         if (it == instances.end()) { Err("Unable to find instance named \"" + name + "\""); return; }
+        // (api.cpp:1594-1610 gives the TransformedPrimitive an AnimatedTransform; see Shape)
+        if (CtmIsAnimated()) Err("ObjectInstance \"" + name + "\": animated transforms of instances are outside the hot-path scope; using the start transform");
         const Transform instanceToWorld = ctm;
         const GraphicsState saved = gs;
         if (expandInstances) {
@@ -561,6 +586,7 @@ struct Api {
 
     void LightSource(const std::string &name, const ParamSet &ps) {  // MakeLight, api.cpp:747-771
         if (state != World) { Err("\"LightSource\" not allowed outside world block. Ignoring."); return; }
+        WarnIfAnimated("LightSource");   // api.cpp:1328
         mi_light l{};
         if (name == "point") {  // CreatePointLight, point.cpp:80-88
             Spectrum I = ps.FindOneSpectrum("I", Spectrum(1.0));
@@ -643,6 +669,7 @@ struct Api {
         TextureParams tp(ps, empty, gs.textures, &scene->errors);
         const bool isFloat = type == "float", isSpec = type == "color" || type == "spectrum";
         if (!isFloat && !isSpec) { Err("Texture type \"" + type + "\" unknown."); return; }
+        WarnIfAnimated("Texture");   // api.cpp:1231, 1249
         if (texname == "checkerboard") {  // CreateCheckerboardSpectrumTexture, checkerboard.cpp:99-150
             if (isFloat) { Err("Texture \"" + name + "\": float \"checkerboard\" textures are outside the hot-path scope"); return; }
             if (ps.FindOneInt("dimension", 2) != 2) { Err("Texture \"" + name + "\": 3D \"checkerboard\" textures are outside the hot-path scope"); return; }
@@ -868,6 +895,19 @@ void Api::WorldEnd() {
         Transform rasterToCamera = Inverse(cameraToScreen) * rasterToScreen;
         std::memcpy(d.camera.raster_to_camera, rasterToCamera.m.m, sizeof(float) * 16);
         std::memcpy(d.camera.camera_to_world, cameraToWorld.m.m, sizeof(float) * 16);
+        // AnimatedTransform(&CameraToWorld[0], transformStartTime, &CameraToWorld[1], transformEndTime) (api.cpp:814-832)
+        std::memcpy(d.camera.camera_to_world_end, cameraToWorldEnd.m.m, sizeof(float) * 16);
+        d.camera.transform_start = transformStart;
+        d.camera.transform_end = transformEnd;
+        d.camera.animated = cameraToWorld != cameraToWorldEnd ? 1 : 0;
+        if (d.camera.animated) {
+            const AnimatedDecomposition ad = DecomposePair(cameraToWorld, cameraToWorldEnd);
+            for (int i = 0; i < 2; ++i) {
+                std::memcpy(d.camera.T[i], ad.d[i].T, sizeof(ad.d[i].T));
+                std::memcpy(d.camera.R[i], ad.d[i].R, sizeof(ad.d[i].R));
+                std::memcpy(d.camera.S[i], ad.d[i].S, sizeof(ad.d[i].S));
+            }
+        }
         d.camera.lens_radius = lensradius;
         d.camera.focal_distance = focaldistance;
         d.camera.shutter_open = shutteropen;
@@ -1415,34 +1455,36 @@ bool Parser::Run() {
         if (quoted) return Fail("unexpected string \"" + tok + "\"");
         if (tok == "AttributeBegin") {
             if (!needWorld("AttributeBegin")) continue;
-            a.gsStack.push_back(a.gs); a.transformStack.push_back(a.ctm); a.pushKinds.push_back('a');
+            a.gsStack.push_back(a.gs); a.PushTransform('a');
         } else if (tok == "AttributeEnd") {
             if (!needWorld("AttributeEnd")) continue;
             if (a.gsStack.empty()) { a.Err("Unmatched AttributeEnd encountered. Ignoring it."); continue; }
             a.gs = a.gsStack.back(); a.gsStack.pop_back();
-            a.ctm = a.transformStack.back(); a.transformStack.pop_back();
-            a.pushKinds.pop_back();
+            a.PopTransform();
         } else if (tok == "TransformBegin") {
             if (!needWorld("TransformBegin")) continue;
-            a.transformStack.push_back(a.ctm); a.pushKinds.push_back('t');
+            a.PushTransform('t');
         } else if (tok == "TransformEnd") {
             if (!needWorld("TransformEnd")) continue;
             if (a.transformStack.empty() || a.pushKinds.back() != 't') { a.Err("Unmatched TransformEnd encountered. Ignoring it."); continue; }
-            a.ctm = a.transformStack.back(); a.transformStack.pop_back(); a.pushKinds.pop_back();
-        } else if (tok == "ActiveTransform") {
+            a.PopTransform();
+        } else if (tok == "ActiveTransform") {   // api.cpp:1017-1034; the parser knows these three words (pbrtparse.y)
             std::string w; bool q;
             if (!Next(&w, &q)) return Fail("premature EOF");
-            if (w != "All") a.Err("ActiveTransform " + w + ": animated transforms are outside the hot-path scope; using one transform");
-        } else if (tok == "Identity") a.ctm = Transform();
-        else if (tok == "Translate") { float v[3]; if (!ReadFloats(3, v)) return false; a.ctm = a.ctm * Translate(Vec3(v[0], v[1], v[2])); }
-        else if (tok == "Scale") { float v[3]; if (!ReadFloats(3, v)) return false; a.ctm = a.ctm * Scale(v[0], v[1], v[2]); }
-        else if (tok == "Rotate") { float v[4]; if (!ReadFloats(4, v)) return false; a.ctm = a.ctm * Rotate(v[0], Vec3(v[1], v[2], v[3])); }
+            if (w == "All") a.activeBits = 3;
+            else if (w == "StartTime") a.activeBits = 1;
+            else if (w == "EndTime") a.activeBits = 2;
+            else return Fail("ActiveTransform: expected All, StartTime or EndTime");
+        } else if (tok == "Identity") a.ForActiveTransforms([](const Transform &) { return Transform(); });
+        else if (tok == "Translate") { float v[3]; if (!ReadFloats(3, v)) return false; const Transform t = Translate(Vec3(v[0], v[1], v[2])); a.ForActiveTransforms([&](const Transform &c) { return c * t; }); }
+        else if (tok == "Scale") { float v[3]; if (!ReadFloats(3, v)) return false; const Transform t = Scale(v[0], v[1], v[2]); a.ForActiveTransforms([&](const Transform &c) { return c * t; }); }
+        else if (tok == "Rotate") { float v[4]; if (!ReadFloats(4, v)) return false; const Transform t = Rotate(v[0], Vec3(v[1], v[2], v[3])); a.ForActiveTransforms([&](const Transform &c) { return c * t; }); }
         else if (tok == "LookAt") {
             float v[9]; if (!ReadFloats(9, v)) return false;
             bool degenerate;
             Transform la = LookAt(Vec3(v[0], v[1], v[2]), Vec3(v[3], v[4], v[5]), Vec3(v[6], v[7], v[8]), &degenerate);
             if (degenerate) a.Err("\"up\" vector and viewing direction passed to LookAt are pointing in the same direction.  Using the identity transformation.");
-            a.ctm = a.ctm * la;
+            a.ForActiveTransforms([&](const Transform &c) { return c * la; });
         } else if (tok == "Transform" || tok == "ConcatTransform") {
             std::string b; bool q;
             if (!Next(&b, &q) || b != "[") return Fail("expected [");
@@ -1450,13 +1492,18 @@ bool Parser::Run() {
             if (!Next(&b, &q) || b != "]") return Fail("expected ]");
             Transform t(Matrix4x4(tr[0], tr[4], tr[8], tr[12], tr[1], tr[5], tr[9], tr[13], tr[2], tr[6], tr[10], tr[14],
                                   tr[3], tr[7], tr[11], tr[15]));
-            a.ctm = (tok == "Transform") ? t : a.ctm * t;
-        } else if (tok == "CoordinateSystem") { std::string n; if (!ReadString(&n)) return false; a.namedCoordSys[n] = a.ctm; }
-        else if (tok == "CoordSysTransform") {
+            const bool replace = tok == "Transform";
+            a.ForActiveTransforms([&](const Transform &c) { return replace ? t : c * t; });
+        } else if (tok == "CoordinateSystem") { std::string n; if (!ReadString(&n)) return false; a.namedCoordSys[n] = std::make_pair(a.ctm, a.ctmEnd); }
+        else if (tok == "CoordSysTransform") {   // the whole pair, whatever the active bits say (api.cpp:1002-1015)
             std::string n; if (!ReadString(&n)) return false;
-            if (a.namedCoordSys.count(n)) a.ctm = a.namedCoordSys[n];
+            if (a.namedCoordSys.count(n)) { a.ctm = a.namedCoordSys[n].first; a.ctmEnd = a.namedCoordSys[n].second; }
             else a.Warn("Couldn't find named coordinate system \"" + n + "\"");
-        } else if (tok == "TransformTimes") { float v[2]; if (!ReadFloats(2, v)) return false; }
+        } else if (tok == "TransformTimes") {   // api.cpp:1036-1044
+            float v[2]; if (!ReadFloats(2, v)) return false;
+            if (!needOptions("TransformTimes")) continue;
+            a.transformStart = v[0]; a.transformEnd = v[1];
+        }
         else if (tok == "ReverseOrientation") { if (needWorld("ReverseOrientation")) a.gs.reverseOrientation = !a.gs.reverseOrientation; }
         else if (tok == "Include") {
             std::string fn; if (!ReadString(&fn)) return false;
@@ -1465,8 +1512,9 @@ bool Parser::Run() {
         } else if (tok == "WorldBegin") {
             if (!needOptions("WorldBegin")) continue;
             a.state = Api::World;
-            a.ctm = Transform();
-            a.namedCoordSys["world"] = a.ctm;
+            a.ctm = a.ctmEnd = Transform();
+            a.activeBits = 3;
+            a.namedCoordSys["world"] = std::make_pair(a.ctm, a.ctmEnd);
         } else if (tok == "WorldEnd") {
             if (!needWorld("WorldEnd")) continue;
             while (!a.gsStack.empty()) { a.Warn("Missing end to AttributeBegin"); a.gsStack.pop_back(); a.transformStack.pop_back(); }
@@ -1503,8 +1551,9 @@ bool Parser::Run() {
             if (tok == "Camera") {
                 if (!needOptions("Camera")) continue;
                 a.cameraName = name; a.cameraParams = ps;
-                a.cameraToWorld = Inverse(a.ctm);
-                a.namedCoordSys["camera"] = a.cameraToWorld;
+                a.cameraToWorld = Inverse(a.ctm);   // the pair of inverses (Inverse(TransformSet), api.cpp:179-184)
+                a.cameraToWorldEnd = Inverse(a.ctmEnd);
+                a.namedCoordSys["camera"] = std::make_pair(a.cameraToWorld, a.cameraToWorldEnd);
             } else if (tok == "Film") { if (needOptions("Film")) { a.filmName = name; a.filmParams = ps; } }
             else if (tok == "Sampler") { if (needOptions("Sampler")) { a.samplerName = name; a.samplerParams = ps; } }
             else if (tok == "Accelerator") { if (needOptions("Accelerator")) { a.accelName = name; a.accelParams = ps; } }
@@ -1520,6 +1569,7 @@ bool Parser::Run() {
                 a.gs.currentMaterial = mi;
             } else if (tok == "MakeNamedMaterial") {
                 if (!needWorld("MakeNamedMaterial")) continue;
+                a.WarnIfAnimated("MakeNamedMaterial");   // api.cpp:1287
                 ParamSet empty;
                 std::string matName = ps.FindOneString("type", "");
                 if (matName == "") { a.Err("No parameter string \"type\" found in MakeNamedMaterial"); continue; }
@@ -1538,7 +1588,7 @@ bool Parser::Run() {
             else if (tok == "LightSource") a.LightSource(name, ps);
             else if (tok == "Shape") a.Shape(name, ps);
             else if (tok == "Texture") { if (needWorld("Texture")) a.Texture(name, texType, texClass, ps); }
-            else if (tok == "MakeNamedMedium") a.Warn("MakeNamedMedium ignored: media are outside the hot-path scope");
+            else if (tok == "MakeNamedMedium") { a.WarnIfAnimated("MakeNamedMedium"); a.Warn("MakeNamedMedium ignored: media are outside the hot-path scope"); }
         }
     }
     return error.empty();

@@ -163,4 +163,72 @@ Transform Perspective(float fov, float n, float f) {
     return Scale(invTan, invTan, 1) * Transform(proj);
 }
 
+// Order-sensitive details of Decompose kept: the iteration averages all sixteen entries, measures the change as the largest
+// row sum of absolute differences over the upper 3x3, stops after 100 rounds or when that float is no longer above the
+// double .0001; the quaternion comes from the trace branch when the trace is positive and from the largest diagonal entry
+// otherwise; the scale is the full 4x4 product Inverse(R) * M.
+Decomposition Decompose(const Matrix4x4 &m) {
+    Decomposition out;
+    for (int i = 0; i < 3; ++i) out.T[i] = m.m[i][3];
+    Matrix4x4 M = m;
+    for (int i = 0; i < 3; ++i) M.m[i][3] = M.m[3][i] = 0.f;
+    M.m[3][3] = 1.f;
+    Matrix4x4 R = M;
+    float change;
+    int rounds = 0;
+    do {
+        const Matrix4x4 inverseTranspose = Inverse(Transpose(R));
+        Matrix4x4 next;
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) next.m[r][c] = 0.5f * (R.m[r][c] + inverseTranspose.m[r][c]);
+        change = 0;
+        for (int r = 0; r < 3; ++r) {
+            const float rowSum = std::abs(R.m[r][0] - next.m[r][0]) + std::abs(R.m[r][1] - next.m[r][1]) + std::abs(R.m[r][2] - next.m[r][2]);
+            change = std::max(change, rowSum);
+        }
+        R = next;
+    } while (++rounds < 100 && change > .0001);
+    out.steps = rounds;
+    // quaternion of R
+    float q[3], w;
+    const float trace = R.m[0][0] + R.m[1][1] + R.m[2][2];
+    if (trace > 0.f) {
+        float s = std::sqrt(trace + 1.0f);
+        w = s / 2.0f;
+        s = 0.5f / s;
+        q[0] = (R.m[2][1] - R.m[1][2]) * s;
+        q[1] = (R.m[0][2] - R.m[2][0]) * s;
+        q[2] = (R.m[1][0] - R.m[0][1]) * s;
+    } else {
+        int i = 0;
+        if (R.m[1][1] > R.m[0][0]) i = 1;
+        if (R.m[2][2] > R.m[i][i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        float s = std::sqrt((R.m[i][i] - (R.m[j][j] + R.m[k][k])) + 1.0f);
+        q[i] = s * 0.5f;
+        if (s != 0.f) s = 0.5f / s;
+        w = (R.m[k][j] - R.m[j][k]) * s;
+        q[j] = (R.m[j][i] + R.m[i][j]) * s;
+        q[k] = (R.m[k][i] + R.m[i][k]) * s;
+    }
+    out.R[0] = q[0]; out.R[1] = q[1]; out.R[2] = q[2]; out.R[3] = w;
+    const Matrix4x4 S = Matrix4x4::Mul(Inverse(R), M);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) out.S[3 * r + c] = S.m[r][c];
+    return out;
+}
+
+AnimatedDecomposition DecomposePair(const Transform &start, const Transform &end) {
+    AnimatedDecomposition a;
+    a.animated = start != end;
+    a.d[0] = Decompose(start.m);
+    a.d[1] = Decompose(end.m);
+    const float *q0 = a.d[0].R;
+    float *q1 = a.d[1].R;
+    const float dot = (q0[0] * q1[0] + q0[1] * q1[1] + q0[2] * q1[2]) + q0[3] * q1[3];   // Dot(v, v) + w w, quaternion.h:117-119
+    if (dot < 0)
+        for (int i = 0; i < 4; ++i) q1[i] = -q1[i];
+    return a;
+}
+
 }  // namespace mipt

@@ -200,4 +200,20 @@ Transform Rotate(float theta, const Vec3 &axis);
 Transform LookAt(const Vec3 &pos, const Vec3 &look, const Vec3 &up, bool *degenerate);
 Transform Perspective(float fov, float n, float f);
 
+// One member of an AnimatedTransform, taken apart as its constructor does (transform.cpp:396-411 through Decompose,
+// 1103-1142): M = T R S with T the translation column, R the rotation the polar iteration R <- (R + R^-T) / 2 settles on,
+// as a quaternion {x, y, z, w} (Quaternion(Transform), quaternion.cpp:61-92), and S = R^-1 M (its upper 3x3, row major).
+struct Decomposition {
+    float T[3], R[4], S[9];
+    int steps;   // iterations the polar loop took (informational)
+};
+Decomposition Decompose(const Matrix4x4 &m);
+// The pair of an AnimatedTransform: both members decomposed, R of the second negated when the quaternions' dot product is
+// negative (the shorter arc). `animated` = actuallyAnimated: the members differ (m or mInv).
+struct AnimatedDecomposition {
+    bool animated;
+    Decomposition d[2];
+};
+AnimatedDecomposition DecomposePair(const Transform &start, const Transform &end);
+
 }  // namespace mipt
