@@ -553,6 +553,28 @@ int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *querie
  * scene does not use "lightsamplestrategy" "spatial" (or has no lights). Host pointers. */
 int mi_pt_light_distribution(mi_pt *pt, float *func, float *func_int, uint64_t capacity_voxels);
 
+/* ---- Parity tools for the shading plan: which instance of the shading kernel a material is shaded by. The kernel k_shade
+ * exists once per (NL, TM): NL lobes at most, and a mask TM outside of which the BxDF, Fresnel, light, sampler, texture and
+ * instance code is compiled out (bit t: mi_bxdf_type t; bit 16 + f: mi_fresnel_type f; bit 24 + l: mi_light_type l; the
+ * other bits by name, mi_pt_shade_mask). mi_pt_create gives every material a shading class (one per distinct list of lobe
+ * types, Fresnel kinds and texturedness, in order of first appearance; the 15th and later lists share class 14, which counts
+ * MI_MAX_BXDFS lobes; class 15 is the escaped rays') and every class an instance. These three calls touch no device.
+ *
+ * The instance table in launch order: nl[i], tm[i] for i < *count; either array may be NULL, otherwise capacity >= *count. */
+int mi_pt_shade_instances(int32_t *nl, uint32_t *tm, uint32_t capacity, uint32_t *count);
+/* A mask by its name in the device code: "TM_DIFFUSE", "TM_PLASTIC", "TM_GLASS", "TM_UBER", "TM_DISNEY", "TM_GENERIC",
+ * "TM_FULL", "TM_ALL" (what an instance is compiled for), "TM_SCALED", "TM_TEXTURED", "TM_INSTANCES", "TM_SAMPLERS",
+ * "TM_LIGHTS_ALL", "TM_LIGHTS_NO_ENV" (single properties). MI_ERR_INVALID for another name. */
+int mi_pt_shade_mask(const char *name, uint32_t *mask);
+/* The plan mi_pt_create would make for a description (the same routine computes both). material_class: [n_materials]
+ * (capacity material_capacity). The classes in use, in rising order, the escaped rays' class last: class_id, the index of
+ * its instance, its lobe count (the longest list of its materials) and its type word (the lobe and Fresnel bits present,
+ * TM_SCALED if a lobe is a mix's, TM_TEXTURED if a material reads an image texture), each [class_capacity >= 16], *n_classes
+ * of them. hot: the light and sampler bits of the scene's matte and plastic instances. Any output may be NULL. */
+int mi_pt_shade_plan(const mi_scene_desc *scene, int32_t *material_class, uint32_t material_capacity, int32_t *class_id,
+                     int32_t *class_instance, int32_t *class_lobes, uint32_t *class_types, uint32_t class_capacity,
+                     uint32_t *n_classes, uint32_t *hot);
+
 /* ---- HLBVH build on the device (Accelerator "bvh" "string splitmethod" "hlbvh"; BVHAccel::HLBVHBuild,
  * src/accelerators/bvh.cpp:404-638): Morton codes, stable radix sort, one LBVH treelet per run of equal top 12 bits
  * (emitLBVH), and the treelets flattened into the depth-first 32-byte node array. The SAH tree over the (at most 4096)

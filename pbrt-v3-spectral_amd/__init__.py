@@ -261,6 +261,11 @@ def hip_lib():
         lib.mi_pt_texture_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_light_distribution.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]
         lib.mi_pt_debug_path.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+        lib.mi_pt_shade_instances.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.mi_pt_shade_mask.argtypes = [C.c_char_p, C.POINTER(C.c_uint32)]
+        lib.mi_pt_shade_plan.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32,
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         _hip = lib
     return _hip
 
@@ -370,6 +375,28 @@ class Scene:
     @property
     def spp(self):
         return int(self.desc.sampler.samples_per_pixel)
+
+    def shade_plan(self):
+        """The shading plan mi_pt_create would make of this scene (mi_pt_shade_plan; host code of the HIP library, no device):
+        {"material_class": [class of material i], "classes": {class: {"instance", "nl", "tm", "lobes", "types"}} for the
+        classes in use (MISS_CLASS, the escaped rays', among them; instance indexes shade_instances(), whose (nl, tm) is
+        repeated here), "hot": the light and sampler bits of the scene's matte and plastic instances}."""
+        lib = hip_lib()
+        n_mat = int(self.desc.n_materials)
+        mat = (C.c_int32 * max(1, n_mat))()
+        cid, cinst, clobes = (C.c_int32 * MAX_CLASSES)(), (C.c_int32 * MAX_CLASSES)(), (C.c_int32 * MAX_CLASSES)()
+        ctypes_ = (C.c_uint32 * MAX_CLASSES)()
+        n, hot = C.c_uint32(), C.c_uint32()
+        rc = lib.mi_pt_shade_plan(self.desc_ptr, mat, n_mat, cid, cinst, clobes, ctypes_, MAX_CLASSES, C.byref(n), C.byref(hot))
+        if rc != 0:
+            raise RuntimeError("mi_pt_shade_plan failed (%d): %s" % (rc, lib.mi_pt_last_error().decode()))
+        table = shade_instances()
+        classes = {}
+        for k in range(n.value):
+            i = int(cinst[k])
+            nl, tm = table[i] if 0 <= i < len(table) else (None, None)
+            classes[int(cid[k])] = {"instance": i, "nl": nl, "tm": tm, "lobes": int(clobes[k]), "types": int(ctypes_[k])}
+        return {"material_class": [int(mat[i]) for i in range(n_mat)], "classes": classes, "hot": int(hot.value)}
 
 
 class PathIntegrator:
@@ -528,6 +555,66 @@ def math_probe(op, x, y=None, device=0):
     if rc != 0:
         raise RuntimeError("mi_pt_math_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
     return out
+
+
+# The shading plan (include/mi_pt.h, "Parity tools for the shading plan"): mirrors of the enums whose values are the bit
+# numbers of a k_shade mask -- bit t: BXDF_TYPES[t], bit 16 + f: FRESNEL_TYPES[f], bit 24 + l: LIGHT_TYPES[l].
+BXDF_TYPES = ("lambertian_reflection", "oren_nayar", "specular_reflection", "specular_transmission", "fresnel_specular",
+              "microfacet_reflection", "microfacet_transmission", "lambertian_transmission", "disney_diffuse", "disney_fake_ss",
+              "disney_retro", "disney_sheen", "disney_clearcoat", "fresnel_blend")
+FRESNEL_TYPES = ("noop", "dielectric", "disney", "conductor")
+LIGHT_TYPES = ("diffuse_area", "point", "distant", "infinite", "spot")
+SAMPLER_TYPES = ("halton", "sobol", "random", "02sequence", "stratified")   # mi_sampler_type 0..4 (ZEROTWO: "02sequence")
+# (tests/test_shade_plan.py reads the four enums from include/mi_pt.h and compares)
+MAX_CLASSES = 16   # shading classes 0..14 of materials (14: the overflow class), MISS_CLASS: the escaped rays'
+MISS_CLASS = 15
+SHADE_MASK_NAMES = ("TM_DIFFUSE", "TM_PLASTIC", "TM_GLASS", "TM_UBER", "TM_DISNEY", "TM_GENERIC", "TM_FULL", "TM_ALL",
+                    "TM_SCALED", "TM_TEXTURED", "TM_INSTANCES", "TM_SAMPLERS", "TM_LIGHTS_ALL", "TM_LIGHTS_NO_ENV")
+
+
+def shade_mask(name):
+    """A k_shade mask by its name in the device code (mi_pt_shade_mask); also an attribute of the package: pt.TM_UBER."""
+    m = C.c_uint32()
+    if hip_lib().mi_pt_shade_mask(name.encode(), C.byref(m)) != 0:
+        raise ValueError(hip_lib().mi_pt_last_error().decode())
+    return int(m.value)
+
+
+def __getattr__(name):   # pt.TM_DIFFUSE, ...: read from the library when first asked (it loads without a GPU)
+    if name in SHADE_MASK_NAMES:
+        return shade_mask(name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def lobe_bits(*names):
+    """The mask bits of lobe types (BXDF_TYPES) and Fresnel kinds ("fresnel_" + FRESNEL_TYPES) given by name."""
+    m = 0
+    for n in names:
+        if n in BXDF_TYPES:   # ("fresnel_specular" and "fresnel_blend" are lobe types)
+            m |= 1 << BXDF_TYPES.index(n)
+        elif n.startswith("fresnel_") and n[len("fresnel_"):] in FRESNEL_TYPES:
+            m |= 1 << (16 + FRESNEL_TYPES.index(n[len("fresnel_"):]))
+        else:
+            raise ValueError("%r is neither a lobe type nor a Fresnel kind" % (n,))
+    return m
+
+
+def lobe_names(mask):
+    """The names lobe_bits() takes, of the lobe and Fresnel bits set in a mask or type word."""
+    return ([n for t, n in enumerate(BXDF_TYPES) if (mask >> t) & 1] +
+            ["fresnel_" + n for f, n in enumerate(FRESNEL_TYPES) if (mask >> (16 + f)) & 1])
+
+
+def shade_instances():
+    """[(NL, TM)] of the k_shade instances in launch order (mi_pt_shade_instances; no device)."""
+    n = C.c_uint32()
+    lib = hip_lib()
+    if lib.mi_pt_shade_instances(None, None, 0, C.byref(n)) != 0:
+        raise RuntimeError("mi_pt_shade_instances failed: %s" % lib.mi_pt_last_error().decode())
+    nl, tm = (C.c_int32 * n.value)(), (C.c_uint32 * n.value)()
+    if lib.mi_pt_shade_instances(nl, tm, n.value, C.byref(n)) != 0:
+        raise RuntimeError("mi_pt_shade_instances failed: %s" % lib.mi_pt_last_error().decode())
+    return [(int(nl[i]), int(tm[i])) for i in range(n.value)]
 
 
 def _strategy_number(strategy):

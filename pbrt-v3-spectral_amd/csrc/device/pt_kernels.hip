@@ -3016,6 +3016,7 @@ __global__ void __launch_bounds__(BLOCK) k_commit_metadata(DScene s, Pool pool, 
 
 // Every k_shade instance, in launch order (LaunchShade): X(part, NL, TM). The part is the MIPT_PART that compiles the
 // instance (three groups of about equal compile time); without MIPT_PART the kernel table instantiates them all.
+// A new instance needs a row in tests/test_shade_instances_gpu.py (the suite fails without a GPU until it has one).
 constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_TEXTURED;
 #define MIPT_SHADE_INSTANCES(X) \
     X(1, 2, TM_DIFFUSE | TM_LIGHTS_ALL) X(1, 2, TM_DIFFUSE | TM_LIGHTS_NO_ENV) \
@@ -3560,14 +3561,20 @@ struct ShadingClasses {
     std::vector<int> matClass;                       // per material: its shading class
     unsigned classMask = 1u << MISS_CLASS;           // DScene::classMask
     unsigned shadeClasses[N_SHADE_INSTANCES] = {0};  // mi_pt::shadeClasses
+    // what the two above were made from (mi_pt_shade_plan reports it)
+    int classLobes[MAX_CLASSES] = {0};       // per class: the longest lobe list
+    unsigned classTypes[MAX_CLASSES] = {0};  // per class: lobe types (bits 0..15) and fresnel kinds (bits 16..) present
+    int classInstance[MAX_CLASSES] = {0};    // per class in classMask: its k_shade instance
+    bool hasInfiniteLight = false, instanced = false;
+    unsigned hot = 0;   // the lights and sampler bits of the scene's matte and plastic instances
 };
 
 // Shading classes: one per distinct lobe-type list, in order of first appearance; then each class to its k_shade
 // instance (ShadeInstanceOf; `hot`: the lights and sampler bits of the scene's matte and plastic instances).
 int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, ShadingClasses &sc) {
     sc.matClass.assign(d->n_materials, 0);
-    int classLobes[MAX_CLASSES] = {0};       // per class: the longest lobe list
-    unsigned classTypes[MAX_CLASSES] = {0};  // per class: lobe types (bits 0..15) and fresnel kinds (bits 16..) present
+    int (&classLobes)[MAX_CLASSES] = sc.classLobes;
+    unsigned (&classTypes)[MAX_CLASSES] = sc.classTypes;
     std::vector<std::vector<int>> signatures;
     for (uint32_t i = 0; i < d->n_materials; ++i) {
         const mi_material &m = d->materials[i];
@@ -3590,9 +3597,21 @@ int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, Sh
         if (!((sc.classMask >> c) & 1u)) continue;
         const int i = ShadeInstanceOf(classTypes[c], classLobes[c], instanced, hot);
         if (i < 0) { g_err = "no k_shade instance for shading class " + std::to_string(c); return MI_ERR_UNSUPPORTED; }
+        sc.classInstance[c] = i;
         sc.shadeClasses[i] |= 1u << c;
     }
     return MI_OK;
+}
+
+// The shading plan of a description: what of the scene picks among the instances, then the classes and their instances.
+// mi_pt_create (BuildHostTables) and mi_pt_shade_plan both get it here. (The class records are accumulated: sc starts empty.)
+int PlanShading(const mi_scene_desc *d, ShadingClasses &sc) {
+    sc = ShadingClasses{};
+    for (uint32_t i = 0; i < d->n_lights; ++i) sc.hasInfiniteLight |= d->lights[i].type == MI_LIGHT_INFINITE;
+    sc.instanced = d->n_instances > 0;
+    // the matte and plastic instances exist with and without the environment-light code and with the Halton sampler alone or all three
+    sc.hot = (sc.hasInfiniteLight ? TM_LIGHTS_ALL : TM_LIGHTS_NO_ENV) | (d->sampler.type == MI_SAMPLER_HALTON ? 0u : TM_SAMPLERS);
+    return BuildShadingClasses(d, sc.instanced, sc.hot, sc);
 }
 
 // Whether Triangle::Intersect rejects the triangle (vertices v, positions a, b, c) as degenerate (triangle.cpp:303-314):
@@ -3779,17 +3798,14 @@ struct HostTables {
     std::vector<uint64_t> primeMagic;
     std::vector<uint32_t> pixelOffsets;
     std::vector<float> ewaWeights;
-    bool hasAlphaMasks = false, hasQuadrics = false, hasInfiniteLight = false, misAny = false;
+    bool hasAlphaMasks = false, hasQuadrics = false, misAny = false;
 };
 
 int BuildHostTables(const mi_scene_desc *d, HostTables &h) {
     const bool coop = getenv("MIPT_NO_COOP_LEAVES") == nullptr;
     int rc = BuildBvhTables(d, coop, h.bvh);
     if (rc != MI_OK) return rc;
-    for (uint32_t i = 0; i < d->n_lights; ++i) h.hasInfiniteLight |= d->lights[i].type == MI_LIGHT_INFINITE;
-    // the matte and plastic instances exist with and without the environment-light code and with the Halton sampler alone or all three
-    const unsigned hot = (h.hasInfiniteLight ? TM_LIGHTS_ALL : TM_LIGHTS_NO_ENV) | (d->sampler.type == MI_SAMPLER_HALTON ? 0u : TM_SAMPLERS);
-    if ((rc = BuildShadingClasses(d, d->n_instances > 0, hot, h.classes)) != MI_OK) return rc;
+    if ((rc = PlanShading(d, h.classes)) != MI_OK) return rc;
     h.primTri = BuildPrimRecords(d, h.classes.matClass, h.hasAlphaMasks, h.hasQuadrics);
     h.lightBounds = BuildLightBounds(d);
     h.lightPrim = BuildLightPrims(d, h.misAny);
@@ -3838,7 +3854,7 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     pt->hasAlphaMasks = h.hasAlphaMasks;
     pt->hasInstances = d->n_instances > 0;
     pt->hasQuadrics = h.hasQuadrics;
-    pt->hasInfiniteLight = h.hasInfiniteLight;
+    pt->hasInfiniteLight = h.classes.hasInfiniteLight;
     memcpy(pt->shadeClasses, h.classes.shadeClasses, sizeof(pt->shadeClasses));
     pt->nTextures = d->n_textures;
     for (uint32_t i = 0; i < d->n_textures; ++i) pt->textureTypes.push_back(d->textures[i].type);
@@ -4400,6 +4416,62 @@ int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out)
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+// Parity tools for the shading plan (include/mi_pt.h): host code only.
+int mi_pt_shade_instances(int32_t *nl, uint32_t *tm, uint32_t capacity, uint32_t *count) {
+    if (!count) { g_err = "null argument"; return MI_ERR_INVALID; }
+    *count = N_SHADE_INSTANCES;
+    if ((nl || tm) && capacity < (uint32_t)N_SHADE_INSTANCES) { g_err = "mi_pt_shade_instances: buffer too small"; return MI_ERR_INVALID; }
+    for (int i = 0; i < N_SHADE_INSTANCES; ++i) {
+        if (nl) nl[i] = kShadeInstances[i].nl;
+        if (tm) tm[i] = kShadeInstances[i].tm;
+    }
+    return MI_OK;
+}
+
+int mi_pt_shade_mask(const char *name, uint32_t *mask) {
+    if (!name || !mask) { g_err = "null argument"; return MI_ERR_INVALID; }
+#define MIPT_MASK_NAME(M_) {#M_, M_}
+    static const struct { const char *name; unsigned mask; } kMasks[] = {
+        MIPT_MASK_NAME(TM_DIFFUSE), MIPT_MASK_NAME(TM_PLASTIC), MIPT_MASK_NAME(TM_GLASS), MIPT_MASK_NAME(TM_UBER), MIPT_MASK_NAME(TM_DISNEY),
+        MIPT_MASK_NAME(TM_GENERIC), MIPT_MASK_NAME(TM_FULL), MIPT_MASK_NAME(TM_ALL), MIPT_MASK_NAME(TM_SCALED), MIPT_MASK_NAME(TM_TEXTURED),
+        MIPT_MASK_NAME(TM_INSTANCES), MIPT_MASK_NAME(TM_SAMPLERS), MIPT_MASK_NAME(TM_LIGHTS_ALL), MIPT_MASK_NAME(TM_LIGHTS_NO_ENV)};
+#undef MIPT_MASK_NAME
+    for (const auto &m : kMasks)
+        if (strcmp(m.name, name) == 0) { *mask = m.mask; return MI_OK; }
+    g_err = std::string("mi_pt_shade_mask: no mask named ") + name;
+    return MI_ERR_INVALID;
+}
+
+int mi_pt_shade_plan(const mi_scene_desc *d, int32_t *material_class, uint32_t material_capacity, int32_t *class_id,
+                     int32_t *class_instance, int32_t *class_lobes, uint32_t *class_types, uint32_t class_capacity,
+                     uint32_t *n_classes, uint32_t *hot) {
+    if (!d) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (d->abi_version != MI_ABI_VERSION) { g_err = "mi_scene_desc ABI version mismatch"; return MI_ERR_INVALID; }
+    int rc = CheckSceneDesc(d);
+    if (rc != MI_OK) return rc;
+    ShadingClasses sc;
+    if ((rc = PlanShading(d, sc)) != MI_OK) return rc;
+    if (material_class) {
+        if (material_capacity < d->n_materials) { g_err = "mi_pt_shade_plan: material buffer too small"; return MI_ERR_INVALID; }
+        for (uint32_t i = 0; i < d->n_materials; ++i) material_class[i] = sc.matClass[i];
+    }
+    if ((class_id || class_instance || class_lobes || class_types) && class_capacity < (uint32_t)MAX_CLASSES) {
+        g_err = "mi_pt_shade_plan: class buffers too small"; return MI_ERR_INVALID;
+    }
+    uint32_t n = 0;
+    for (int c = 0; c < MAX_CLASSES; ++c) {
+        if (!((sc.classMask >> c) & 1u)) continue;
+        if (class_id) class_id[n] = c;
+        if (class_instance) class_instance[n] = sc.classInstance[c];
+        if (class_lobes) class_lobes[n] = sc.classLobes[c];
+        if (class_types) class_types[n] = sc.classTypes[c];
+        ++n;
+    }
+    if (n_classes) *n_classes = n;
+    if (hot) *hot = sc.hot;
     return MI_OK;
 }
 
