@@ -493,6 +493,11 @@ int mi_pt_last_timings(mi_pt *pt, double *seconds, int n);
  * takes at most 65 % of the free device memory and falls back to half, a quarter, ... if the allocation fails: this says what
  * was had. */
 int mi_pt_pool_info(mi_pt *pt, uint64_t *slots, uint64_t *bytes);
+/* The k_shade launches of the last render and the blocks they covered, summed over the sub-renderers (host-side counts).
+ * A render sizes each launch by the shading queues it serves (mi_pt_shade_grid) and skips an instance whose queues are
+ * empty; with MIPT_SHADE_GRID=pool in the environment every instance of the plan is launched on pool / 256 + 16 blocks in
+ * every iteration. A metadata pass launches none. */
+int mi_pt_shade_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *blocks);
 void mi_pt_destroy(mi_pt *pt);
 const char *mi_pt_last_error(void);
 
@@ -566,6 +571,11 @@ int mi_pt_shade_instances(int32_t *nl, uint32_t *tm, uint32_t capacity, uint32_t
  * "TM_FULL", "TM_ALL" (what an instance is compiled for), "TM_SCALED", "TM_TEXTURED", "TM_INSTANCES", "TM_SAMPLERS",
  * "TM_LIGHTS_ALL", "TM_LIGHTS_NO_ENV" (single properties). MI_ERR_INVALID for another name. */
 int mi_pt_shade_mask(const char *name, uint32_t *mask);
+/* The grid of one k_shade launch: the blocks of 256 that the shading queues of the classes in `classes` (bit c: class c)
+ * fill when each queue is padded to whole blocks on its own -- the sum over those classes of ceil(counts[c] / 256), which is
+ * how the kernel maps a block index to (class, block of that queue). counts: the entries of the 16 queues, n_counts = 16
+ * (MI_ERR_INVALID otherwise, and for a NULL argument). 0 blocks: the render does not launch the instance. */
+int mi_pt_shade_grid(const uint32_t *counts, uint32_t n_counts, uint32_t classes, uint32_t *blocks);
 /* The plan mi_pt_create would make for a description (the same routine computes both). material_class: [n_materials]
  * (capacity material_capacity). The classes in use, in rising order, the escaped rays' class last: class_id, the index of
  * its instance, its lobe count (the longest list of its materials) and its type word (the lobe and Fresnel bits present,
