@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define MI_NSPEC 31
-#define MI_ABI_VERSION 12
+#define MI_ABI_VERSION 13
 #define MI_MAX_BXDFS 8 /* BSDF::MaxBxDFs, src/core/reflection.h:196 */
 
 typedef enum mi_status {
@@ -293,7 +293,32 @@ typedef struct mi_lightdistrib {
     const float *func_int;
 } mi_lightdistrib;
 
-/* ---- camera (perspective only, src/cameras/perspective.cpp:45-146) */
+/* ---- camera: perspective (src/cameras/perspective.cpp:45-146) or, ABI v13, realistic (src/cameras/realistic.cpp) */
+typedef enum mi_camera_type { MI_CAMERA_PERSPECTIVE = 0, MI_CAMERA_REALISTIC = 1 } mi_camera_type;
+/* ABI v13 -- Camera "realistic": the lens system as RealisticCamera's constructor leaves it (realistic.cpp:126-187). Plain
+ * data. elements[i] = {curvature radius, thickness, eta, aperture radius} of interface i, front (scene side) first, in
+ * metres (the file's mm * .001, the diameter halved); curvature radius 0 is the aperture stop, whose aperture is the
+ * clamped "aperturediameter". The last thickness is the focused lens-to-film distance (film_distance repeats it): the
+ * "filmdistance" parameter, or FocusThickLens("focusdistance") when that is 0. exit_pupil_bounds[k] = {x0, y0, x1, y1}: the
+ * bounds of the exit pupil on the rear element's plane seen from film points at radius [k, k + 1) / 64 of the half diagonal
+ * (BoundExitPupil, realistic.cpp:753-790). physical_extent = Film::GetPhysicalExtent() {x0, y0, x1, y1} and film_diagonal
+ * = Film::diagonal in metres (film.cpp:54, 94-99). */
+#define MI_MAX_LENS_ELEMENTS 32
+#define MI_EXIT_PUPIL_BOUNDS 64
+typedef struct mi_lens {
+    int32_t n_elements;
+    int32_t simple_weighting;      /* "simpleweighting" (true) */
+    int32_t no_weighting;          /* "noweighting": parsed, never read (as in the reference) */
+    int32_t chromatic_aberration;  /* "chromaticAberrationEnabled" (false) */
+    int32_t full_res[2];           /* Film::fullResolution (= mi_film.full_res): a sample's film point is pFilm / full_res */
+    float film_distance;
+    float film_diagonal;
+    float thick_lens_pz[2], thick_lens_fz[2]; /* ComputeThickLensApproximation's cardinal points, film side [0] and scene
+                                               * side [1], traced before focusing; fz[0] - pz[0] is the effective focal length */
+    float physical_extent[4];
+    float elements[MI_MAX_LENS_ELEMENTS][4];
+    float exit_pupil_bounds[MI_EXIT_PUPIL_BOUNDS][4];
+} mi_lens;
 typedef struct mi_camera {
     float raster_to_camera[16];
     float camera_to_world[16];
@@ -311,6 +336,10 @@ typedef struct mi_camera {
     float transform_start, transform_end;
     int32_t animated;
     float T[2][3], R[2][4], S[2][9];
+    /* (ABI v13: the camera's type and a realistic camera's lens system are mi_scene_desc.camera_type and .lens; this record
+     * keeps its size. For a realistic camera raster_to_camera is the matrix of a perspective camera with the scene's "fov"
+     * (default 90): a defined value nothing renders with; lens_radius is the rear element's aperture radius (> 0: the camera
+     * sample's lens dimensions are evaluated) and focal_distance the "focusdistance".) */
 } mi_camera;
 
 /* ---- film + reconstruction filter (src/core/film.cpp:50-112, film.h:123-163) */
@@ -424,6 +453,8 @@ typedef struct mi_scene_desc {
     uint32_t n_mipmaps;  const mi_mipmap *mipmaps;
     uint32_t n_instances; const mi_instance *instances; /* ABI v7 */
     const mi_prim_meta *prim_meta; /* ABI v11: [n_prims], may be NULL (then mi_pt_render_metadata refuses) */
+    int32_t camera_type;           /* ABI v13: mi_camera_type of `camera` */
+    const mi_lens *lens;           /* ABI v13: MI_CAMERA_REALISTIC: the lens system; NULL for a perspective camera */
 } mi_scene_desc;
 
 /* Counters with the reference's STAT names (src/core/integrator.cpp:48,
@@ -532,8 +563,21 @@ int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, fl
 
 /* Parity tool for the camera: sample i = {px, py, sample number} (three int32) goes through the device functions k_generate
  * calls -- CameraSampleDims, then CameraRay -- and out receives 8 floats per sample: o[3], d[3], tMax, time. (time is
- * shutter_open for a camera that does not move: such a camera's time sample is never evaluated.) Host pointers; n <= 2^24. */
+ * shutter_open for a camera that does not move: such a camera's time sample is never evaluated.) For a realistic camera
+ * the ray is the lens camera's at 550 nm and time is the ray's time; a sample that does not get through the lens (weight 0)
+ * has o, d and tMax all 0, which this layout cannot tell from a ray -- ask mi_pt_camera_rays_ex for the weight.
+ * Host pointers; n <= 2^24. */
 int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out);
+/* The same for every camera, with what a realistic camera adds: band s of Integrator "spectralpath" generates its ray at
+ * wavelength 395 + D s + D / 2 nm, D = 10 * round(31 / n_ca_bands) (spectralpath.cpp:234-267 with sampledLambdaStart = 395 and
+ * (705 - 395) / 31 = 10 nm per bin, spectrum.h:48-50); band must be 0 for other
+ * integrators (550 nm). out receives MI_CAMERA_RAY_EX_FLOATS floats per sample: o[3], d[3], tMax, time (here always
+ * Lerp(time sample, shutter_open, shutter_close), whether or not the camera moves), the ray weight
+ * (Camera::GenerateRayDifferential's return value, camera.cpp:60-99: 0 when the main ray, or both signs of an offset ray, do
+ * not get through the lens; then the other fields are unspecified), and the four differential vectors rxOrigin, ryOrigin,
+ * rxDirection, ryDirection after ScaleDifferentials(1 / sqrt(samples per pixel)). Runs the device functions k_generate runs. */
+#define MI_CAMERA_RAY_EX_FLOATS 21
+int mi_pt_camera_rays_ex(mi_pt *pt, const int32_t *samples, uint32_t n, int32_t band, float *out);
 
 /* Parity tool for the scalar helpers under the shape and sampling code, each run on the device for n inputs (x, y: 2 floats per
  * element; out: 3 floats per element) -- the reference's own tests of them are restated over this entry point and the oracle's:

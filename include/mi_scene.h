@@ -4,7 +4,8 @@
  * It stands where the reference's parse -> pbrtWorldEnd() path stands
  * (src/core/parser.cpp:1094 pbrtParseFile, src/core/api.cpp:1617 pbrtWorldEnd):
  * it reads a scene file and produces the flat mi_scene_desc (include/mi_pt.h)
- * that mi_pt_create() consumes, plus the spectral ".dat" film writer
+ * that mi_pt_create() consumes (Camera "perspective" and, ABI v13, Camera "realistic": mi_scene_desc.camera_type and .lens
+ * -- lens table, focus and exit-pupil boxes are computed here), plus the spectral ".dat" film writer
  * (src/core/film.cpp:226-308). Pure host C++; no HIP, no GPU needed.
  * Errors never abort: the reference's Error()/Warning() "report and continue"
  * policy (src/core/error.cpp:62-102) is kept; messages are retrievable below.

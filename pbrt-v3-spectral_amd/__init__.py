@@ -95,6 +95,20 @@ class LightDistrib(C.Structure):
                 ("func", C.POINTER(C.c_float)), ("cdf", C.POINTER(C.c_float)), ("func_int", C.POINTER(C.c_float))]
 
 
+MAX_LENS_ELEMENTS = 32
+EXIT_PUPIL_BOUNDS = 64
+CAMERA_PERSPECTIVE, CAMERA_REALISTIC = 0, 1
+
+
+class Lens(C.Structure):
+    """mi_lens: Camera "realistic" -- elements[i] = (curvature radius, thickness, eta, aperture radius) in metres, front first."""
+    _fields_ = [("n_elements", C.c_int32), ("simple_weighting", C.c_int32), ("no_weighting", C.c_int32),
+                ("chromatic_aberration", C.c_int32), ("full_res", C.c_int32 * 2), ("film_distance", C.c_float), ("film_diagonal", C.c_float),
+                ("thick_lens_pz", C.c_float * 2), ("thick_lens_fz", C.c_float * 2),
+                ("physical_extent", C.c_float * 4), ("elements", (C.c_float * 4) * MAX_LENS_ELEMENTS),
+                ("exit_pupil_bounds", (C.c_float * 4) * EXIT_PUPIL_BOUNDS)]
+
+
 class Camera(C.Structure):
     _fields_ = [("raster_to_camera", C.c_float * 16), ("camera_to_world", C.c_float * 16),
                 ("lens_radius", C.c_float), ("focal_distance", C.c_float), ("shutter_open", C.c_float),
@@ -146,7 +160,8 @@ class SceneDesc(C.Structure):
                 ("n_textures", C.c_uint32), ("textures", C.POINTER(Texture)),
                 ("n_mipmaps", C.c_uint32), ("mipmaps", C.POINTER(MipMap)),
                 ("n_instances", C.c_uint32), ("instances", C.POINTER(Instance)),
-                ("prim_meta", C.POINTER(PrimMeta))]
+                ("prim_meta", C.POINTER(PrimMeta)),
+                ("camera_type", C.c_int32), ("lens", C.POINTER(Lens))]
 
 
 class Counters(C.Structure):
@@ -256,6 +271,7 @@ def hip_lib():
         lib.mi_pt_last_error.restype = C.c_char_p
         lib.mi_pt_trace.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(C.c_float)]
         lib.mi_pt_camera_rays.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_float)]
+        lib.mi_pt_camera_rays_ex.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_int32, C.POINTER(C.c_float)]
         lib.mi_pt_math_probe.argtypes = [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_trace_wavefront.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_texture_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -510,6 +526,17 @@ class PathIntegrator:
         rc = hip_lib().mi_pt_camera_rays(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], _fptr(out))
         if rc != 0:
             raise RuntimeError("mi_pt_camera_rays failed: %s" % hip_lib().mi_pt_last_error().decode())
+        return out
+
+    def camera_rays_ex(self, samples, band=0):
+        """camera_rays for every camera, with what a realistic camera adds (mi_pt_camera_rays_ex): samples [n, 3] ->
+        [n, 21] = o, d, tMax, time, weight, rxOrigin, ryOrigin, rxDirection, ryDirection (the differentials scaled by
+        1 / sqrt(spp)); `band`: the "spectralpath" band whose wavelength the lens is traced at."""
+        s = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
+        out = np.zeros((s.shape[0], 21), np.float32)
+        rc = hip_lib().mi_pt_camera_rays_ex(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], int(band), _fptr(out))
+        if rc != 0:
+            raise RuntimeError("mi_pt_camera_rays_ex failed: %s" % hip_lib().mi_pt_last_error().decode())
         return out
 
     def trace_wavefront(self, rays, mode=0):

@@ -95,6 +95,10 @@ struct DScene {
     // set per render (mi_pt_render): the Halton indices of the pass fit 32 bits (I_IDXHI is neither stored nor read); somebody
     // reads a path's pixel and sample number after k_generate (other samplers, spectralpath bands, textured lens cameras)
     int index32, storePixelSample;
+    int cameraType;        // mi_camera_type
+    const mi_lens *lens;   // Camera "realistic": the device copy of mi_scene_desc.lens (d_lens.h reads the table from here)
+    int lensDiff;          // a realistic camera in front of a textured material: the pool carries the camera ray's differentials (P_LENSDIFF)
+    int ignoreRayWeight;   // set per pass: Integrator "metadata" adds its samples with weight 1 (a realistic camera's ray weight is ignored)
     const float *pixTab1, *pixTab2;
     int pixelDims, xSamples, ySamples, jitter;
     // integrator

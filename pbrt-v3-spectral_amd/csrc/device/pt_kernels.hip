@@ -34,6 +34,7 @@
 #include <type_traits>
 #include "d_sampling.h"
 #include "d_texture.h"
+#include "d_lens.h"
 
 using namespace dpt;
 
@@ -79,6 +80,14 @@ enum : int {
     P_TENC0, P_TENC1, P_TENC2, P_TENC3,   // the ray's tMax when the k-th postponed quadric was met (closest-hit traversals)
     P_COUNT
 };
+// Camera "realistic" only: one more float plane behind the others (a pool is allocated with FloatPlanes(scene) of them) -- the
+// weight GenerateRayDifferential returned for the slot's camera ray, which the film flush multiplies the sample by. A plane
+// and not a second evaluation at the flush: the weight is the outcome of three to five lens traces.
+constexpr int P_WEIGHT = P_COUNT;
+// ... and, in front of image textures only (DScene::lensDiff), twelve more: the camera ray's scaled differentials rxOrigin,
+// ryOrigin, rxDirection, ryDirection as LensCameraRay leaves them (they come from the offset rays' lens traces). k_generate
+// writes them, the textured k_shade instances load them where they rebuild a perspective camera's from the film position.
+constexpr int P_LENSDIFF = P_COUNT + 1, N_LENSDIFF = 12;
 // ---- float4 record planes: values that are read and written together travel in one 16-B access
 enum : int {
     R_RAY0 = 0,   // path ray: o.xyz, tMax
@@ -1502,7 +1511,12 @@ DEV void CameraRay(const DScene &s, float pFilmX, float pFilmY, float lensU, flo
 //   ------  one atomicAdd each on the two cursors of the extend work list;
 //   pass 3  write the work list: new camera rays from the front (consecutive samples of a pixel: the most coherent rays),
 //           continuing paths from the back.
-template <bool MOVING>   // the camera moves (mi_camera.animated): the camera sample's time is evaluated and the ray goes through the transform at that time
+// MOVING: the camera moves (mi_camera.animated): the camera sample's time is evaluated and the ray goes through the transform at that time.
+// REAL: Camera "realistic" (mi_scene_desc.camera_type): the ray comes through the lens system (LensCameraRay) with a weight, kept in
+// P_WEIGHT and multiplied into the sample at the flush. A sample of weight 0 is a camera ray that traces nothing: its slot is
+// finished here (L = 0), stays out of the extend list, counts as alive -- the host's next iteration flushes it -- and a
+// "spectralpath" band that is vignetted restarts as the next band like any finished one.
+template <bool MOVING, bool REAL>
 __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *film, DevCounters *ctr, WorkDesc wd) {
     __shared__ float sL[BLOCK * 33];
     __shared__ float sFilter[256];  // the 16x16 filter table, one LDS copy per block
@@ -1578,6 +1592,7 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
         const unsigned fe = fin ? sFin[fi] : 0u;
         const uint32_t slot = blockIdx.x * SLOT_CHUNKS * BLOCK + (fe & 0x3fffu);
         float myFx = 0, myFy = 0;
+        [[maybe_unused]] float myW = 1.f;
         int myZero = 0;
         bool restart = false;
         if (fin) {
@@ -1585,6 +1600,7 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
             if (nBands > 1) band = pool.I(I_BAND, slot);
             myFx = pool.F(P_FILMX, slot);   // (asked for with the L line: behind the guards, the film rows waited a round trip of their own)
             myFy = pool.F(P_FILMY, slot);
+            if constexpr (REAL) myW = pool.F(P_WEIGHT, slot);   // (spectralpath: the last band's)
             // guards of SamplerIntegrator::Render, integrator.cpp:295-316
             float yy = 0.f;
             bool hasNaN = false;
@@ -1701,9 +1717,11 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
                     g &= g - 1;
                     const float fw = __shfl(myFw, p, 64);
                     const int zero = __shfl(myZero, p, 64);
+                    float sw = 1.f;
+                    if constexpr (REAL) sw = __shfl(myW, p, 64);
                     if (have) {
                         if (bin == 31) acc += fw;                                                // filterWeightSum += fw
-                        else if (!zero) acc += (sL[(waveBase + p) * 33 + bin] * 1.f) * fw;      // contribSum += L * sampleWeight * fw
+                        else if (!zero) acc += (sL[(waveBase + p) * 33 + bin] * sw) * fw;       // contribSum += L * sampleWeight * fw
                     }
                 }
                 if (tgt >= 0 && acc != 0.f) atomicAdd(film + (size_t)tgt * 32 + bin, acc);   // (x + 0 == x: a black bin is not sent)
@@ -1719,6 +1737,8 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
                 const int src = j >= 0 ? j : 0;
                 const float pfx = __shfl(myFx, src, 64), pfy = __shfl(myFy, src, 64);
                 const int zero = __shfl(myZero, src, 64);
+                float sw = 1.f;
+                if constexpr (REAL) sw = __shfl(myW, src, 64);
                 const int q0x = __shfl(p0x, src, 64), q0y = __shfl(p0y, src, 64), q1x = __shfl(p1x, src, 64), q1y = __shfl(p1y, src, 64);
                 if (j >= 0) {
                     const float val = (bin < MI_NSPEC) ? sL[(waveBase + j) * 33 + bin] : 0.f;
@@ -1733,7 +1753,7 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
                             size_t pix = (size_t)(x2 - s.croppedBounds[0]) + (size_t)(y2 - s.croppedBounds[1]) * w;
                             float *dst = film + pix * 32 + bin;
                             if (bin == 31) atomicAdd(dst, fw);                     // filterWeightSum += fw
-                            else if (!zero && val != 0.f) atomicAdd(dst, (val * 1.f) * fw);   // contribSum += L * sampleWeight * fw (x + 0 == x: a black bin is not sent)
+                            else if (!zero && val != 0.f) atomicAdd(dst, (val * sw) * fw);   // contribSum += L * sampleWeight * fw (x + 0 == x: a black bin is not sent)
                         }
                     }
                 }
@@ -1811,10 +1831,27 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
             const uint64_t index = CameraSampleDims<MOVING>(s, px, py, sampleNum, &u0, &u1, &lu, &lv, &dimAfter, &tu);
             float pfx = (float)px + u0, pfy = (float)py + u1;
             Ray ray;
-            CameraRay<MOVING>(s, pfx, pfy, lu, lv, &ray, tu);
+            bool traced = true;   // REAL: the ray got through the lens (GenerateRayDifferential's weight > 0: Li is called)
+            if constexpr (REAL) {
+                float wavelength = 550.f;
+                if (nBands > 1) wavelength = BandWavelength(s.bandDelta, restart ? band + 1 : 0);
+                V3 diff[4];   // (always asked for, stored only under lensDiff: a pointer chosen at run time moved the array to private memory)
+                const float rayWeight = LensCameraRay<MOVING>(s, pfx, pfy, lu, lv, tu, wavelength, &ray, nullptr, diff, s.invSqrtSpp);
+                traced = rayWeight > 0;
+                if (s.lensDiff && traced) {   // (uniform)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        pool.F(P_LENSDIFF + 3 * k, slot) = diff[k].x; pool.F(P_LENSDIFF + 3 * k + 1, slot) = diff[k].y; pool.F(P_LENSDIFF + 3 * k + 2, slot) = diff[k].z;
+                    }
+                }
+                pool.F(P_WEIGHT, slot) = s.ignoreRayWeight ? 1.f : rayWeight;   // (Integrator "metadata": IgnoreRayWeight)
+            } else
+                CameraRay<MOVING>(s, pfx, pfy, lu, lv, &ray, tu);
             ++cam;
-            pool.R(R_RAY0, slot) = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tMax);
-            pool.R(R_RAY1, slot) = make_float4(ray.d.x, ray.d.y, ray.d.z, 1.f);   // etaScale = 1
+            if (traced) {
+                pool.R(R_RAY0, slot) = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.tMax);
+                pool.R(R_RAY1, slot) = make_float4(ray.d.x, ray.d.y, ray.d.z, 1.f);   // etaScale = 1
+            }
             pool.F(P_FILMX, slot) = pfx; pool.F(P_FILMY, slot) = pfy;
 
             if (s.storePixelSample) {   // (a moving camera in front of textures: k_shade evaluates the sample's time again)
@@ -1831,17 +1868,19 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
                 pool.I(I_BAND, slot) = restart ? band + 1 : 0;
                 if (!restart) for (int c = 0; c < NQ; ++c) pool.Q(Q_LCA + c, slot) = make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            pool.I(I_FLAGS, slot) = StateWord(F_ALIVE | F_L_ZERO | F_BETA_ONE | F_DIFF, 0, pixelSampler ? 0 : (restart ? dimBefore : dimAfter));   // L = 0, beta = 1, not stored
-            sGot[e] = 1;
+            pool.I(I_FLAGS, slot) = StateWord(traced ? (F_ALIVE | F_L_ZERO | F_BETA_ONE | F_DIFF) : (F_FINISHED | F_L_ZERO | F_BETA_ONE), 0,
+                                              pixelSampler ? 0 : (restart ? dimBefore : dimAfter));   // L = 0, beta = 1, not stored
+            sGot[e] = (REAL && !traced) ? 2 : 1;
         } else if (want) pool.I(I_FLAGS, slot) = 0;   // stays free (its finished path has been flushed)
     }
     __syncthreads();
 #pragma unroll 1
     for (int ch = 0; ch < SLOT_CHUNKS; ++ch) {
-        const bool got = sGot[ch * BLOCK + threadIdx.x] != 0;
+        const bool got = REAL ? sGot[ch * BLOCK + threadIdx.x] == 1 : sGot[ch * BLOCK + threadIdx.x] != 0;
         if (got) gotBits |= 1u << ch;
         const bool isCont = ((contBits >> ch) & 1u) != 0;
         anyAlive |= got || isCont;
+        if constexpr (REAL) anyAlive |= sGot[ch * BLOCK + threadIdx.x] == 2;   // (finished above, flushed by the next iteration)
         // the extend work list: new camera rays first (lanes of a traversal wave then hold neighbouring samples)
         const unsigned long long pm = __ballot(got), cm = __ballot(isCont);
         if (lane == 0) { sPrim[ch][wave] = (unsigned)__popcll(pm); sCont[ch][wave] = (unsigned)__popcll(cm); }
@@ -1865,6 +1904,13 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
     }
     CountAdd(&Stats(ctr).cameraRays, cam);
     CountAdd(&Stats(ctr).badSamples, bad);
+}
+
+// The k_generate of a scene's camera: a uniform choice per launch.
+using GenerateKernel = void (*)(DScene, Pool, float *, DevCounters *, WorkDesc);
+static GenerateKernel GenerateKernelOf(const DScene &s) {
+    if (s.cameraType == MI_CAMERA_REALISTIC) return s.camera.animated ? k_generate<true, true> : k_generate<false, true>;
+    return s.camera.animated ? k_generate<true, false> : k_generate<false, false>;
 }
 
 #endif   // MIPT_HAS_MAIN
@@ -1958,7 +2004,10 @@ DEV void StoreSpectrumLines(SpectrumTile &t, const Pool &pool, int spectrum, uin
 #define MIPT_SHADE_WAVES_PER_EU 4
 #endif
 
-template <int NL, unsigned TM>
+// LENS (textured instances only, chosen per launch for a realistic camera in front of textures: DScene::lensDiff): the
+// camera ray's differentials are loaded from the pool planes k_generate wrote (P_LENSDIFF); the LENS = false instances hold
+// no trace of that and compile to the code they were.
+template <int NL, unsigned TM, bool LENS = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT_SHADE_WAVES_PER_EU, 8))) k_shade(DScene s, Pool pool, DevCounters *ctr, unsigned classes) {
     // the grid covers the queues of `classes` back to back, each padded to whole blocks
     unsigned blk = blockIdx.x, count = 0;
@@ -2102,6 +2151,14 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                     TexDifferentials td;
                     td.dudx = td.dvdx = td.dudy = td.dvdy = 0;
                     if (flags & F_DIFF) {   // SurfaceInteraction::ComputeDifferentials, interaction.cpp:99-143
+                        if constexpr (LENS) {   // the lens camera's, from its offset rays: k_generate stored them
+                            CamDifferentials cd;
+                            cd.rxOrigin = V3(pool.F(P_LENSDIFF + 0, slot), pool.F(P_LENSDIFF + 1, slot), pool.F(P_LENSDIFF + 2, slot));
+                            cd.ryOrigin = V3(pool.F(P_LENSDIFF + 3, slot), pool.F(P_LENSDIFF + 4, slot), pool.F(P_LENSDIFF + 5, slot));
+                            cd.rxDirection = V3(pool.F(P_LENSDIFF + 6, slot), pool.F(P_LENSDIFF + 7, slot), pool.F(P_LENSDIFF + 8, slot));
+                            cd.ryDirection = V3(pool.F(P_LENSDIFF + 9, slot), pool.F(P_LENSDIFF + 10, slot), pool.F(P_LENSDIFF + 11, slot));
+                            td = ComputeDifferentials(isect.p, isect.n, isect.dpdu, tsh.dpdv, cd);
+                        } else {
                         float lu = 0.f, lv = 0.f;
                         // CameraToWorld for the offset rays: one call of CameraDifferentials on one local array
                         float c2w[16];
@@ -2121,6 +2178,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                         }
                         const CamDifferentials cd = CameraDifferentials(s, c2w, pool.F(P_FILMX, slot), pool.F(P_FILMY, slot), lu, lv, ro, rd, s.invSqrtSpp);
                         td = ComputeDifferentials(isect.p, isect.n, isect.dpdu, tsh.dpdv, cd);
+                        }
                     }
                     if (mat->bump_tex >= 0) Bump(s, mat->bump_tex, u, v, td, tsh, &isect);   // `if (bumpMap) Bump(bumpMap, si)`
                     // `rough = roughness->Evaluate(*si); if (remapRoughness) rough = RoughnessToAlpha(rough)` (plastic.cpp:57-62 ...)
@@ -2790,6 +2848,39 @@ __global__ void k_camera_rays(DScene s, const int32_t *__restrict__ samples, uin
     o[0] = ray.o.x; o[1] = ray.o.y; o[2] = ray.o.z; o[3] = ray.d.x; o[4] = ray.d.y; o[5] = ray.d.z; o[6] = ray.tMax; o[7] = time;
 }
 
+// mi_pt_camera_rays_ex: the same with the ray's weight and its scaled differentials; a realistic camera's through LensCameraRay.
+template <bool MOVING, bool REAL>
+__global__ void k_camera_rays_ex(DScene s, const int32_t *__restrict__ samples, uint32_t n, int band, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int px = samples[3 * i], py = samples[3 * i + 1];
+    const long long sampleNum = samples[3 * i + 2];
+    float u0, u1, lu, lv, tu = 0.f;
+    CameraSampleDims<true>(s, px, py, sampleNum, &u0, &u1, &lu, &lv, nullptr, &tu);   // (the time sample also where no transform waits for it: the ray's time is reported)
+    float time = lerpf(tu, s.camera.shutter_open, s.camera.shutter_close);
+    const float pfx = (float)px + u0, pfy = (float)py + u1;
+    Ray ray;
+    float weight = 1.f;
+    V3 diff[4];
+    if constexpr (REAL) {
+        const float wavelength = s.nBands > 1 ? BandWavelength(s.bandDelta, band) : 550.f;
+        weight = LensCameraRay<MOVING>(s, pfx, pfy, lu, lv, tu, wavelength, &ray, &time, diff, s.invSqrtSpp);
+    } else {
+        CameraRay<MOVING>(s, pfx, pfy, lu, lv, &ray, tu, &time);
+        float m[16];
+        if constexpr (MOVING) MovingCameraToWorld(s.cameraMotion, time, m);
+        else for (int k = 0; k < 16; ++k) m[k] = s.cameraMotion->camera_to_world[k];
+        const CamDifferentials cd = CameraDifferentials(s, m, pfx, pfy, lu, lv, ray.o, ray.d, s.invSqrtSpp);
+        diff[0] = cd.rxOrigin; diff[1] = cd.ryOrigin; diff[2] = cd.rxDirection; diff[3] = cd.ryDirection;
+    }
+    float *o = out + MI_CAMERA_RAY_EX_FLOATS * (size_t)i;
+    for (int k = 0; k < MI_CAMERA_RAY_EX_FLOATS; ++k) o[k] = 0.f;
+    o[7] = time; o[8] = weight;
+    if (weight == 0) return;
+    o[0] = ray.o.x; o[1] = ray.o.y; o[2] = ray.o.z; o[3] = ray.d.x; o[4] = ray.d.y; o[5] = ray.d.z; o[6] = ray.tMax;
+    for (int k = 0; k < 4; ++k) { o[9 + 3 * k] = diff[k].x; o[10 + 3 * k] = diff[k].y; o[11 + 3 * k] = diff[k].z; }
+}
+
 __global__ void k_texture_lookup(DScene s, int tex, const float *q, uint32_t n, float *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -3036,6 +3127,16 @@ constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_
     X(2, MI_MAX_BXDFS, TM_FULL) \
     X(2, 2, TM_ALL) \
     X(1, MI_MAX_BXDFS, TM_ALL)
+// The LENS = true twins of the instances above that read image textures (TM_TEXTURED): not part of the plan's table, a launch
+// takes the twin where the scene has a realistic camera in front of textures (LaunchShade).
+#define MIPT_SHADE_LENS_INSTANCES(X) \
+    X(3, 4, TM_FULL) \
+    X(3, 2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(3, 2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(2, 2, TM_FULL) \
+    X(2, MI_MAX_BXDFS, TM_FULL) \
+    X(2, 2, TM_ALL) \
+    X(1, MI_MAX_BXDFS, TM_ALL)
 #ifdef MIPT_PART   // each part defines its own instances and declares the others
 #if MIPT_PART == 1
 #define MIPT_SHADE_IN_1
@@ -3054,6 +3155,8 @@ constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_
 #endif
 #define MIPT_SHADE_INSTANCE(P_, NL_, TM_) MIPT_SHADE_IN_##P_ template __global__ void k_shade<NL_, (TM_)>(DScene, Pool, DevCounters *, unsigned);
 MIPT_SHADE_INSTANCES(MIPT_SHADE_INSTANCE)
+#define MIPT_SHADE_LENS_INSTANCE(P_, NL_, TM_) MIPT_SHADE_IN_##P_ template __global__ void k_shade<NL_, (TM_), true>(DScene, Pool, DevCounters *, unsigned);
+MIPT_SHADE_LENS_INSTANCES(MIPT_SHADE_LENS_INSTANCE)
 #endif
 
 }  // namespace dptk
@@ -3071,6 +3174,7 @@ struct SubRenderer {
     hipEvent_t evIter[2][N_EV] = {{nullptr}};  // per-iteration kernel boundaries, two alternating sets
     double t[7] = {0};
     int poolQuadPlanes = 0;   // spectral planes the pool was allocated with (spectralpath needs one set more)
+    int poolFloatPlanes = P_COUNT;   // float planes likewise (a realistic camera needs one more)
     size_t poolBytes = 0;     // bytes of device memory behind the pool
     unsigned long long iterations = 0;
     DevCounters result{};
@@ -3089,8 +3193,14 @@ struct ShadeInstance {
     int nl;
     unsigned tm;
     void (*kernel)(DScene, Pool, DevCounters *, unsigned);
+    void (*kernelLens)(DScene, Pool, DevCounters *, unsigned);   // the LENS twin of an instance that reads image textures, or null
 };
-#define MIPT_SHADE_ENTRY(P_, NL_, TM_) {NL_, (TM_), k_shade<NL_, (TM_)>},
+template <int NL, unsigned TM>
+constexpr auto LensShadeKernel() -> void (*)(DScene, Pool, DevCounters *, unsigned) {
+    if constexpr ((TM & TM_TEXTURED) != 0) return k_shade<NL, TM, true>;
+    else return nullptr;
+}
+#define MIPT_SHADE_ENTRY(P_, NL_, TM_) {NL_, (TM_), k_shade<NL_, (TM_)>, LensShadeKernel<NL_, (TM_)>()},
 static const ShadeInstance kShadeInstances[] = {MIPT_SHADE_INSTANCES(MIPT_SHADE_ENTRY)};
 #undef MIPT_SHADE_ENTRY
 constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstances[0]);
@@ -3208,12 +3318,14 @@ int Alloc(mi_pt *pt, size_t bytes, T **dst, const char *what) {
 
 // Spectral quad planes of a path slot: spectralpath keeps one set more, the stitched spectrum of the camera sample (Q_LCA).
 int QuadPlanes(const DScene &s) { return Q_COUNT + (s.nBands > 1 ? NQ : 0); }
+// Float planes of a path slot: a realistic camera keeps the ray weight (P_WEIGHT).
+int FloatPlanes(const DScene &s) { return P_COUNT + (s.cameraType == MI_CAMERA_REALISTIC ? 1 + (s.lensDiff ? N_LENSDIFF : 0) : 0); }
 // Samples per pixel of one pass.
 long long PassSpp(const mi_pt *pt, const mi_render_params *rp) { return rp->spp_override > 0 ? rp->spp_override : pt->spp; }
 
 // Device bytes of one path slot: planes, records, spectra and its entries in the queues.
-size_t PoolSlotBytes(int nQuadPlanes) {
-    return (size_t)P_COUNT * sizeof(float) + (size_t)nQuadPlanes * sizeof(float4) + (size_t)R_COUNT * sizeof(float4) + (size_t)I_COUNT * sizeof(int) +
+size_t PoolSlotBytes(int nQuadPlanes, int nFloatPlanes) {
+    return (size_t)nFloatPlanes * sizeof(float) + (size_t)nQuadPlanes * sizeof(float4) + (size_t)R_COUNT * sizeof(float4) + (size_t)I_COUNT * sizeof(int) +
            (size_t)(6 + MAX_CLASSES + 3) * sizeof(uint32_t);
 }
 
@@ -3224,14 +3336,14 @@ void FreePool(Pool &p) {
 
 // Failure-safe: the new pool is built aside and swapped in only when every allocation succeeded; after a failure the
 // sub-renderer holds no pool at all (n == 0), so the next render allocates afresh instead of launching on stale sizes.
-int EnsurePool(SubRenderer &sub, uint32_t n, int nQuadPlanes) {
+int EnsurePool(SubRenderer &sub, uint32_t n, int nQuadPlanes, int nFloatPlanes) {
     Pool &p = sub.pool;
-    if (p.n == n && p.f && sub.poolQuadPlanes == nQuadPlanes) return MI_OK;
+    if (p.n == n && p.f && sub.poolQuadPlanes == nQuadPlanes && sub.poolFloatPlanes == nFloatPlanes) return MI_OK;
     FreePool(p);
-    sub.poolQuadPlanes = 0;
+    sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0;
     sub.poolBytes = 0;
     Pool t{};
-    const bool ok = hipMalloc((void **)&t.f, (size_t)P_COUNT * n * sizeof(float)) == hipSuccess &&
+    const bool ok = hipMalloc((void **)&t.f, (size_t)nFloatPlanes * n * sizeof(float)) == hipSuccess &&
                     hipMalloc((void **)&t.q, (size_t)nQuadPlanes * n * sizeof(float4)) == hipSuccess &&
                     hipMalloc((void **)&t.r, (size_t)R_COUNT * n * sizeof(float4)) == hipSuccess &&
                     hipMalloc((void **)&t.i, (size_t)I_COUNT * n * sizeof(int)) == hipSuccess &&
@@ -3249,7 +3361,8 @@ int EnsurePool(SubRenderer &sub, uint32_t n, int nQuadPlanes) {
     t.n = n;
     p = t;
     sub.poolQuadPlanes = nQuadPlanes;
-    sub.poolBytes = (size_t)n * PoolSlotBytes(nQuadPlanes);
+    sub.poolFloatPlanes = nFloatPlanes;
+    sub.poolBytes = (size_t)n * PoolSlotBytes(nQuadPlanes, nFloatPlanes);
     return MI_OK;
 }
 
@@ -3341,6 +3454,14 @@ int CheckSceneDesc(const mi_scene_desc *d) {
         if (nVox == 0 || nVox * d->n_lights > (1ull << 31)) { g_err = "spatial light distribution too large for the dense per-voxel table"; return MI_ERR_UNSUPPORTED; }
     }
     if (d->integrator.n_ca_bands < 1 || d->integrator.n_ca_bands > MI_NSPEC) { g_err = "n_ca_bands must be in [1, 31]"; return MI_ERR_INVALID; }
+    if (d->camera_type != MI_CAMERA_PERSPECTIVE && d->camera_type != MI_CAMERA_REALISTIC) { g_err = "unknown mi_scene_desc.camera_type"; return MI_ERR_INVALID; }
+    if (d->camera_type == MI_CAMERA_REALISTIC) {
+        const mi_lens *l = d->lens;
+        if (!l || l->n_elements < 1 || l->n_elements > MI_MAX_LENS_ELEMENTS || l->full_res[0] < 1 || l->full_res[1] < 1 || !(l->film_diagonal > 0)) {
+            g_err = "realistic camera: mi_scene_desc.lens missing or malformed (1 .. 32 elements, the film's resolution and diagonal)";
+            return MI_ERR_INVALID;
+        }
+    }
     if (d->integrator.max_depth < 0 || d->integrator.max_depth > 255) { g_err = "max_depth must be in [0, 255] (a path's bounce count travels in 8 bits of its state word)"; return MI_ERR_UNSUPPORTED; }
     const mi_sampler &sm = d->sampler;
     if (sm.type < MI_SAMPLER_HALTON || sm.type > MI_SAMPLER_STRATIFIED) { g_err = "unknown mi_sampler.type"; return MI_ERR_INVALID; }
@@ -3841,6 +3962,11 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     for (uint32_t i = 0; i < d->n_lights; ++i)
         if (d->lights[i].type == MI_LIGHT_INFINITE) s.infiniteLights[s.nInfiniteLights++] = (int)i;
     s.camera = d->camera;
+    s.cameraType = d->camera_type;
+    s.lens = nullptr;   // (UploadScene: the device copy)
+    s.lensDiff = 0;
+    if (d->camera_type == MI_CAMERA_REALISTIC)
+        for (uint32_t i = 0; i < d->n_materials; ++i) if (d->materials[i].textured) s.lensDiff = 1;
     for (int i = 0; i < 4; ++i) { s.croppedBounds[i] = d->film.cropped_bounds[i]; s.sampleBounds[i] = d->film.sample_bounds[i]; s.pixelBounds[i] = d->integrator.pixel_bounds[i]; }
     s.filterRadius[0] = d->film.filter_radius[0]; s.filterRadius[1] = d->film.filter_radius[1];
     s.maxSampleLuminance = d->film.max_sample_luminance;
@@ -3850,6 +3976,7 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     s.samplerType = d->sampler.type;
     s.samplesPerPixel = d->sampler.samples_per_pixel;
     s.index32 = 0; s.storePixelSample = 1;
+    s.ignoreRayWeight = 0;
     s.pixelDims = d->sampler.pixel_dims; s.xSamples = d->sampler.x_samples; s.ySamples = d->sampler.y_samples; s.jitter = d->sampler.jitter;
     s.sobolResolution = d->sampler.sobol_resolution;
     s.sobolLog2Resolution = d->sampler.sobol_log2_resolution;
@@ -3895,6 +4022,7 @@ int UploadScene(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     up(d->materials, d->n_materials, s.materials);
     up(d->lights, d->n_lights, s.lights);
     up(&d->camera, 1, s.cameraMotion);
+    if (d->camera_type == MI_CAMERA_REALISTIC) up(d->lens, 1, s.lens);   // (the by-value record now points at the device copy)
     up(h.lightBounds.data(), h.lightBounds.size(), s.lightBounds);
     up(h.lightPrim.data(), h.lightPrim.size(), s.lightPrim);
     up(d->sampler.primes, d->sampler.n_dims, s.primes);
@@ -4106,7 +4234,8 @@ int LaunchShade(mi_pt *pt, SubRenderer &sub, dim3 grid) {
         if (!pt->shadeClasses[i]) continue;
         const unsigned long long blocks = pt->shadeGridPool ? (unsigned long long)grid.x + MAX_CLASSES : ShadeGridBlocks(counts, pt->shadeClasses[i]);
         if (blocks == 0) continue;
-        hipLaunchKernelGGL(kShadeInstances[i].kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, pt->shadeClasses[i]);
+        const bool lens = pt->scene.lensDiff && kShadeInstances[i].kernelLens;   // (a realistic camera in front of textures: the twin that loads the stored differentials)
+        hipLaunchKernelGGL(lens ? kShadeInstances[i].kernelLens : kShadeInstances[i].kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, pt->shadeClasses[i]);
         ++sub.shadeLaunches;
         sub.shadeBlocks += blocks;
     }
@@ -4204,18 +4333,18 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
             const size_t budget = (size_t)(0.65 * (double)(freeB + sub.poolBytes)) / (size_t)subCount;
-            const size_t fit = budget / PoolSlotBytes(QuadPlanes(s)) / BLOCK * BLOCK;
+            const size_t fit = budget / PoolSlotBytes(QuadPlanes(s), FloatPlanes(s)) / BLOCK * BLOCK;
             if (fit < poolN) poolN = (uint32_t)std::max<size_t>(fit, (size_t)BLOCK);
         } else (void)hipGetLastError();
     }
     if (wd.totalWork < poolN) poolN = (uint32_t)((wd.totalWork + BLOCK - 1) / BLOCK * BLOCK);
     if (poolN < BLOCK) poolN = BLOCK;
-    int rc = EnsurePool(sub, poolN, QuadPlanes(s));
+    int rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
     // the default size is a preference, not a requirement: on a device that cannot hold it the render goes on with half,
     // a quarter, ... (an explicit mi_render_params.path_pool is taken at its word and fails)
     while (rc == MI_ERR_NOMEM && rp->path_pool == 0 && poolN > (1u << 22)) {
         poolN = poolN / 2 / BLOCK * BLOCK;
-        rc = EnsurePool(sub, poolN, QuadPlanes(s));
+        rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
     }
     if (rc != MI_OK) return rc;
     HIPCHK(hipMemsetAsync(sub.pool.i + (size_t)I_FLAGS * poolN, 0, (size_t)poolN * sizeof(int), st));
@@ -4245,7 +4374,7 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         hipEvent_t *ev = sub.evIter[set];
         HIPCHK(hipMemsetAsync(&sub.ctr->alive, 0, ITER_CLEAR_BYTES, st));
         HIPCHK(hipEventRecord(ev[0], st));
-        hipLaunchKernelGGL((s.camera.animated ? k_generate<true> : k_generate<false>), chunkGrid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
+        hipLaunchKernelGGL(GenerateKernelOf(s), chunkGrid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
         HIPCHK(hipEventRecord(ev[1], st));
         HIPCHK(hipMemcpyAsync(&sub.reads->alive, &sub.ctr->alive.v, sizeof(unsigned), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(&sub.reads->drawn, &sub.ctr->nextWork, sizeof(drawn), hipMemcpyDeviceToHost, st));
@@ -4403,6 +4532,7 @@ int mi_pt_render_metadata(mi_pt *pt, const mi_render_params *rp, int strategy, f
     pt->scene.maxDepth = 255;
     pt->scene.nBands = 1;
     pt->scene.bandDelta = MI_NSPEC;
+    pt->scene.ignoreRayWeight = 1;   // MetadataIntegrator::IgnoreRayWeight (metadata.h:64): a vignetted sample adds zeros with weight 1
     pt->metaStrategy = strategy;
     return RenderFrame(pt, rp, film_sum, weight_sum, counters);
 }
@@ -4449,6 +4579,13 @@ int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out)
     if (n > (1u << 24)) { g_err = "mi_pt_camera_rays: more than 2^24 samples"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
     const DScene &s = pt->scene;
+    if (s.cameraType == MI_CAMERA_REALISTIC) {   // the lens camera's ray at 550 nm (band 0), in this call's layout
+        std::vector<float> ex((size_t)n * MI_CAMERA_RAY_EX_FLOATS);
+        const int rc = mi_pt_camera_rays_ex(pt, samples, n, 0, ex.data());
+        if (rc != MI_OK) return rc;
+        for (uint32_t i = 0; i < n; ++i) memcpy(out + 8 * (size_t)i, ex.data() + (size_t)i * MI_CAMERA_RAY_EX_FLOATS, 8 * sizeof(float));
+        return MI_OK;
+    }
     for (uint32_t i = 0; i < n; ++i) {   // the pixel indexes per-pixel tables (Halton offsets, a pixel sampler's tables): inside the sample bounds
         const int px = samples[3 * i], py = samples[3 * i + 1];
         if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3] || samples[3 * i + 2] < 0 ||
@@ -4467,6 +4604,35 @@ int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out)
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_pt_camera_rays_ex(mi_pt *pt, const int32_t *samples, uint32_t n, int32_t band, float *out) {
+    if (!pt || !samples || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_camera_rays_ex: more than 2^24 samples"; return MI_ERR_INVALID; }
+    const DScene &s = pt->scene;
+    if (band < 0 || band >= std::max(1, s.nBands)) { g_err = "mi_pt_camera_rays_ex: no such band"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    for (uint32_t i = 0; i < n; ++i) {
+        const int px = samples[3 * i], py = samples[3 * i + 1];
+        if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3] || samples[3 * i + 2] < 0 ||
+            (s.samplerType >= MI_SAMPLER_ZEROTWO && samples[3 * i + 2] >= pt->spp)) {
+            g_err = "mi_pt_camera_rays_ex: a sample lies outside the sample bounds (or beyond a pixel sampler's tables)";
+            return MI_ERR_INVALID;
+        }
+    }
+    HIPCHK(hipSetDevice(pt->device));
+    DevBuf ds, dout;
+    HIPCHK(ds.alloc((size_t)n * 3 * sizeof(int32_t)));
+    HIPCHK(dout.alloc((size_t)n * MI_CAMERA_RAY_EX_FLOATS * sizeof(float)));
+    HIPCHK(hipMemcpy(ds.p, samples, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice));
+    const bool real = s.cameraType == MI_CAMERA_REALISTIC, moving = s.camera.animated != 0;
+    auto kernel = real ? (moving ? k_camera_rays_ex<true, true> : k_camera_rays_ex<false, true>)
+                       : (moving ? k_camera_rays_ex<true, false> : k_camera_rays_ex<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, s, ds.as<int32_t>(), n, (int)band, dout.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * MI_CAMERA_RAY_EX_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
     return MI_OK;
 }
 
@@ -4580,7 +4746,7 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
     wd.sampleBegin = sample;
     wd.totalWork = 256;
     const uint32_t poolN = BLOCK;
-    int rc = EnsurePool(sub, poolN, QuadPlanes(s));
+    int rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
     if (rc != MI_OK) return rc;
     HIPCHK(hipMemsetAsync(sub.pool.i + (size_t)I_FLAGS * poolN, 0, (size_t)poolN * sizeof(int), st));
     HIPCHK(hipMemsetAsync(sub.ctr, 0, sizeof(DevCounters), st));
@@ -4599,7 +4765,7 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
     int slot = -1;
     for (int it = 0; it < 4096; ++it) {
         HIPCHK(hipMemsetAsync(&sub.ctr->alive, 0, ITER_CLEAR_BYTES, st));
-        hipLaunchKernelGGL((s.camera.animated ? k_generate<true> : k_generate<false>), grid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
+        hipLaunchKernelGGL(GenerateKernelOf(s), grid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipMemcpy(flags.data(), pool.i + (size_t)I_FLAGS * poolN, poolN * sizeof(int), hipMemcpyDeviceToHost));
         slot = -1;
@@ -4641,7 +4807,7 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
         ++*n_records;
     }
     FreePool(sub.pool);   // the next render sizes its own
-    sub.poolQuadPlanes = 0;
+    sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0;
     HIPCHK(hipMemset(pt->film, 0, pt->nPix * 32 * sizeof(float)));
     return MI_OK;
 }
@@ -4703,9 +4869,9 @@ int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, fl
     hipStream_t st = sub.stream;
     const DScene &s = pt->scene;
     const uint32_t poolN = (n + SLOT_CHUNKS * BLOCK - 1) / (SLOT_CHUNKS * BLOCK) * (SLOT_CHUNKS * BLOCK);
-    int rc = EnsurePool(sub, poolN, QuadPlanes(s));
+    int rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
     if (rc != MI_OK) return rc;
-    struct PoolGuard { SubRenderer &sub; ~PoolGuard() { FreePool(sub.pool); sub.poolQuadPlanes = 0; } } guard{sub};   // the next render sizes its own
+    struct PoolGuard { SubRenderer &sub; ~PoolGuard() { FreePool(sub.pool); sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0; } } guard{sub};   // the next render sizes its own
     DevBuf dr, dh, dx;
     HIPCHK(dr.alloc((size_t)n * 7 * sizeof(float)));
     HIPCHK(dh.alloc((size_t)n * 4 * sizeof(float)));

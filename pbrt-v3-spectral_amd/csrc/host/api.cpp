@@ -176,12 +176,14 @@ struct Api {
     uint32_t expandingInstance = 0;   // MIPT_INSTANCES=expand: the ObjectInstance call whose copies are being created
     std::map<std::string, std::shared_ptr<PLYMeshData>> plyCache;   // an instanced plymesh is read once
     std::map<std::string, Spectrum> cachedSpectra;                  // paramset.cpp:48, SPD files by name
+    float filmDiagonal = .035f;
     bool worldEnded = false;
     bool fatal = false;
     std::string fatalMsg;
 
     void Warn(const std::string &m) { scene->warnings.push_back(m); }
     void Err(const std::string &m) { scene->errors.push_back(m); }
+    void CreateRealisticCamera(const ParamSet &ps, float diagonal);
 
     template <typename F> void ForActiveTransforms(F f) {
         if (activeBits & 1u) ctm = f(ctm);
@@ -843,7 +845,7 @@ void Api::WorldEnd() {
         if (ov.crop[0] >= 0) for (int i = 0; i < 4; ++i) crop[i] = ov.crop[i];
         mi_film &f = d.film;
         f.scale = filmParams.FindOneFloat("scale", 1.);
-        (void)filmParams.FindOneFloat("diagonal", 35.);
+        filmDiagonal = (float)(filmParams.FindOneFloat("diagonal", 35.) * .001);   // Film::diagonal(diagonal * .001), film.cpp:54: a double product rounded to float
         f.max_sample_luminance = filmParams.FindOneFloat("maxsampleluminance", kInfinity);
         scene->spectralFlag = filmParams.FindOneBool("spectralFlag", true);
         f.full_res[0] = xres; f.full_res[1] = yres;
@@ -867,7 +869,7 @@ void Api::WorldEnd() {
     }
     // ---- camera (CreatePerspectiveCamera, perspective.cpp:235-285; ProjectiveCamera ctor camera.h:91-112)
     {
-        if (cameraName != "perspective")
+        if (cameraName != "perspective" && cameraName != "realistic")
             Err("Camera \"" + cameraName + "\" is outside the hot-path scope (SURVEY 2 row 25); using perspective.");
         const ParamSet &ps = cameraParams;
         float shutteropen = ps.FindOneFloat("shutteropen", 0.f);
@@ -912,6 +914,8 @@ void Api::WorldEnd() {
         d.camera.focal_distance = focaldistance;
         d.camera.shutter_open = shutteropen;
         d.camera.shutter_close = shutterclose;
+        d.camera_type = MI_CAMERA_PERSPECTIVE;
+        if (cameraName == "realistic") CreateRealisticCamera(ps, filmDiagonal);
         if (cameraToWorld.HasScale()) Warn("Scaling detected in world-to-camera transformation!");
     }
     // ---- sampler (CreateHaltonSampler + ctor, halton.cpp:65-96,133-140)
@@ -1199,6 +1203,50 @@ bool ReadFloatFile(const std::string &filename, std::vector<float> *values, Api 
     }
     fclose(f);
     return true;
+}
+
+// CreateRealisticCamera, src/cameras/realistic.cpp:934-989 (the shutter is the caller's: it is parsed the same way for both
+// cameras). An error leaves the scene with the perspective stand-in and the message.
+void Api::CreateRealisticCamera(const ParamSet &ps, float diagonal) {
+    mi_scene_desc &d = scene->desc;
+    std::string lensFile = ps.FindOneString("lensfile", "");
+    if (!lensFile.empty() && lensFile[0] != '/') lensFile = baseDir + "/" + lensFile;   // FindOneFilename
+    const float apertureDiameter = ps.FindOneFloat("aperturediameter", 1.0);
+    const float focusDistance = ps.FindOneFloat("focusdistance", 10.0);
+    const bool simpleWeighting = ps.FindOneBool("simpleweighting", true);
+    const bool noWeighting = ps.FindOneBool("noweighting", false);
+    if (lensFile == "") { Err("No lens description file supplied!"); return; }
+    std::vector<float> lensData;
+    if (!ReadFloatFile(lensFile, &lensData, this)) { Err("Error reading lens specification file \"" + lensFile + "\"."); return; }
+    if (lensData.size() % 4 != 0) {
+        if (lensData.size() % 4 == 1) {
+            Warn("Extra value in lens specification file, this lens file may be for pbrt-v2-spectral. Removing extra value to make it compatible with pbrt-v3-spectral...");
+            lensData.erase(lensData.begin());
+        } else {
+            Err("Excess values in lens specification file \"" + lensFile + "\"; must be multiple-of-four values, read " +
+                std::to_string((int)lensData.size()) + ".");
+            return;
+        }
+    }
+    const float filmDistance = ps.FindOneFloat("filmdistance", 0);
+    const bool caFlag = ps.FindOneBool("chromaticAberrationEnabled", false);
+    mi_lens lens{};
+    std::string err;
+    if (!BuildRealisticLens(lensData, apertureDiameter, filmDistance, focusDistance, diagonal, d.film.full_res, &lens, &scene->warnings, &err)) {
+        Err(err);
+        return;
+    }
+    lens.simple_weighting = simpleWeighting ? 1 : 0;
+    lens.no_weighting = noWeighting ? 1 : 0;
+    lens.chromatic_aberration = caFlag ? 1 : 0;
+    if (simpleWeighting)
+        Warn("\"simpleweighting\" option with RealisticCamera no longer necessarily matches regular camera images. Further, pixel "
+             "values will vary a bit depending on the aperture size.");
+    scene->lensStore.assign(1, lens);
+    d.camera_type = MI_CAMERA_REALISTIC;
+    // (the camera sample's lens dimensions are evaluated for a camera with a lens: mi_camera)
+    d.camera.lens_radius = lens.elements[lens.n_elements - 1][3];
+    d.camera.focal_distance = focusDistance;
 }
 
 // Blackbody / BlackbodyNormalized, src/core/spectrum.cpp:1009-1034
@@ -1639,6 +1687,7 @@ void HostScene::Finalize() {
     d.n_lights = (uint32_t)lights.size(); d.lights = lights.data();
     d.n_instances = (uint32_t)instances.size(); d.instances = instances.empty() ? nullptr : instances.data();
     d.prim_meta = primMeta.size() == prims.size() && !primMeta.empty() ? primMeta.data() : nullptr;
+    d.lens = (d.camera_type == MI_CAMERA_REALISTIC && !lensStore.empty()) ? lensStore.data() : nullptr;
     d.light_distrib.func = ldFunc.empty() ? nullptr : ldFunc.data();
     d.light_distrib.cdf = ldCdf.empty() ? nullptr : ldCdf.data();
     d.light_distrib.func_int = ldFuncInt.empty() ? nullptr : ldFuncInt.data();

@@ -48,6 +48,7 @@ struct HostScene {
     std::vector<HostMipMap> mipStore;   // storage behind desc.mipmaps
     std::vector<mi_mipmap> mipmaps;
     std::vector<mi_texture> textures;
+    std::vector<mi_lens> lensStore;       // Camera "realistic": the one record behind desc.lens (empty for a perspective camera)
     std::vector<mi_instance> instances;   // ObjectInstance as TransformedPrimitive (their BVHs follow the world's in `nodes`)
     // Integrator "metadata": the ids of every primitive (parallel to prims) and the names behind them
     std::vector<mi_prim_meta> primMeta;
@@ -108,6 +109,12 @@ void ComputeHaltonTables(int nDims, std::vector<int32_t> *primes, std::vector<in
 float RadicalInverseHost(int baseIndex, uint64_t a);  // unscrambled, lowdiscrepancy.cpp:389-424
 // Sobol' tables for a film whose sample bounds span `extent` pixels (sobol.h:51-62); false when the resolution is beyond the tables.
 bool ComputeSobolTables(int extent, int nDims, HostScene *scene, int *resolution, int *log2Resolution);
+
+// Camera "realistic" (realistic.cpp in this directory; src/cameras/realistic.cpp:126-187, 934-989): the element table from the
+// lens file's values (4 per interface, mm), the focused film distance and the exit-pupil boxes. diagonal: Film::diagonal in
+// metres. false with *err: what the reference reports as an error or CHECKs away.
+bool BuildRealisticLens(std::vector<float> lensData, float apertureDiameter, float filmDistance, float focusDistance,
+                        float diagonal, const int fullRes[2], mi_lens *lens, std::vector<std::string> *warnings, std::string *err);
 
 // Light-selection distributions, src/core/lightdistrib.cpp:48-300.
 void BuildLightDistribution(HostScene *scene, const std::string &strategy);

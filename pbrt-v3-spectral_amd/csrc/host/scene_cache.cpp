@@ -16,7 +16,7 @@
 namespace mipt {
 namespace {
 
-const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '6'};
+const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '7'};
 
 struct Out {
     FILE *f;
@@ -68,6 +68,7 @@ void Fields(IO &io, S &s) {   // the same walk writes and reads
     io.Str(s.filmFilename); io.Str(s.integratorName); io.Str(s.samplerName); io.Str(s.lightStrategy);
     io.Strs(s.warnings); io.Strs(s.errors);
     io.Vec(s.primMeta); io.Strs(s.instanceNames); io.Strs(s.namedMaterialNames); io.Vec(s.namedMaterialIds);   // Integrator "metadata" (kind and strategy travel in desc)
+    io.Vec(s.lensStore);   // Camera "realistic" (the camera's type travels in desc)
 }
 
 }  // namespace
@@ -156,7 +157,9 @@ HostScene *LoadSceneCache(const std::string &path, std::string *err) {
                       s->materials.size() == d.n_materials && s->lights.size() == d.n_lights && s->textures.size() == d.n_textures && s->instances.size() == d.n_instances &&
                       s->envStore.size() == d.n_envmaps && s->mipStore.size() == d.n_mipmaps && d.sampler.n_dims >= 0 && (int)s->primes.size() == d.sampler.n_dims &&
                       s->primeSums.size() == s->primes.size() && s->perms.size() == d.sampler.n_perms &&
-                      (s->primMeta.empty() || s->primMeta.size() == d.n_prims) && s->namedMaterialIds.size() == s->namedMaterialNames.size();
+                      (s->primMeta.empty() || s->primMeta.size() == d.n_prims) && s->namedMaterialIds.size() == s->namedMaterialNames.size() &&
+                      s->lensStore.size() == (d.camera_type == MI_CAMERA_REALISTIC ? 1u : 0u) && (d.camera_type == MI_CAMERA_PERSPECTIVE || d.camera_type == MI_CAMERA_REALISTIC) &&
+                      (s->lensStore.empty() || (s->lensStore[0].n_elements >= 1 && s->lensStore[0].n_elements <= MI_MAX_LENS_ELEMENTS));
     if (consistent) {   // light-selection tables (mi_lightdistrib): UNIFORM / POWER carry one distribution, SPATIAL none (built on the device)
         if (d.n_lights == 0 || d.light_distrib.type == MI_LD_SPATIAL) consistent = s->ldFunc.empty() && s->ldCdf.empty() && s->ldFuncInt.empty();
         else consistent = s->ldFunc.size() == d.n_lights && s->ldCdf.size() == (size_t)d.n_lights + 1 && s->ldFuncInt.size() == 1;
