@@ -140,12 +140,15 @@ enum : int {
     F_DIFF = 1024,      // the path ray is still the camera ray: it has ray differentials (RayDifferential::hasDifferentials)
     // F_CAND: the line that does not hold L holds L + the pending light sample's contribution (see F_L_IN_B); the shadow ray
     // decides. F_NEE_NZ: that contribution has a non-zero bin.
-    F_CAND = 2048, F_NEE_NZ = 4096,
-    // The BSDF-sampled (MIS) ray is traced, but it cannot reach the sampled area light (it misses the dilated bounds of the
-    // light's shape: Sphere::Pdf gives every direction the cone's pdf, sphere.cpp:294-310, so the estimate goes on for rays
-    // that point away from the sphere), so its contribution was neither formed nor stored in Q_LMIS.
-    F_MIS_DARK = 8192
+    F_CAND = 2048, F_NEE_NZ = 4096
 };
+// A DARK MIS ray has no flag: the BSDF-sampled ray is traced (the reference traces and counts it), but it cannot reach the
+// sampled area light -- it misses the dilated bounds of the light's shape: Sphere::Pdf gives every direction the cone's pdf,
+// sphere.cpp:294-310, so the estimate goes on for rays that point away from the sphere -- so its contribution is neither
+// formed nor stored in Q_LMIS and nothing reads its answer. For the state machine such an estimate has no MIS ray at all
+// (no F_MIS): the shadow ray's commit closes it (CommitShadowVerdict), or k_shade itself when there is no shadow ray either.
+// The ray still goes to the MIS queue, marked in its record (MIS_EXCL_DARK), the traversal answers MIS_ANSWER_DARK in the
+// queue's answer words and touches no slot, and k_resolve_mis skips the entry on that word alone.
 // The I_FLAGS word carries the path's bounce count and sampler dimension beside the flags: bits 0-13 the flags above, 14-21
 // `bounces` (mi_pt_create bounds max_depth by 255), 22-31 the next sampler dimension (the Halton / Sobol' tables end at 1000 /
 // 1024 dimensions; the random sampler only counts). Three 4-byte planes used to hold them: a shading lane read and wrote
@@ -153,7 +156,7 @@ enum : int {
 // path. One word: every kernel that reads the flags has the other two for nothing. (A pixel sampler's two table counters
 // need 32 bits: they stay in the I_DIM plane.)
 constexpr int FLAG_BITS = 14, FLAG_MASK = (1 << FLAG_BITS) - 1, BOUNCE_SHIFT = 14, DIM_SHIFT = 22;
-static_assert(F_MIS_DARK < (1 << FLAG_BITS), "slot flags outgrew their field");
+static_assert(F_NEE_NZ < (1 << FLAG_BITS), "slot flags outgrew their field");
 DEV int LPlane(int flags) { return (flags & F_L_IN_B) ? Q_LB : Q_L; }        // the line that holds the path's L
 DEV int LOtherPlane(int flags) { return (flags & F_L_IN_B) ? Q_L : Q_LB; }   // ... and the one for the candidate
 DEV int StateWord(int flags, int bounces, int dim) { return (flags & FLAG_MASK) | ((bounces & 0xff) << BOUNCE_SHIFT) | (int)((unsigned)(dim & 0x3ff) << DIM_SHIFT); }
@@ -177,6 +180,8 @@ DEV bool RaySpanInBox(const V3 &o, const V3 &d, const float4 &bmin, const float4
     return !(t0 > t1);
 }
 constexpr unsigned MIS_EXCL_BITS = 27, MIS_EXCL_NONE = (1u << MIS_EXCL_BITS) - 1u;
+constexpr unsigned MIS_EXCL_DARK = MIS_EXCL_NONE - 1u;   // in place of the light's primitive: a dark ray (no primitive has this number, BuildLightPrims)
+constexpr unsigned MIS_ANSWER_DARK = 0x80000000u;        // bit 31 of a MIS ray's second answer word (beside the postponed quadrics): a dark ray's
 // The two words k_trav<3> reads beside a MIS ray (R_MI1.z, .w): the end tHi of the span in which the sampled light's shape can
 // be hit, and that shape's primitive | c << 27 with tLo = tHi (1 - 2^-c) at or below the span's start (c = 0: tLo = 0).
 DEV void MisSpanWords(float lo, float hi, unsigned prim, float *tHi, float *word) {
@@ -204,7 +209,8 @@ struct Pool {
                                // PEND_OVERFLOW) -- in queue order, so k_resolve_shadow reads it as whole lines where the
                                // hit words of the slot planes cost it a sector each. misQ[n + 2k], [n + 2k + 1]: hit
                                // primitive and postponed quadrics of MIS ray k, likewise (its t and barycentrics, which
-                               // k_resolve_mis rarely needs, stay in the slot's R_HIT)
+                               // k_resolve_mis rarely needs, stay in the slot's R_HIT). A dark ray's second word is
+                               // MIS_ANSWER_DARK: k_resolve_mis skips the entry without touching its slot
     uint32_t *extQ;            // this iteration's path rays: new camera rays from the front (coherent: consecutive
                                // samples of a pixel), continuing paths from the back
     uint32_t *shadeQ;          // slots to shade: MAX_CLASSES queues of n entries, one per shading class
@@ -712,8 +718,9 @@ template <int MODE, bool ALPHA, int W, bool INST = false>
 // rules: a primitive other than the light's that is accepted below tLo ends the ray (occluded whatever the visiting order);
 // one accepted inside the span only marks the ray ambiguous (the outcome depends on the order in which the reference meets
 // the two), and an ambiguous ray, or one that met a quadric, is traversed again by the reference-order routine
-// (k_resolve_overflow). Rays towards the environment light, and the rays whose answer nothing reads (F_MIS_DARK), carry
-// tLo = tHi = infinity: any hit ends them.
+// (k_resolve_overflow). Rays towards the environment light, and the dark rays, whose answer nothing reads (MIS_EXCL_DARK),
+// carry tLo = tHi = infinity: any hit ends them. A dark ray is traced and counted like any other -- by this kernel or by
+// MODE 2, whichever the scene uses -- but it writes nothing at its slot: its answer is MIS_ANSWER_DARK.
 #define TRAV_IS_ANY(MODE_) ((MODE_) == 1 || (MODE_) == 3)
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu((TRAV_IS_ANY(MODE) && !ALPHA) ? MIPT_TRAV_WAVES_PER_EU_ANY : MIPT_TRAV_WAVES_PER_EU, (TRAV_IS_ANY(MODE) && !ALPHA) ? MIPT_TRAV_WAVES_PER_EU_ANY : MIPT_TRAV_WAVES_PER_EU)))
 k_trav(DScene s, Pool pool, DevCounters *ctr) {
@@ -722,7 +729,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
     constexpr bool MISANY = (MODE == 3);
     constexpr int QM = MISANY ? 2 : MODE;   // the queue and cursor of the class
     static_assert(!(MISANY && INST), "the visibility form of the MIS rays is not built for scenes with instances");
-    int excl = -1;                          // MISANY: the sampled light's primitive
+    int excl = -1;                          // MISANY: the sampled light's primitive. MODE 2 as well: MIS_EXCL_DARK or not
     float tLo = 0;                          // MISANY: hits accepted at or beyond it are ambiguous
     bool ambiguous = false;
     const int lane = threadIdx.x;
@@ -784,6 +791,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                             if (MODE == 0) InitRayCtx(r, r0.x, r0.y, r0.z, r1.x, r1.y, r1.z);
                             else InitRayCtx(r, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y);
                             tMax = (MODE == 0) ? r0.w : ((MODE == 1) ? 1 - kShadowEpsilon : (MISANY ? r1.z : kInfinity));
+                            if (MODE == 2) excl = (int)(__float_as_uint(r1.w) & MIS_EXCL_NONE);
                             if (MISANY) {   // (k_shade: R_MI1 = d.y, d.z, tHi, light primitive | width code << 27; tLo = tHi (1 - 2^-code))
                                 const unsigned xw = __float_as_uint(r1.w);
                                 excl = (int)(xw & MIS_EXCL_NONE);
@@ -801,10 +809,11 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                             if (st.cur >= 0) has = true;
                             else if (MODE == 1) pool.shadowQ[pool.n + myEntry] = 0u;   // nothing to traverse: unoccluded
                             else if (MODE == 2) {
-                                *reinterpret_cast<uint2 *>(pool.misQ + pool.n + 2 * (size_t)myEntry) = make_uint2(0xffffffffu, 0u);
-                                pool.R(R_HIT, slot) = make_float4(0.f, 0.f, 0.f, 0.f);
+                                const bool dark = excl == (int)MIS_EXCL_DARK;
+                                *reinterpret_cast<uint2 *>(pool.misQ + pool.n + 2 * (size_t)myEntry) = make_uint2(0xffffffffu, dark ? MIS_ANSWER_DARK : 0u);
+                                if (!dark) pool.R(R_HIT, slot) = make_float4(0.f, 0.f, 0.f, 0.f);
                             } else if (MISANY) {
-                                *reinterpret_cast<uint2 *>(pool.misQ + pool.n + 2 * (size_t)myEntry) = make_uint2(0xffffffffu, 0u);
+                                *reinterpret_cast<uint2 *>(pool.misQ + pool.n + 2 * (size_t)myEntry) = make_uint2(0xffffffffu, excl == (int)MIS_EXCL_DARK ? MIS_ANSWER_DARK : 0u);
                             } else {  // the ray misses the world bound: nothing to traverse
                                 pool.I(I_HITPRIM, slot) = -1;
                                 pool.I(I_NPEND, slot) = 0;
@@ -974,6 +983,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                     }
                 } else
                 if (MISANY && prim == excl) {}   // the sampled light's own shape
+                else if ((MODE >= 2) && (pf & PRIM_FLAG_SPHERE) && excl == (int)MIS_EXCL_DARK) {}   // (a dark ray's quadrics: nothing resolves them)
                 else if (pf & PRIM_FLAG_SPHERE) {
                     if ((nPend & 0xff) < MAX_PEND) {
                         pool.I(I_PEND0 + (nPend & 0xff), slot) = prim;
@@ -1040,13 +1050,14 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                 leafCnt = 0;
             } else
             if (finished && MODE == 2) {
-                *reinterpret_cast<uint2 *>(pool.misQ + pool.n + 2 * (size_t)myEntry) = make_uint2((unsigned)hitPrim, (unsigned)nPend);
-                pool.R(R_HIT, slot) = make_float4(hitT, hitB0, hitB1, hitB2);
+                const bool dark = excl == (int)MIS_EXCL_DARK;
+                *reinterpret_cast<uint2 *>(pool.misQ + pool.n + 2 * (size_t)myEntry) = make_uint2((unsigned)hitPrim, dark ? MIS_ANSWER_DARK : (unsigned)nPend);
+                if (!dark) pool.R(R_HIT, slot) = make_float4(hitT, hitB0, hitB1, hitB2);
                 has = false;
                 leafCnt = 0;
             } else
             if (finished && MISANY) {   // an occluder's primitive, -1: nothing in front of the light's span, -2: ambiguous
-                *reinterpret_cast<uint2 *>(pool.misQ + pool.n + 2 * (size_t)myEntry) = make_uint2(hitPrim >= 0 ? (unsigned)hitPrim : (ambiguous ? 0xfffffffeu : 0xffffffffu), (unsigned)nPend);
+                *reinterpret_cast<uint2 *>(pool.misQ + pool.n + 2 * (size_t)myEntry) = make_uint2(hitPrim >= 0 ? (unsigned)hitPrim : (ambiguous ? 0xfffffffeu : 0xffffffffu), excl == (int)MIS_EXCL_DARK ? MIS_ANSWER_DARK : (unsigned)nPend);
                 has = false;
                 leafCnt = 0;
             } else
@@ -1307,9 +1318,10 @@ DEV bool AddMisContribution(const Pool &pool, uint32_t slot, int &flags) {
     return added;
 }
 // The MIS ray closes its vertex's direct-lighting estimate: zero radiance if neither it nor the light sample (F_A_ADDED) added.
+// (Not a dark ray: its estimate never had F_MIS and was closed with added = false by CommitShadowVerdict or by k_shade.)
 DEV void CloseMisEstimate(const Pool &pool, uint32_t slot, int flags, bool added, unsigned &zero) {
     if (!added && !(flags & F_A_ADDED)) ++zero;
-    pool.I(I_FLAGS, slot) = flags & ~(F_NEE | F_MIS | F_A_ADDED | F_MIS_DARK);
+    pool.I(I_FLAGS, slot) = flags & ~(F_NEE | F_MIS | F_A_ADDED);
 }
 
 // A MIS ray and the record of the hit k_trav<2> found for it (h.prim comes with the queue entry). They are fetched only by the
@@ -1350,7 +1362,7 @@ DEV void ResolveMisSlot(const DScene &s, const Pool &pool, DevCounters *ctr, uin
     if (!found && s.lights[misLight].type == MI_LIGHT_INFINITE) added |= AddMisContribution(pool, slot, flags);   // Li = light.Le(ray), integrator.cpp:204
     if (found) {
         const int lightNum = misLight;
-        if (s.prims[h.prim].area_light == lightNum && !(flags & F_MIS_DARK)) {   // (dark: cannot happen, the bounds are conservative)
+        if (s.prims[h.prim].area_light == lightNum) {
             const mi_light &l = s.lights[lightNum];
             bool emit = l.two_sided != 0;
             if (!emit) {
@@ -1370,9 +1382,8 @@ DEV void ResolveMisSlot(const DScene &s, const Pool &pool, DevCounters *ctr, uin
 // hit beyond the span, goes to k_resolve_overflow: the closest-hit routine in the reference's order, then ResolveMisSlot.
 DEV void ResolveMisVisibility(const DScene &s, const Pool &pool, DevCounters *ctr, uint32_t slot, int word0, int npend, unsigned &zero) {
     int flags = pool.I(I_FLAGS, slot);
-    const bool dark = (flags & F_MIS_DARK) != 0;   // (nothing reads the ray's answer)
-    bool exact = !dark && (npend & PEND_OVERFLOW) != 0, add = false;
-    if (!exact && !dark) {
+    bool exact = (npend & PEND_OVERFLOW) != 0, add = false;
+    if (!exact) {
         const int misLight = s.nLights > 1 ? pool.I(I_MISLIGHT, slot) : 0;
         const mi_light &l = s.lights[misLight];
         if (l.type == MI_LIGHT_INFINITE) {   // Li = light.Le(ray) if nothing is hit, integrator.cpp:204
@@ -1418,6 +1429,7 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_mis(DScene s, Pool pool, DevC
     unsigned zero = 0;
     for (uint32_t qi = blockIdx.x * BLOCK + threadIdx.x; qi < count; qi += gridDim.x * BLOCK) {
         const uint2 v = *reinterpret_cast<const uint2 *>(pool.misQ + pool.n + 2 * (size_t)qi);   // k_trav<2>'s / k_trav<3>'s answer, in queue order
+        if (v.y & MIS_ANSWER_DARK) continue;   // a dark ray: nothing reads its answer, and its estimate is closed already
         if (!INST && s.misAny) ResolveMisVisibility(s, pool, ctr, pool.misQ[qi], (int)v.x, (int)v.y, zero);
         else ResolveMisSlot<INST, false>(s, pool, ctr, pool.misQ[qi], (int)v.x, (int)v.y, zero);
     }
@@ -2007,6 +2019,9 @@ DEV void StoreSpectrumLines(SpectrumTile &t, const Pool &pool, int spectrum, uin
 // LENS (textured instances only, chosen per launch for a realistic camera in front of textures: DScene::lensDiff): the
 // camera ray's differentials are loaded from the pool planes k_generate wrote (P_LENSDIFF); the LENS = false instances hold
 // no trace of that and compile to the code they were.
+// k_shade's own note beside the flags it is forming: the vertex has a dark MIS ray, which goes to the MIS queue but not into
+// the state word (StateWord keeps FLAG_BITS bits).
+constexpr int SHADE_DARK_RAY = 1 << FLAG_BITS;
 template <int NL, unsigned TM, bool LENS = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT_SHADE_WAVES_PER_EU, 8))) k_shade(DScene s, Pool pool, DevCounters *ctr, unsigned classes) {
     // the grid covers the queues of `classes` back to back, each padded to whole blocks
@@ -2412,7 +2427,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                 const Divisor spDiv = MakeDivisor(sPdf);
                                 bool fNonBlack = false;
                                 // a ray that cannot reach the sampled area light is traced all the same (the reference
-                                // traces it), but its contribution is never read: F_MIS_DARK
+                                // traces it), but its contribution is never read: a dark ray (MIS_EXCL_DARK)
                                 const Ray mr = SpawnRay(isect, wi);
                                 float spanLo = 0.f, spanHi = kInfinity;
                                 const bool dark = go && !isEnvLight && !RaySpanInBox(mr.o, mr.d, s.lightBounds[2 * lightNum], s.lightBounds[2 * lightNum + 1], &spanLo, &spanHi);
@@ -2536,11 +2551,12 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                 }
                                 StoreSpectrumLines(tile, pool, Q_LMIS, slot, go && !dark);   // whole 128-B lines, as for the light sample
                                 if (fNonBlack && go) {
-                                    if (dark) newFlags |= F_MIS_DARK;
+                                    // (a dark ray is queued and traced, but the estimate does not wait for it: no F_MIS)
+                                    if (dark) misWord = __uint_as_float(MIS_EXCL_DARK | (31u << MIS_EXCL_BITS));
                                     pool.R(R_MI0, slot) = make_float4(mr.o.x, mr.o.y, mr.o.z, mr.d.x);
                                     pool.R(R_MI1, slot) = make_float4(mr.d.y, mr.d.z, misTHi, misWord);
-                                    if (s.nLights > 1) pool.I(I_MISLIGHT, slot) = lightNum;   // (one light: k_resolve_mis knows which)
-                                    newFlags |= F_MIS;
+                                    if (s.nLights > 1 && !dark) pool.I(I_MISLIGHT, slot) = lightNum;   // (one light: k_resolve_mis knows which)
+                                    newFlags |= dark ? SHADE_DARK_RAY : F_MIS;
                                 }
                             }
                         }
@@ -2680,7 +2696,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             if (finished) {
                 // ReportValue(pathLength, bounces): `bounces` at the break of path.cpp's loop
                 pathLen = (unsigned)bounces;
-                newFlags = (newFlags & (F_NEE | F_SHADOW | F_MIS | F_CAND | F_NEE_NZ | F_MIS_DARK)) | F_FINISHED;
+                newFlags = (newFlags & (F_NEE | F_SHADOW | F_MIS | F_CAND | F_NEE_NZ | SHADE_DARK_RAY)) | F_FINISHED;
             } else {
                 newFlags |= F_ALIVE;
             }
@@ -2688,9 +2704,9 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             newFlags |= flags & F_L_IN_B;
             if (betaOne && !betaWritten) newFlags |= F_BETA_ONE;
             wantShadow = (newFlags & F_SHADOW) != 0;
-            wantMis = (newFlags & F_MIS) != 0;
-            // a direct-lighting estimate with neither ray pending is already known to be black
-            if ((newFlags & F_NEE) && !wantShadow && !wantMis) { ++zeroNow; newFlags &= ~F_NEE; }
+            wantMis = (newFlags & (F_MIS | SHADE_DARK_RAY)) != 0;
+            // a direct-lighting estimate with neither ray pending (a dark MIS ray is none) is already known to be black
+            if ((newFlags & F_NEE) && !wantShadow && !(newFlags & F_MIS)) { ++zeroNow; newFlags &= ~F_NEE; }
             pool.I(I_FLAGS, slot) = StateWord(newFlags, finished ? bounces : bounces + 1, dimNow);
         }
     }
@@ -3813,7 +3829,7 @@ std::vector<float4> BuildPrimRecords(const mi_scene_desc *d, const std::vector<i
     return pt3;
 }
 
-// Dilated world bounds of the area lights' shapes (F_MIS_DARK), two float4 per light (min, max).
+// Dilated world bounds of the area lights' shapes (dark MIS rays, MIS_EXCL_DARK), two float4 per light (min, max).
 std::vector<float4> BuildLightBounds(const mi_scene_desc *d) {
     std::vector<float4> lb((size_t)std::max<uint32_t>(d->n_lights, 1) * 2, float4{-INFINITY, -INFINITY, -INFINITY, 0});
     for (uint32_t i = 0; i < d->n_lights; ++i) {
@@ -3854,7 +3870,7 @@ std::vector<float4> BuildLightBounds(const mi_scene_desc *d) {
 // emitter's own mesh, and every area light the shape of exactly one primitive.
 std::vector<int> BuildLightPrims(const mi_scene_desc *d, bool &misAny) {
     std::vector<int> lp((size_t)std::max<uint32_t>(d->n_lights, 1), (int)MIS_EXCL_NONE), seen((size_t)std::max<uint32_t>(d->n_lights, 1), 0);
-    bool ok = d->n_instances == 0 && d->n_prims < MIS_EXCL_NONE;
+    bool ok = d->n_instances == 0 && d->n_prims < MIS_EXCL_DARK;
     for (uint32_t i = 0; i < d->n_prims; ++i) {
         const int al = d->prims[i].area_light;
         if (al < 0) continue;
