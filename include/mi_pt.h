@@ -529,6 +529,14 @@ int mi_pt_pool_info(mi_pt *pt, uint64_t *slots, uint64_t *bytes);
  * empty; with MIPT_SHADE_GRID=pool in the environment every instance of the plan is launched on pool / 256 + 16 blocks in
  * every iteration. A metadata pass launches none. */
 int mi_pt_shade_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *blocks);
+/* The dark MIS rays of the last render, summed over the sub-renderers: BSDF-sampled rays that cannot reach the sampled light,
+ * traced and counted because the reference does so, read by nothing. Where the live MIS rays are visibility queries (no
+ * object instances, no alpha mask on an emitter's mesh) k_shade lists them in a queue of their own and a traversal launch
+ * of their own walks it, beside the next iteration on a second stream (MIPT_DARK_STREAM=0 in the environment, read at
+ * every render: in line after the live MIS stage). launches: those launches (host-side count); entries: what they found in
+ * the queue; rays: what they traced (= entries); resolve_skipped: dark entries that the resolve kernel of the MIS queue
+ * met and skipped -- 0 for such a scene, the dark rays of the others, which keep one queue and launch nothing here. */
+int mi_pt_dark_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *entries, uint64_t *rays, uint64_t *resolve_skipped);
 void mi_pt_destroy(mi_pt *pt);
 const char *mi_pt_last_error(void);
 

@@ -282,6 +282,8 @@ def hip_lib():
         if hasattr(lib, "mi_pt_shade_grid"):   # (an older build behind MIPT_HIP_LIB still renders: A/Bs against a parent's library)
             lib.mi_pt_shade_grid.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
             lib.mi_pt_shade_launch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(lib, "mi_pt_dark_launch_stats"):
+            lib.mi_pt_dark_launch_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4
         lib.mi_pt_shade_plan.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32,
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -502,6 +504,13 @@ class PathIntegrator:
         if hip_lib().mi_pt_shade_launch_stats(self._h, C.byref(n), C.byref(b)) != 0:
             raise RuntimeError("mi_pt_shade_launch_stats failed: %s" % hip_lib().mi_pt_last_error().decode())
         return int(n.value), int(b.value)
+
+    def dark_launch_stats(self):
+        """(launches, entries, rays, resolve_skipped) of the dark MIS rays in the last render (mi_pt_dark_launch_stats)."""
+        v = [C.c_uint64() for _ in range(4)]
+        if hip_lib().mi_pt_dark_launch_stats(self._h, *[C.byref(x) for x in v]) != 0:
+            raise RuntimeError("mi_pt_dark_launch_stats failed: %s" % hip_lib().mi_pt_last_error().decode())
+        return tuple(int(x.value) for x in v)
 
     def device_film(self):
         p = C.c_void_p()

@@ -147,8 +147,10 @@ enum : int {
 // sphere.cpp:294-310, so the estimate goes on for rays that point away from the sphere -- so its contribution is neither
 // formed nor stored in Q_LMIS and nothing reads its answer. For the state machine such an estimate has no MIS ray at all
 // (no F_MIS): the shadow ray's commit closes it (CommitShadowVerdict), or k_shade itself when there is no shadow ray either.
-// The ray still goes to the MIS queue, marked in its record (MIS_EXCL_DARK), the traversal answers MIS_ANSWER_DARK in the
-// queue's answer words and touches no slot, and k_resolve_mis skips the entry on that word alone.
+// Where the live MIS rays are visibility queries (DScene::misAny) the ray goes to a queue of its own (Pool::darkQ) and
+// k_trav<4> traces it for the counters alone. In the other scenes it still goes to the MIS queue, marked in its record
+// (MIS_EXCL_DARK), k_trav<2> answers MIS_ANSWER_DARK in the queue's answer words and touches no slot, and k_resolve_mis
+// skips the entry on that word alone.
 // The I_FLAGS word carries the path's bounce count and sampler dimension beside the flags: bits 0-13 the flags above, 14-21
 // `bounces` (mi_pt_create bounds max_depth by 255), 22-31 the next sampler dimension (the Halton / Sobol' tables end at 1000 /
 // 1024 dimensions; the random sampler only counts). Three 4-byte planes used to hold them: a shading lane read and wrote
@@ -211,6 +213,9 @@ struct Pool {
                                // primitive and postponed quadrics of MIS ray k, likewise (its t and barycentrics, which
                                // k_resolve_mis rarely needs, stay in the slot's R_HIT). A dark ray's second word is
                                // MIS_ANSWER_DARK: k_resolve_mis skips the entry without touching its slot
+    uint32_t *darkQ;           // DScene::misAny: the slots of this iteration's dark MIS rays (n entries), which then stay out of
+                               // misQ. Nothing answers them: k_trav<4> walks this queue for the counters alone, on a stream
+                               // of its own beside the next iteration (RenderSub)
     uint32_t *extQ;            // this iteration's path rays: new camera rays from the front (coherent: consecutive
                                // samples of a pixel), continuing paths from the back
     uint32_t *shadeQ;          // slots to shade: MAX_CLASSES queues of n entries, one per shading class
@@ -241,7 +246,11 @@ constexpr int STAT_STRIPES = 64;
 struct alignas(128) DevStats {
     unsigned long long cameraRays, regularRays, shadowRays, totalPaths, zeroRadiancePaths, pathLengthSum, nodesVisited,
         triTests, badSamples, extendNodes, extendTris, extendRays;
+    // the dark MIS rays (mi_pt_dark_launch_stats): rays k_trav<4> traced, entries its launches found in Pool::darkQ, and
+    // entries of Pool::misQ that k_resolve_mis skipped as dark (scenes without the queue of their own)
+    unsigned long long darkRays, darkEntries, misDarkSeen;
 };
+static_assert(sizeof(DevStats) == 128, "a stripe of the statistics is one 128-B line");
 struct alignas(128) DevCursor {
     unsigned int v;
 };
@@ -255,8 +264,14 @@ struct DevCounters {
     DevCursor shadeCount[MAX_CLASSES];  // entries in shading queue c
     DevCursor travNext[3];              // work cursors of the persistent traversal kernels (extend/shadow/mis)
     DevCursor ovfCount[3];              // entries in Pool::ovfQ (extend/shadow/mis)
+    // NOT cleared with them: the dark traversal of iteration i runs beside iteration i + 1, whose clear it must not meet.
+    // Whoever launches k_trav<4> clears both behind it, on the kernel's stream.
+    DevCursor darkCount, darkNext;      // entries in Pool::darkQ, and the work cursor of k_trav<4>
 };
 constexpr size_t ITER_CLEAR_BYTES = sizeof(DevCursor) * (5 + MAX_CLASSES + 3 + 3);
+constexpr size_t DARK_CLEAR_BYTES = sizeof(DevCursor) * 2;
+static_assert(offsetof(DevCounters, darkCount) >= offsetof(DevCounters, alive) + ITER_CLEAR_BYTES && offsetof(DevCounters, darkNext) == offsetof(DevCounters, darkCount) + sizeof(DevCursor),
+              "the dark cursors lie behind the block that every iteration clears, side by side");
 DEV DevStats &Stats(DevCounters *ctr) { return ctr->stats[blockIdx.x & (STAT_STRIPES - 1)]; }
 
 struct WorkDesc {
@@ -306,25 +321,27 @@ DEV unsigned BlockReserve(unsigned *counter, bool pred, unsigned *scratch) {
     return base + (unsigned)__popcll(mask & ((1ull << lane) - 1));
 }
 
-// Two reservations behind ONE pair of barriers, their atomics issued by two different waves (k_shade ends in an append to the
-// shadow queue and one to the MIS queue; one after the other they cost two atomic round trips and four barriers).
-// `scratch`: 10 words of LDS.
-DEV void BlockReserve2(unsigned *counterA, bool predA, unsigned *counterB, bool predB, unsigned *scratch, unsigned *posA, unsigned *posB) {
-    const unsigned long long mA = __ballot(predA), mB = __ballot(predB);
+// Three reservations behind ONE pair of barriers, their atomics issued by three different waves (k_shade ends in an append to
+// the shadow queue, one to the MIS queue and one to the queue of the dark MIS rays; one after the other they cost three atomic
+// round trips and six barriers). `scratch`: 15 words of LDS.
+DEV void BlockReserve3(unsigned *counterA, bool predA, unsigned *counterB, bool predB, unsigned *counterC, bool predC, unsigned *scratch,
+                       unsigned *posA, unsigned *posB, unsigned *posC) {
+    const unsigned long long mA = __ballot(predA), mB = __ballot(predB), mC = __ballot(predC);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { scratch[wave] = (unsigned)__popcll(mA); scratch[5 + wave] = (unsigned)__popcll(mB); }
+    if (lane == 0) { scratch[wave] = (unsigned)__popcll(mA); scratch[5 + wave] = (unsigned)__popcll(mB); scratch[10 + wave] = (unsigned)__popcll(mC); }
     __syncthreads();
-    if (threadIdx.x == 0 || threadIdx.x == 64) {
-        unsigned *sc = scratch + (threadIdx.x ? 5 : 0);
+    if (lane == 0 && wave < 3) {
+        unsigned *sc = scratch + 5 * wave;
         const unsigned tot = sc[0] + sc[1] + sc[2] + sc[3];
-        sc[4] = tot ? atomicAdd(threadIdx.x ? counterB : counterA, tot) : 0;
+        sc[4] = tot ? atomicAdd(wave == 0 ? counterA : (wave == 1 ? counterB : counterC), tot) : 0;
     }
     __syncthreads();
-    unsigned a = scratch[4], b = scratch[9];
-    for (int w = 0; w < wave; ++w) { a += scratch[w]; b += scratch[5 + w]; }
+    unsigned a = scratch[4], b = scratch[9], c = scratch[14];
+    for (int w = 0; w < wave; ++w) { a += scratch[w]; b += scratch[5 + w]; c += scratch[10 + w]; }
     const unsigned long long lt = (1ull << lane) - 1ull;
     *posA = a + (unsigned)__popcll(mA & lt);
     *posB = b + (unsigned)__popcll(mB & lt);
+    *posC = c + (unsigned)__popcll(mC & lt);
 }
 
 // ------------------------------------------------------------------ traversal
@@ -666,7 +683,7 @@ DEV void HitInteraction(const DScene &s, int prim, const V3 &ro, const V3 &rd, f
 // ------------------------------------------------------------------ persistent traversal
 // One launch traverses every ray of a class (MODE 0: path rays of the alive slots, closest
 // hit; 1: NEE shadow rays of shadowQ, any hit; 2: MIS rays of misQ, closest hit; 3: the same rays as visibility queries,
-// see TRAV_IS_ANY below). A fixed
+// see TRAV_IS_ANY below; 4: the dark MIS rays of darkQ, any hit, no answer). A fixed
 // grid of waves pulls rays from a device-wide cursor: lanes whose ray finished fetch a new
 // one as soon as fewer than REFILL_BELOW lanes of the wave are still traversing (dynamic
 // fetch), so a long ray no longer idles the other 63 lanes. Quadrics are only recorded
@@ -721,22 +738,23 @@ template <int MODE, bool ALPHA, int W, bool INST = false>
 // (k_resolve_overflow). Rays towards the environment light, and the dark rays, whose answer nothing reads (MIS_EXCL_DARK),
 // carry tLo = tHi = infinity: any hit ends them. A dark ray is traced and counted like any other -- by this kernel or by
 // MODE 2, whichever the scene uses -- but it writes nothing at its slot: its answer is MIS_ANSWER_DARK.
-#define TRAV_IS_ANY(MODE_) ((MODE_) == 1 || (MODE_) == 3)
+#define TRAV_IS_ANY(MODE_) ((MODE_) == 1 || (MODE_) == 3 || (MODE_) == 4)
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu((TRAV_IS_ANY(MODE) && !ALPHA) ? MIPT_TRAV_WAVES_PER_EU_ANY : MIPT_TRAV_WAVES_PER_EU, (TRAV_IS_ANY(MODE) && !ALPHA) ? MIPT_TRAV_WAVES_PER_EU_ANY : MIPT_TRAV_WAVES_PER_EU)))
 k_trav(DScene s, Pool pool, DevCounters *ctr) {
     constexpr bool ANY = TRAV_IS_ANY(MODE);
     constexpr bool PSEM = (MODE == 1);      // Triangle::IntersectP's acceptance rules (MODE 3 asks with Intersect's)
     constexpr bool MISANY = (MODE == 3);
-    constexpr int QM = MISANY ? 2 : MODE;   // the queue and cursor of the class
-    static_assert(!(MISANY && INST), "the visibility form of the MIS rays is not built for scenes with instances");
+    constexpr bool DARK = (MODE == 4);      // the dark MIS rays of Pool::darkQ: MODE 3's walk for tLo = tHi = infinity and no light primitive, no answer
+    constexpr int QM = (MISANY || DARK) ? 2 : MODE;   // the queue and cursor of the class (DARK: DevCounters::darkNext)
+    static_assert(!((MISANY || DARK) && INST), "the visibility form of the MIS rays is not built for scenes with instances");
     int excl = -1;                          // MISANY: the sampled light's primitive. MODE 2 as well: MIS_EXCL_DARK or not
     float tLo = 0;                          // MISANY: hits accepted at or beyond it are ambiguous
     bool ambiguous = false;
     const int lane = threadIdx.x;
     const int wlane = threadIdx.x & 63;
     const unsigned nPrim = (MODE == 0) ? ctr->primCount.v : 0, nCont = (MODE == 0) ? ctr->contCount.v : 0;
-    const unsigned total = (MODE == 0) ? nPrim + nCont : ((MODE == 1) ? ctr->shadowCount.v : ctr->misCount.v);
-    const uint32_t *__restrict__ queue = (MODE == 0) ? pool.extQ : ((MODE == 1) ? pool.shadowQ : pool.misQ);
+    const unsigned total = (MODE == 0) ? nPrim + nCont : ((MODE == 1) ? ctr->shadowCount.v : (DARK ? ctr->darkCount.v : ctr->misCount.v));
+    const uint32_t *__restrict__ queue = (MODE == 0) ? pool.extQ : ((MODE == 1) ? pool.shadowQ : (DARK ? pool.darkQ : pool.misQ));
     (void)excl; (void)tLo; (void)ambiguous;
     const unsigned travChunk = (total >= (1u << 23)) ? 2u * (unsigned)TRAV_CHUNK : (unsigned)TRAV_CHUNK;
     const float4 *__restrict__ primTri = s.primTri;
@@ -771,7 +789,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
             if (idle) {
                 if (chunkNext == chunkEnd) {  // the wave's private range is used up: reserve a chunk more
                     unsigned base = 0;
-                    if (wlane == 0) base = atomicAdd(&ctr->travNext[QM].v, travChunk);
+                    if (wlane == 0) base = atomicAdd(DARK ? &ctr->darkNext.v : &ctr->travNext[QM].v, travChunk);
                     base = __shfl(base, 0, 64);
                     chunkNext = min(base, total);
                     chunkEnd = min(base + travChunk, total);
@@ -784,13 +802,13 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                     if (my < chunkEnd) {
                         if (MODE == 0) slot = queue[(my < nPrim) ? my : pool.n - nCont + (my - nPrim)];
                         else slot = queue[my];
-                        if (MODE != 0) myEntry = my;
+                        if (MODE != 0 && !DARK) myEntry = my;
                         {
                             const float4 r0 = pool.R((MODE == 0) ? R_RAY0 : ((MODE == 1) ? R_SH0 : R_MI0), slot);
                             const float4 r1 = pool.R((MODE == 0) ? R_RAY1 : ((MODE == 1) ? R_SH1 : R_MI1), slot);
                             if (MODE == 0) InitRayCtx(r, r0.x, r0.y, r0.z, r1.x, r1.y, r1.z);
                             else InitRayCtx(r, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y);
-                            tMax = (MODE == 0) ? r0.w : ((MODE == 1) ? 1 - kShadowEpsilon : (MISANY ? r1.z : kInfinity));
+                            tMax = (MODE == 0) ? r0.w : ((MODE == 1) ? 1 - kShadowEpsilon : (MISANY ? r1.z : kInfinity));   // (a dark ray's R_MI1.z is infinity as well)
                             if (MODE == 2) excl = (int)(__float_as_uint(r1.w) & MIS_EXCL_NONE);
                             if (MISANY) {   // (k_shade: R_MI1 = d.y, d.z, tHi, light primitive | width code << 27; tLo = tHi (1 - 2^-code))
                                 const unsigned xw = __float_as_uint(r1.w);
@@ -807,6 +825,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                             curInst = hitInst = -1; hitInCur = false;
                             ++rayCount;
                             if (st.cur >= 0) has = true;
+                            else if (DARK) {}   // (counted; nothing to answer)
                             else if (MODE == 1) pool.shadowQ[pool.n + myEntry] = 0u;   // nothing to traverse: unoccluded
                             else if (MODE == 2) {
                                 const bool dark = excl == (int)MIS_EXCL_DARK;
@@ -917,7 +936,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
 #endif
                         triCount += (unsigned)grant;
                     }
-                } else if (ANY) {
+                } else if (ANY) {   // (DARK: MODE 3's rule with every accepted hit below tLo -- res leaves the degenerate triangles out, PSEM is off)
                     if (seg) { hitPrim = leafOff + (__ffs(seg) - 1); finished = true; triCount += (unsigned)__ffs(seg); }
                     else triCount += (unsigned)grant;
                 } else {
@@ -983,7 +1002,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                     }
                 } else
                 if (MISANY && prim == excl) {}   // the sampled light's own shape
-                else if ((MODE >= 2) && (pf & PRIM_FLAG_SPHERE) && excl == (int)MIS_EXCL_DARK) {}   // (a dark ray's quadrics: nothing resolves them)
+                else if ((MODE >= 2) && (pf & PRIM_FLAG_SPHERE) && (DARK || excl == (int)MIS_EXCL_DARK)) {}   // (a dark ray's quadrics: nothing resolves them)
                 else if (pf & PRIM_FLAG_SPHERE) {
                     if ((nPend & 0xff) < MAX_PEND) {
                         pool.I(I_PEND0 + (nPend & 0xff), slot) = prim;
@@ -1005,6 +1024,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                                 counts = !(pf & PRIM_FLAG_DEGENERATE) && AlphaPass(s, __float_as_int(v1.w), th.b0, th.b1, th.b2, PSEM);   // (the shadow mask is IntersectP's alone, triangle.cpp:531-570)
                         if (!counts) {}
                         else if (PSEM) { hitPrim = prim; finished = true; }
+                        else if (DARK) { if (!(pf & PRIM_FLAG_DEGENERATE)) { hitPrim = prim; finished = true; } }   // (MODE 3 with tLo = infinity)
                         else if (MISANY) {
                             if (!(pf & PRIM_FLAG_DEGENERATE)) {
                                 if (th.t < tLo) { hitPrim = prim; finished = true; }
@@ -1044,6 +1064,10 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                 if (tkMeta > 0) { leafOff = tkChild; leafCnt = tkMeta & LEAF_COUNT_MASK; leafSimple = (tkMeta & LEAF_SIMPLE) != 0; }
                 else st.cur = tkChild;
             }
+            if (finished && DARK) {   // no answer, nothing at the slot
+                has = false;
+                leafCnt = 0;
+            } else
             if (finished && MODE == 1) {
                 pool.shadowQ[pool.n + myEntry] = (hitPrim >= 0 ? 0x80000000u : 0u) | (unsigned)nPend;
                 has = false;
@@ -1084,6 +1108,10 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
     CountAdd(&st8.nodesVisited, nodeCount);
     CountAdd(&st8.triTests, triCount);
     if (MODE == 0) { CountAdd(&st8.extendNodes, nodeCount); CountAdd(&st8.extendTris, triCount); CountAdd(&st8.extendRays, rayCount); }
+    if (DARK) {   // (mi_pt_dark_launch_stats: what the launch found in its queue against what it traced)
+        CountAdd(&st8.darkRays, rayCount);
+        if (blockIdx.x == 0 && threadIdx.x == 0 && total) atomicAdd(&st8.darkEntries, (unsigned long long)total);
+    }
 }
 
 // Quadrics recorded by k_trav, tested after the triangles at full lane utilisation -- with the outcome of the reference's
@@ -1426,14 +1454,17 @@ DEV void ResolveMisVisibility(const DScene &s, const Pool &pool, DevCounters *ct
 template <bool INST>
 __global__ void __launch_bounds__(BLOCK) k_resolve_mis(DScene s, Pool pool, DevCounters *ctr) {
     const unsigned count = ctr->misCount.v;   // (a resident-sized grid walks the queue, as in k_resolve_shadow)
-    unsigned zero = 0;
+    unsigned zero = 0, darkSeen = 0;
     for (uint32_t qi = blockIdx.x * BLOCK + threadIdx.x; qi < count; qi += gridDim.x * BLOCK) {
         const uint2 v = *reinterpret_cast<const uint2 *>(pool.misQ + pool.n + 2 * (size_t)qi);   // k_trav<2>'s / k_trav<3>'s answer, in queue order
-        if (v.y & MIS_ANSWER_DARK) continue;   // a dark ray: nothing reads its answer, and its estimate is closed already
+        // a dark ray: nothing reads its answer, and its estimate is closed already (k_trav<2> scenes and mi_pt_trace_wavefront
+        // only: where k_trav<3> serves the queue the dark rays have Pool::darkQ and none comes by here)
+        if (v.y & MIS_ANSWER_DARK) { ++darkSeen; continue; }
         if (!INST && s.misAny) ResolveMisVisibility(s, pool, ctr, pool.misQ[qi], (int)v.x, (int)v.y, zero);
         else ResolveMisSlot<INST, false>(s, pool, ctr, pool.misQ[qi], (int)v.x, (int)v.y, zero);
     }
     CountAdd(&Stats(ctr).zeroRadiancePaths, zero);
+    CountAdd(&Stats(ctr).misDarkSeen, darkSeen);
 }
 
 // The rays whose list of postponed quadrics overflowed (more than MAX_PEND quadrics met: PEND_OVERFLOW), handed over by
@@ -2042,7 +2073,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
     auto rdTile = [&](int c) -> float4 { return tile.q[c][threadIdx.x]; };
     auto wrTile = [&](int c, const float4 &v) { tile.q[c][threadIdx.x] = v; };
     unsigned totalPaths = 0, pathLen = 0, zeroNow = 0;
-    bool wantShadow = false, wantMis = false;
+    bool wantShadow = false, wantMis = false, wantDark = false;
     uint32_t slot = 0;
     if (cls >= 0 && qi < count) {
         slot = pool.shadeQ[(size_t)cls * pool.n + qi];
@@ -2704,17 +2735,20 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             newFlags |= flags & F_L_IN_B;
             if (betaOne && !betaWritten) newFlags |= F_BETA_ONE;
             wantShadow = (newFlags & F_SHADOW) != 0;
-            wantMis = (newFlags & (F_MIS | SHADE_DARK_RAY)) != 0;
+            // (a dark ray has a queue of its own where k_trav<3> serves the live ones; with k_trav<2> both share misQ)
+            wantDark = s.misAny && (newFlags & SHADE_DARK_RAY) != 0;
+            wantMis = (newFlags & F_MIS) != 0 || (!s.misAny && (newFlags & SHADE_DARK_RAY) != 0);
             // a direct-lighting estimate with neither ray pending (a dark MIS ray is none) is already known to be black
             if ((newFlags & F_NEE) && !wantShadow && !(newFlags & F_MIS)) { ++zeroNow; newFlags &= ~F_NEE; }
             pool.I(I_FLAGS, slot) = StateWord(newFlags, finished ? bounces : bounces + 1, dimNow);
         }
     }
-    __shared__ unsigned sAppend[10];
-    unsigned posS, posM;
-    BlockReserve2(&ctr->shadowCount.v, wantShadow, &ctr->misCount.v, wantMis, sAppend, &posS, &posM);
+    __shared__ unsigned sAppend[15];
+    unsigned posS, posM, posD;
+    BlockReserve3(&ctr->shadowCount.v, wantShadow, &ctr->misCount.v, wantMis, &ctr->darkCount.v, wantDark, sAppend, &posS, &posM, &posD);
     if (wantShadow) pool.shadowQ[posS] = slot;
     if (wantMis) pool.misQ[posM] = slot;
+    if (wantDark) pool.darkQ[posD] = slot;
     {   // the three statistics of a wave in one reduction: per lane at most one path, one black estimate and 255 bounces
         unsigned packed = totalPaths | (zeroNow << 8) | (pathLen << 16);
         for (int off = 32; off > 0; off >>= 1) packed += __shfl_down(packed, off, 64);
@@ -3202,6 +3236,16 @@ struct SubRenderer {
         unsigned alive;                      // extend class, which holds this read, 0.4500 -> 0.4489 s per three killeroo frames)
     } *reads = nullptr;
     unsigned long long shadeLaunches = 0, shadeBlocks = 0;   // k_shade launches of the last render and the blocks they covered
+    // The dark MIS rays of iteration i are traced beside iteration i + 1 (LaunchDarkTraversal): a stream at the lowest
+    // priority, the hand-over from k_shade (evDarkGo), the kernel's own boundaries in two alternating sets (evDark) and its
+    // end with the cursors cleared behind it (evDarkDone), which the next k_shade -- the next writer of darkQ and the
+    // R_MI planes -- waits for.
+    hipStream_t darkStream = nullptr;
+    hipEvent_t evDarkGo = nullptr, evDarkDone = nullptr, evDark[2][2] = {{nullptr}};
+    bool darkPending = false;            // evDarkDone has been recorded and nothing has waited for it yet
+    bool darkTimed[2] = {false, false};  // evDark[k] holds a launch whose time is not in t[5] yet
+    unsigned long long darkSeq = 0;      // launches on darkStream so far (picks the set)
+    unsigned long long darkLaunches = 0; // k_trav<4> launches of the last render
 };
 
 // The k_shade instances by their index in MIPT_SHADE_INSTANCES.
@@ -3280,6 +3324,7 @@ struct mi_pt {
     int resolveBlocksPerCU[3] = {0};    // [1]: k_resolve_shadow, [2]: k_resolve_mis ([0], k_resolve_extend, walks the pool)
     unsigned queueBlocksCap = 0;        // MIPT_QUEUE_BLOCKS (tests): at most so many blocks for those kernels, 0 = unset
     bool shadeGridPool = false;         // MIPT_SHADE_GRID=pool: every k_shade instance on a pool-sized grid, no read of the class counts
+    bool darkInLine = false;            // MIPT_DARK_STREAM=0: k_trav<4> on the main stream after the live MIS stage (the partner for A/B runs and tests)
     // Integrator "metadata" (mi_pt_render_metadata): the ids of the primitives as create copied them, their device copy
     // (made by the first metadata pass: a renderer that only renders radiance holds none) and, during such a pass, its
     // strategy (-1: a radiance render)
@@ -3342,11 +3387,11 @@ long long PassSpp(const mi_pt *pt, const mi_render_params *rp) { return rp->spp_
 // Device bytes of one path slot: planes, records, spectra and its entries in the queues.
 size_t PoolSlotBytes(int nQuadPlanes, int nFloatPlanes) {
     return (size_t)nFloatPlanes * sizeof(float) + (size_t)nQuadPlanes * sizeof(float4) + (size_t)R_COUNT * sizeof(float4) + (size_t)I_COUNT * sizeof(int) +
-           (size_t)(6 + MAX_CLASSES + 3) * sizeof(uint32_t);
+           (size_t)(7 + MAX_CLASSES + 3) * sizeof(uint32_t);
 }
 
 void FreePool(Pool &p) {
-    hipFree(p.f); hipFree(p.q); hipFree(p.r); hipFree(p.i); hipFree(p.shadowQ); hipFree(p.extQ); hipFree(p.misQ); hipFree(p.shadeQ); hipFree(p.ovfQ);
+    hipFree(p.f); hipFree(p.q); hipFree(p.r); hipFree(p.i); hipFree(p.shadowQ); hipFree(p.extQ); hipFree(p.misQ); hipFree(p.darkQ); hipFree(p.shadeQ); hipFree(p.ovfQ);
     p = Pool{};   // n = 0, every pointer null: a later render cannot mistake a half-built pool for a usable one
 }
 
@@ -3366,6 +3411,7 @@ int EnsurePool(SubRenderer &sub, uint32_t n, int nQuadPlanes, int nFloatPlanes) 
                     hipMalloc((void **)&t.shadowQ, (size_t)2 * n * sizeof(uint32_t)) == hipSuccess &&
                     hipMalloc((void **)&t.extQ, (size_t)n * sizeof(uint32_t)) == hipSuccess &&
                     hipMalloc((void **)&t.misQ, (size_t)3 * n * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc((void **)&t.darkQ, (size_t)n * sizeof(uint32_t)) == hipSuccess &&
                     hipMalloc((void **)&t.shadeQ, (size_t)MAX_CLASSES * n * sizeof(uint32_t)) == hipSuccess &&
                     hipMalloc((void **)&t.ovfQ, (size_t)3 * n * sizeof(uint32_t)) == hipSuccess;
     if (!ok) {
@@ -4140,6 +4186,12 @@ int CreateRenderState(mi_pt *pt, const mi_scene_desc *d) {
         for (int a = 0; a < 2; ++a)
             for (int b = 0; b < N_EV; ++b)
                 if (hipEventCreate(&sub.evIter[a][b]) != hipSuccess) { g_err = "hipEventCreate failed"; return MI_ERR_HIP; }
+        int prioLeast = 0, prioGreatest = 0;   // (the lowest priority: the dark traversal fills what the main stream leaves idle)
+        if (hipDeviceGetStreamPriorityRange(&prioLeast, &prioGreatest) != hipSuccess) { (void)hipGetLastError(); prioLeast = 0; }
+        if (hipStreamCreateWithPriority(&sub.darkStream, hipStreamNonBlocking, prioLeast) != hipSuccess) { g_err = "hipStreamCreate failed"; return MI_ERR_HIP; }
+        hipEvent_t *darkEvents[] = {&sub.evDarkGo, &sub.evDarkDone, &sub.evDark[0][0], &sub.evDark[0][1], &sub.evDark[1][0], &sub.evDark[1][1]};
+        for (int k = 0; k < 6; ++k)   // (the two that only order the streams carry no timestamp)
+            if (hipEventCreateWithFlags(darkEvents[k], k < 2 ? hipEventDisableTiming : hipEventDefault) != hipSuccess) { g_err = "hipEventCreate failed"; return MI_ERR_HIP; }
     }
     return MI_OK;
 }
@@ -4153,18 +4205,76 @@ using SceneKernel = void (*)(DScene, Pool, DevCounters *);
 // (BuildBvhTables) and never MODE 3 (misAny is 0 for them): three instances serve them.
 template <int MODE>
 SceneKernel TravKernel(const mi_pt *pt) {
-    if (pt->hasInstances) return k_trav<MODE == 3 ? 2 : MODE, true, 4, true>;
+    if (pt->hasInstances) return k_trav<MODE >= 3 ? 2 : MODE, true, 4, true>;   // (never asked for MODE 3 or 4)
     const bool w4 = pt->scene.bvhWidth == 4;
     if (pt->hasAlphaMasks) return w4 ? k_trav<MODE, true, 4> : k_trav<MODE, true, 2>;
     return w4 ? k_trav<MODE, false, 4> : k_trav<MODE, false, 2>;
 }
 
 // `closestMis`: the MIS rays (mode 2) with the closest-hit kernel even where the scene could ask them as visibility queries.
-void LaunchTraversal(mi_pt *pt, SubRenderer &sub, int mode, dim3 travGrid, bool closestMis = false) {
+// Mode 4: the dark MIS rays of Pool::darkQ (DScene::misAny scenes only). `beside`: on that stream and on exactly `travGrid`.
+void LaunchTraversal(mi_pt *pt, SubRenderer &sub, int mode, dim3 travGrid, bool closestMis = false, hipStream_t beside = nullptr) {
     if (mode == 2 && pt->scene.misAny && !closestMis) mode = 3;   // the MIS rays as visibility queries (k_trav, MODE 3)
-    if (TRAV_IS_ANY(mode) && !pt->hasAlphaMasks && !pt->hasInstances && travGrid.x == (unsigned)pt->numCUs * TRAV_BLOCKS_PER_CU) travGrid.x = (unsigned)pt->numCUs * MIPT_TRAV_WAVES_PER_EU_ANY;   // (a full-size launch: one more block per CU)
-    const SceneKernel k = mode == 0 ? TravKernel<0>(pt) : mode == 1 ? TravKernel<1>(pt) : mode == 3 ? TravKernel<3>(pt) : TravKernel<2>(pt);
-    hipLaunchKernelGGL(k, travGrid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr);
+    if (!beside && TRAV_IS_ANY(mode) && !pt->hasAlphaMasks && !pt->hasInstances && travGrid.x == (unsigned)pt->numCUs * TRAV_BLOCKS_PER_CU) travGrid.x = (unsigned)pt->numCUs * MIPT_TRAV_WAVES_PER_EU_ANY;   // (a full-size launch: one more block per CU)
+    const SceneKernel k = mode == 0 ? TravKernel<0>(pt) : mode == 1 ? TravKernel<1>(pt) : mode == 3 ? TravKernel<3>(pt) : mode == 4 ? TravKernel<4>(pt) : TravKernel<2>(pt);
+    hipLaunchKernelGGL(k, travGrid, dim3(BLOCK), 0, beside ? beside : sub.stream, pt->scene, sub.pool, sub.ctr);
+}
+
+// The dark MIS rays (DScene::misAny: Pool::darkQ, k_trav<4>). Nothing inside the iteration reads what the kernel does -- it
+// adds to regularRays, nodesVisited and triTests -- so it need not stand in the chain of dependent launches: it runs on
+// SubRenderer::darkStream from the end of k_shade, beside the shadow and live MIS stages and the next iteration's k_generate,
+// k_trav<0> and k_resolve_extend, on a grid small enough to leave those their blocks. It reads darkQ and the R_MI planes,
+// whose next writer is the next k_shade: LaunchShade waits for evDarkDone. All ordering is stream events.
+// MIPT_DARK_BLOCKS_PER_CU: the grid of that launch. MIPT_DARK_AFTER_SHADOW: hand over after k_resolve_shadow instead.
+#ifndef MIPT_DARK_BLOCKS_PER_CU
+#define MIPT_DARK_BLOCKS_PER_CU 3   // (same-box A/B of 1, 2, 3, 5 at both hand-over points: DESIGN.md, round 7)
+#endif
+#ifndef MIPT_DARK_AFTER_SHADOW
+#define MIPT_DARK_AFTER_SHADOW 0
+#endif
+static_assert(MIPT_DARK_BLOCKS_PER_CU >= 1 && MIPT_DARK_BLOCKS_PER_CU <= MIPT_TRAV_WAVES_PER_EU_ANY, "MIPT_DARK_BLOCKS_PER_CU: 1 .. the blocks of the any-hit kernels that a CU holds");
+static_assert(MIPT_DARK_AFTER_SHADOW == 0 || MIPT_DARK_AFTER_SHADOW == 1, "MIPT_DARK_AFTER_SHADOW: 0 or 1");
+
+// The time of the launch in evDark[k] into the MIS class. Called when the host knows that launch complete.
+void HarvestDark(SubRenderer &sub, int k) {
+    if (!sub.darkTimed[k]) return;
+    sub.darkTimed[k] = false;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, sub.evDark[k][0], sub.evDark[k][1]) == hipSuccess) sub.t[5] += ms * 1e-3;
+    else (void)hipGetLastError();   // (a time not had is no reason to stop the render, and must not be taken for a launch's error)
+}
+
+int LaunchDarkBeside(mi_pt *pt, SubRenderer &sub, unsigned poolBlocks) {
+    const int k = (int)(sub.darkSeq & 1);
+    // the launch before the last used this set: the k_shade after it waited for its end, and the host has waited for the
+    // main stream since (the read after k_generate)
+    HarvestDark(sub, k);
+    HIPCHK(hipEventRecord(sub.evDarkGo, sub.stream));
+    HIPCHK(hipStreamWaitEvent(sub.darkStream, sub.evDarkGo, 0));
+    HIPCHK(hipEventRecord(sub.evDark[k][0], sub.darkStream));
+    LaunchTraversal(pt, sub, 4, dim3(std::min(poolBlocks, (unsigned)pt->numCUs * MIPT_DARK_BLOCKS_PER_CU)), false, sub.darkStream);
+    HIPCHK(hipEventRecord(sub.evDark[k][1], sub.darkStream));
+    HIPCHK(hipMemsetAsync(&sub.ctr->darkCount, 0, DARK_CLEAR_BYTES, sub.darkStream));
+    HIPCHK(hipEventRecord(sub.evDarkDone, sub.darkStream));
+    sub.darkTimed[k] = true;
+    sub.darkPending = true;
+    ++sub.darkSeq; ++sub.darkLaunches;
+    return MI_OK;
+}
+
+// MIPT_DARK_STREAM=0, and the tools that step through an iteration: the same kernel in line, after the live MIS stage.
+int LaunchDarkInLine(mi_pt *pt, SubRenderer &sub, dim3 travGrid) {
+    LaunchTraversal(pt, sub, 4, travGrid);
+    HIPCHK(hipMemsetAsync(&sub.ctr->darkCount, 0, DARK_CLEAR_BYTES, sub.stream));
+    ++sub.darkLaunches;
+    return MI_OK;
+}
+
+// Before the next writer of darkQ and the R_MI planes, and before the counters are read: the main stream behind the dark one.
+int JoinDark(SubRenderer &sub) {
+    if (sub.darkPending) HIPCHK(hipStreamWaitEvent(sub.stream, sub.evDarkDone, 0));
+    sub.darkPending = false;
+    return MI_OK;
 }
 
 // The grid of a kernel that walks a queue in steps of the grid (k_resolve_shadow, k_resolve_mis): QUEUE_GRID_RESIDENT times the
@@ -4186,6 +4296,8 @@ void ReadQueueBlocksCap(mi_pt *pt) {
     pt->queueBlocksCap = e ? (unsigned)std::max(0, atoi(e)) : 0u;
     e = getenv("MIPT_SHADE_GRID");   // (read with it, at every render: "pool" = the grids before the class counts sized them)
     pt->shadeGridPool = e && strcmp(e, "pool") == 0;
+    e = getenv("MIPT_DARK_STREAM");   // (likewise: "0" = the dark MIS rays in line on the main stream)
+    pt->darkInLine = e && strcmp(e, "0") == 0;
 }
 // The resolve kernels of the three ray classes, by [class][instanced].
 const SceneKernel kResolve[3][2] = {{k_resolve_extend<false>, k_resolve_extend<true>},
@@ -4244,6 +4356,10 @@ int LaunchShade(mi_pt *pt, SubRenderer &sub, dim3 grid) {
     uint32_t counts[MAX_CLASSES];
     if (!pt->shadeGridPool) {
         const int rc = ReadShadeCounts(sub, counts);
+        if (rc != MI_OK) return rc;
+    }
+    {   // (behind the read, so that the host does not wait for the dark traversal as well)
+        const int rc = JoinDark(sub);
         if (rc != MI_OK) return rc;
     }
     for (int i = 0; i < N_SHADE_INSTANCES; ++i) {
@@ -4320,6 +4436,10 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
     while (2 * wd.run <= runCap && wd.spp % (2 * wd.run) == 0) wd.run *= 2;
     sub.iterations = 0;
     sub.shadeLaunches = sub.shadeBlocks = 0;
+    // (a render that failed half way may have left the dark stream busy: nothing of it may meet this render's clears)
+    HIPCHK(hipStreamSynchronize(sub.darkStream));
+    sub.darkPending = false; sub.darkTimed[0] = sub.darkTimed[1] = false;
+    sub.darkLaunches = 0;
     for (double &t : sub.t) t = 0;
     sub.result = DevCounters{};
     if (wd.totalWork == 0) return MI_OK;
@@ -4412,13 +4532,17 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
             HIPCHK(hipEventRecord(ev[4], st));
             HIPCHK(hipEventRecord(ev[5], st));
         } else {
+            const bool darkBeside = s.misAny && !pt->darkInLine;
             if ((rc = LaunchShade(pt, sub, grid)) != MI_OK) return rc;
             HIPCHK(hipEventRecord(ev[3], st));
+            if (darkBeside && !MIPT_DARK_AFTER_SHADOW && (rc = LaunchDarkBeside(pt, sub, grid.x)) != MI_OK) return rc;
             LaunchTraversal(pt, sub, 1, travGrid);
             LaunchResolve(pt, sub, 1, grid);
             HIPCHK(hipEventRecord(ev[4], st));
+            if (darkBeside && MIPT_DARK_AFTER_SHADOW && (rc = LaunchDarkBeside(pt, sub, grid.x)) != MI_OK) return rc;
             LaunchTraversal(pt, sub, 2, travGrid);
             LaunchResolve(pt, sub, 2, grid);
+            if (s.misAny && pt->darkInLine && (rc = LaunchDarkInLine(pt, sub, travGrid)) != MI_OK) return rc;
             HIPCHK(hipEventRecord(ev[5], st));
         }
         HIPCHK(hipGetLastError());   // a launch of this iteration that was refused (bad configuration) stops the render here
@@ -4426,7 +4550,10 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         set ^= 1;
         if (++sub.iterations > 100000000ull) { g_err = "render loop did not terminate"; return MI_ERR_HIP; }
     }
+    if ((rc = JoinDark(sub)) != MI_OK) return rc;   // the last iteration's dark rays are in the counters too
     HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(sub.darkStream));
+    HarvestDark(sub, 0); HarvestDark(sub, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(&sub.result, sub.ctr, sizeof(DevCounters), hipMemcpyDeviceToHost));
     return MI_OK;
@@ -4694,6 +4821,16 @@ int mi_pt_shade_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *blocks) {
     return MI_OK;
 }
 
+int mi_pt_dark_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *entries, uint64_t *rays, uint64_t *resolve_skipped) {
+    if (!pt || !launches || !entries || !rays || !resolve_skipped) { g_err = "null argument"; return MI_ERR_INVALID; }
+    *launches = 0; *entries = 0; *rays = 0; *resolve_skipped = 0;
+    for (const SubRenderer &sub : pt->subs) {
+        *launches += sub.darkLaunches;
+        for (const DevStats &r : sub.result.stats) { *entries += r.darkEntries; *rays += r.darkRays; *resolve_skipped += r.misDarkSeen; }
+    }
+    return MI_OK;
+}
+
 int mi_pt_shade_plan(const mi_scene_desc *d, int32_t *material_class, uint32_t material_capacity, int32_t *class_id,
                      int32_t *class_instance, int32_t *class_lobes, uint32_t *class_types, uint32_t class_capacity,
                      uint32_t *n_classes, uint32_t *hot) {
@@ -4808,6 +4945,7 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
         LaunchResolve(pt, sub, 1, grid);
         LaunchTraversal(pt, sub, 2, travGrid);
         LaunchResolve(pt, sub, 2, grid);
+        if (s.misAny && (rc = LaunchDarkInLine(pt, sub, travGrid)) != MI_OK) return rc;
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
         int fl = 0;
@@ -4920,6 +5058,9 @@ void mi_pt_destroy(mi_pt *pt) {
         FreePool(sub.pool);
         for (int a = 0; a < 2; ++a) for (int b = 0; b < N_EV; ++b) if (sub.evIter[a][b]) hipEventDestroy(sub.evIter[a][b]);
         if (sub.stream) hipStreamDestroy(sub.stream);
+        // (the hipDeviceSynchronize above has joined the dark stream, after a failed create or render as well)
+        for (hipEvent_t e : {sub.evDarkGo, sub.evDarkDone, sub.evDark[0][0], sub.evDark[0][1], sub.evDark[1][0], sub.evDark[1][1]}) if (e) hipEventDestroy(e);
+        if (sub.darkStream) hipStreamDestroy(sub.darkStream);
         if (sub.reads) hipHostFree(sub.reads);
     }
     delete pt;
