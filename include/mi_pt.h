@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define MI_NSPEC 31
-#define MI_ABI_VERSION 13
+#define MI_ABI_VERSION 14
 #define MI_MAX_BXDFS 8 /* BSDF::MaxBxDFs, src/core/reflection.h:196 */
 
 typedef enum mi_status {
@@ -55,7 +55,7 @@ typedef struct mi_bvh_node {
 
 /* One GeometricPrimitive (src/core/primitive.h:70-95) in BVH leaf order. */
 typedef struct mi_prim {
-    int32_t shape;      /* >=0: triangle index; <0: ~sphere index (ignored when `instance` is set) */
+    int32_t shape;      /* >=0: triangle index; <0: ~quadric index: [0, n_spheres) spheres, then n_disks disks (ignored when `instance` is set) */
     int32_t material;   /* index into materials, -1 = none (interface only) */
     int32_t area_light; /* index into lights, -1 = not emissive */
     int32_t instance;   /* 0: a GeometricPrimitive; k + 1: the TransformedPrimitive of mi_scene_desc.instances[k] (ABI v7) */
@@ -93,6 +93,18 @@ typedef struct mi_sphere {
     float radius, z_min, z_max, theta_min, theta_max, phi_max;
     int32_t reverse_orientation, swaps_handedness;
 } mi_sphere;
+
+/* Disk (src/shapes/disk.h, ABI v14): the second kind of quadric. Quadric index n_spheres + k is disks[k]. phi_max in radians
+ * (after Radians(Clamp(phimax, 0, 360))); w2o is the stored inverse. `kind` tells the quadrics that share this record's
+ * layout apart (0 = disk; the others are not built). */
+#define MI_QUADRIC_DISK 0
+typedef struct mi_disk {
+    float o2w[16], w2o[16];
+    float height, radius, inner_radius, phi_max;
+    int32_t reverse_orientation, swaps_handedness;
+    int32_t kind;
+    int32_t pad;
+} mi_disk;
 
 /* ---- materials: with constant textures (src/textures/constant.h:49-58) a
  * Material::ComputeScatteringFunctions result is a fixed BxDF list; image textures bind to lobes through mi_lobe_tex. */
@@ -248,7 +260,7 @@ typedef enum mi_light_type {
 
 typedef struct mi_light {
     int32_t type;
-    int32_t shape;     /* area: >=0 triangle index, <0 ~sphere index */
+    int32_t shape;     /* area: >=0 triangle index, <0 ~quadric index (see mi_prim.shape) */
     int32_t two_sided;
     float area;        /* Shape::Area() */
     float L[MI_NSPEC]; /* Lemit / I / L; infinite: Spectrum(Lmap->Lookup((.5,.5), .5), Illuminant), i.e. Power() / (pi r^2) */
@@ -455,6 +467,7 @@ typedef struct mi_scene_desc {
     const mi_prim_meta *prim_meta; /* ABI v11: [n_prims], may be NULL (then mi_pt_render_metadata refuses) */
     int32_t camera_type;           /* ABI v13: mi_camera_type of `camera` */
     const mi_lens *lens;           /* ABI v13: MI_CAMERA_REALISTIC: the lens system; NULL for a perspective camera */
+    uint32_t n_disks; const mi_disk *disks; /* ABI v14: quadric indices [n_spheres, n_spheres + n_disks) */
 } mi_scene_desc;
 
 /* Counters with the reference's STAT names (src/core/integrator.cpp:48,
@@ -601,6 +614,19 @@ int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, con
  * `tex` for n queries on the device. queries: 6 floats each (s, t, dsdx, dtdx, dsdy, dtdy) in texture space, i.e. after
  * the UVMapping2D; rgb: 3 floats per query. */
 int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *rgb);
+
+/* Parity tool for the quadrics (ABI v14): quadric `quadric` of the scene (the index space of mi_prim.shape: spheres, then
+ * disks) on its own, through the device functions the traversal, shading and light-sampling code call. Host pointers.
+ *   mode 0: Shape::Intersect. queries: 7 floats (o[3], d[3], tMax); out: MI_SHAPE_PROBE_HIT_FLOATS floats -- hit, t, p[3],
+ *           n[3], uv[2], dpdu[3], dpdv[3] (world space; all 0 on a miss). hit is 1 for a hit, 0 for a miss, and -1 when the
+ *           any-hit form of the test (Shape::IntersectP) disagrees with it.
+ *   mode 1: Shape::Sample(ref, u). queries: 5 floats (ref[3], u[2]); out: MI_SHAPE_PROBE_SAMPLE_FLOATS floats -- p[3], n[3], pdf
+ *           (solid angle).
+ *   mode 2: Shape::Pdf(ref, wi). queries: 6 floats (ref[3], wi[3]); out: 1 float.
+ * The reference point is a bare one as Shape::SolidAngle builds it (shape.cpp:90-91): no normal, no error bound. */
+#define MI_SHAPE_PROBE_HIT_FLOATS 16
+#define MI_SHAPE_PROBE_SAMPLE_FLOATS 7
+int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, const float *queries, float *out);
 
 /* Parity tool for the spatial light-selection strategy: the per-voxel Distribution1D tables mi_pt_create estimated on
  * the device (SpatialLightDistribution::ComputeDistribution, src/core/lightdistrib.cpp:232-300; the reference fills its

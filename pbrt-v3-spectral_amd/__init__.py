@@ -48,6 +48,12 @@ class Sphere(C.Structure):
                 ("reverse_orientation", C.c_int32), ("swaps_handedness", C.c_int32)]
 
 
+class Disk(C.Structure):
+    _fields_ = [("o2w", C.c_float * 16), ("w2o", C.c_float * 16), ("height", C.c_float), ("radius", C.c_float),
+                ("inner_radius", C.c_float), ("phi_max", C.c_float), ("reverse_orientation", C.c_int32),
+                ("swaps_handedness", C.c_int32), ("kind", C.c_int32), ("pad", C.c_int32)]
+
+
 class Bxdf(C.Structure):
     _fields_ = [("type", C.c_int32), ("flags", C.c_int32), ("fresnel", C.c_int32), ("scaled", C.c_int32),
                 ("p", C.c_float * 8), ("R", C.c_float * NSPEC), ("S", C.c_float * NSPEC),
@@ -161,7 +167,8 @@ class SceneDesc(C.Structure):
                 ("n_mipmaps", C.c_uint32), ("mipmaps", C.POINTER(MipMap)),
                 ("n_instances", C.c_uint32), ("instances", C.POINTER(Instance)),
                 ("prim_meta", C.POINTER(PrimMeta)),
-                ("camera_type", C.c_int32), ("lens", C.POINTER(Lens))]
+                ("camera_type", C.c_int32), ("lens", C.POINTER(Lens)),
+                ("n_disks", C.c_uint32), ("disks", C.POINTER(Disk))]
 
 
 class Counters(C.Structure):
@@ -188,7 +195,8 @@ class SceneOverrides(C.Structure):
 
 class SceneStats(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_triangles", "n_spheres", "n_meshes", "interior_nodes", "leaf_nodes",
-                                          "n_lights", "n_materials", "n_warnings", "n_errors", "accel_on_device")]
+                                          "n_lights", "n_materials", "n_warnings", "n_errors", "accel_on_device",
+                                          "n_disks")]
 
 
 INTEGRATOR_PATH, INTEGRATOR_METADATA = 0, 1
@@ -275,6 +283,7 @@ def hip_lib():
         lib.mi_pt_math_probe.argtypes = [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_trace_wavefront.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_texture_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.mi_pt_shape_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_light_distribution.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]
         lib.mi_pt_debug_path.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         lib.mi_pt_shade_instances.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -590,6 +599,18 @@ class PathIntegrator:
         if rc != 0:
             raise RuntimeError("mi_pt_texture_lookup failed: %s" % hip_lib().mi_pt_last_error().decode())
         return out
+
+    def shape_probe(self, quadric, mode, queries):
+        """One quadric of the scene on its own (mi_pt_shape_probe; index space of mi_prim.shape: spheres, then disks).
+        mode 0: queries [n, 7] rays (o, d, tMax) -> [n, 16] hit, t, p, n, uv, dpdu, dpdv; mode 1: [n, 5] (ref, u) -> [n, 7]
+        p, n, pdf of Shape::Sample(ref, u); mode 2: [n, 6] (ref, wi) -> [n] Shape::Pdf(ref, wi)."""
+        n_in, n_out = {0: (7, 16), 1: (5, 7), 2: (6, 1)}[int(mode)]
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, n_in)
+        out = np.zeros((q.shape[0], n_out), np.float32)
+        rc = hip_lib().mi_pt_shape_probe(self._h, int(quadric), int(mode), q.shape[0], _fptr(q), _fptr(out))
+        if rc != 0:
+            raise RuntimeError("mi_pt_shape_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
+        return out[:, 0] if n_out == 1 else out
 
 
 def math_probe(op, x, y=None, device=0):

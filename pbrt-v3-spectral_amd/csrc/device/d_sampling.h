@@ -5,7 +5,7 @@
 //   Shape::Sample(ref) / Pdf(ref,wi)    src/core/shape.cpp:56-87 (+ sphere.cpp:232-306)
 //   Distribution1D / SpatialLightDistribution  src/core/sampling.h:55-109, src/core/lightdistrib.cpp:135-300
 #pragma once
-#include "d_bsdf.h"
+#include "d_disk.h"
 
 namespace dpt {
 
@@ -296,8 +296,14 @@ DEV float LightY(const DScene &s, const mi_light &l) {
     return YScale(yy);
 }
 
+// DISKS: the caller can meet a disk. The k_shade instances compiled for a subset of the lobes, lights or samplers cannot: a scene
+// with disks is shaded by the general instances alone (TM_HOLDS_DISKS, d_bsdf.h; ShadeInstanceOf), so the others hold no disk code.
+template <bool DISKS = true>
 DEV Interaction ShapeSample(const DScene &s, int shape, const Interaction &ref, float u0, float u1, float *pdf) {
-    if (shape < 0) return SphereSample(s.spheres[~shape], ref, u0, u1, pdf);
+    if (shape < 0) {
+        if (DISKS && IsDisk(s, ~shape)) return DiskSample(s.disks[~shape - s.nSpheres], ref, u0, u1, pdf);
+        return SphereSample(s.spheres[~shape], ref, u0, u1, pdf);
+    }
     Interaction intr = TriSample(s, shape, u0, u1, pdf);
     V3 wi = intr.p - ref.p;
     if (wi.LengthSquared() == 0) *pdf = 0;
@@ -310,9 +316,11 @@ DEV Interaction ShapeSample(const DScene &s, int shape, const Interaction &ref, 
 }
 
 // Shape::Pdf(ref, wi) for the light's own shape (no BVH: it intersects only that shape).
+template <bool DISKS = true>
 DEV float ShapePdf(const DScene &s, int shape, float area, const Interaction &ref, const V3 &wi, float *tTri = nullptr) {
     Ray ray = SpawnRay(ref, wi);
     if (shape < 0) {
+        if (DISKS && IsDisk(s, ~shape)) return DiskPdf(s.disks[~shape - s.nSpheres], area, ref, wi, tTri);   // (Shape::Pdf intersects it: *tTri as for a triangle)
         const mi_sphere &sp = s.spheres[~shape];
         V3 pCenter = XfPoint(sp.o2w, V3(0, 0, 0));
         V3 pOrigin = OffsetRayOrigin(ref.p, ref.pError, ref.n, pCenter - ref.p);
@@ -426,7 +434,7 @@ DEV LightSample SampleLi(const DScene &s, const mi_light &l, const Interaction &
     ls.pdf = 0; ls.black = true; ls.liScale = 1; ls.liMul = 1; ls.divide = false; ls.isEnv = false;
     ls.env.i1 = ls.env.i2 = 0; ls.env.w0 = ls.env.w1 = ls.env.w2 = 0;
     if (l.type == MI_LIGHT_DIFFUSE_AREA) {
-        Interaction pShape = ShapeSample(s, l.shape, ref, u0, u1, &ls.pdf);
+        Interaction pShape = ShapeSample<TM_HOLDS_DISKS(TM)>(s, l.shape, ref, u0, u1, &ls.pdf);
         if (ls.pdf == 0 || (pShape.p - ref.p).LengthSquared() == 0) { ls.pdf = 0; return ls; }
         ls.wi = Normalize(pShape.p - ref.p);
         ls.pLight = pShape;

@@ -20,7 +20,7 @@
 
 namespace dpt {
 
-#define PRIM_FLAG_SPHERE 1u
+#define PRIM_FLAG_SPHERE 1u   // a quadric: a sphere or a disk, told apart by its index (primTri[3 * prim + 1].w against DScene::nSpheres)
 #define PRIM_FLAG_DEGENERATE 2u
 #define PRIM_FLAG_INSTANCE 64u   // a TransformedPrimitive: primTri[3 * prim + 1].w holds the instance number (mi_prim.instance - 1)
 #define PRIM_FLAG_ALPHA 32u   // the triangle's mesh has an "alpha" / "shadowalpha" mask (mi_mesh.alpha_tex)
@@ -44,6 +44,8 @@ struct DScene {
     const float *P, *N, *UV;
     const mi_mesh *meshes;
     const mi_sphere *spheres;
+    const mi_disk *disks;        // quadric index q: spheres[q] for q < nSpheres, else disks[q - nSpheres] (d_disk.h)
+    int nSpheres;
     const mi_material *materials;
     const mi_light *lights;
     const int *lightPrim;        // [nLights]: the primitive whose shape an area light is (k_trav<3> leaves it out)

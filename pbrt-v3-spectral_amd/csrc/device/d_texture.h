@@ -287,6 +287,17 @@ DEV bool SphereTexCoords(const mi_sphere &sp, const V3 &ro, const V3 &rd, float 
     ts->flip = (sp.reverse_orientation != 0) ^ (sp.swaps_handedness != 0);
     return true;
 }
+// The same for a disk (disk.cpp:73-81): dndu = dndv = 0
+DEV bool DiskTexCoords(const mi_disk &k, const V3 &ro, const V3 &rd, float *u, float *v, TriShading *ts) {
+    SurfaceInteraction si;
+    float t, uv[2];
+    if (!DiskInteraction(k, ro, rd, kInfinity, &si, &t, uv, &ts->dpdv)) return false;
+    *u = uv[0]; *v = uv[1];
+    ts->shDpdv = ts->dpdv;
+    ts->dndu = ts->dndv = V3(0, 0, 0);
+    ts->flip = (k.reverse_orientation != 0) ^ (k.swaps_handedness != 0);
+    return true;
+}
 
 // Texture<Float>::Evaluate(si) of float image texture `tex`
 DEV float EvalFloatImageTexture(const DScene &s, int tex, float u, float v, const TexDifferentials &td) {

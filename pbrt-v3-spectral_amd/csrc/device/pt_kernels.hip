@@ -637,7 +637,7 @@ DEV bool TraverseTree(const DScene &s, int rootRecord, bool rootHit, const V3 &r
             if (pf & PRIM_FLAG_SPHERE) {   // tested where it is met, against the tMax of that moment (the reference's order)
                 const int sph = __float_as_int(primTri[3 * prim + 1].w);
                 float t;
-                if (SphereHitT(s.spheres[sph], ro, rd, tMax, &t)) {
+                if (QuadricHitT(s, sph, ro, rd, tMax, &t)) {
                     if (ANY) return true;
                     tMax = t;
                     hit->prim = prim; hit->t = t; hit->b0 = hit->b1 = hit->b2 = 0; hit->inst = inst;
@@ -678,6 +678,7 @@ DEV bool Traverse(const DScene &s, const V3 &ro, const V3 &rd, float tMax, Hit *
     return TraverseW<ANY, 2, false>(s, ro, rd, tMax, hit, nodeCount, triCount);
 }
 
+template <bool DISKS = true>
 DEV void HitInteraction(const DScene &s, int prim, const V3 &ro, const V3 &rd, float b0, float b1, float b2, SurfaceInteraction *si);
 
 // ------------------------------------------------------------------ persistent traversal
@@ -996,7 +997,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                 } else if (INST && curInst >= 0 && (pf & PRIM_FLAG_SPHERE)) {
                     // a quadric of an instanced object: tested where it is met, with the instance's ray
                     float t;
-                    if (SphereHitT(s.spheres[__float_as_int(primTri[3 * prim + 1].w)], V3(r.ox, r.oy, r.oz), V3(r.dx, r.dy, r.dz), tMax, &t)) {
+                    if (QuadricHitT(s, __float_as_int(primTri[3 * prim + 1].w), V3(r.ox, r.oy, r.oz), V3(r.dx, r.dy, r.dz), tMax, &t)) {
                         if (ANY) { hitPrim = prim; finished = true; }
                         else { tMax = t; hitPrim = prim; hitT = t; hitB0 = hitB1 = hitB2 = 0; hitInst = curInst; hitInCur = true; }
                     }
@@ -1129,7 +1130,7 @@ DEV bool ResolveQuadrics(const DScene &s, const Pool &pool, uint32_t slot, const
         for (int j = 0; j < (np & 0xff); ++j) {
             const int prim = pool.I(I_PEND0 + j, slot);
             float t;
-            if (SphereHitT(s.spheres[__float_as_int(s.primTri[3 * prim + 1].w)], ro, rd, tMaxIn, &t)) return true;
+            if (QuadricHitT(s, __float_as_int(s.primTri[3 * prim + 1].w), ro, rd, tMaxIn, &t)) return true;
         }
         return foundTri;
     }
@@ -1139,7 +1140,7 @@ DEV bool ResolveQuadrics(const DScene &s, const Pool &pool, uint32_t slot, const
         const int prim = pool.I(I_PEND0 + j, slot);
         const float tEnc = pool.F(P_TENC0 + j, slot);
         float t;
-        if (SphereHitT(s.spheres[__float_as_int(s.primTri[3 * prim + 1].w)], ro, rd, minf(tEnc, tBest), &t)) { tBest = t; primBest = prim; tEncBest = tEnc; }
+        if (QuadricHitT(s, __float_as_int(s.primTri[3 * prim + 1].w), ro, rd, minf(tEnc, tBest), &t)) { tBest = t; primBest = prim; tEncBest = tEnc; }
     }
     if (primBest < 0) return foundTri;
     if (foundTri && tEncBest > h->t && h->t <= tBest) return true;   // the triangle was found later, and in front of the quadric
@@ -1427,7 +1428,12 @@ DEV void ResolveMisVisibility(const DScene &s, const Pool &pool, DevCounters *ct
         else {                              // nothing up to the end of the span: the light's shape, if the ray meets it, is the closest hit
             const float4 r0 = pool.R(R_MI0, slot), r1 = pool.R(R_MI1, slot);
             const V3 ro = PackedRayO(r0), rd = PackedRayD(r0, r1);
-            if (l.shape < 0) {
+            if (l.shape < 0 && IsDisk(s, ~l.shape)) {   // a disk: the triangle's way (k_shade: Shape::Pdf has intersected it, else there is no ray)
+                SurfaceInteraction li;
+                float t;
+                if (l.two_sided != 0) add = true;
+                else if (DiskInteraction(s.disks[~l.shape - s.nSpheres], ro, rd, kInfinity, &li, &t)) add = Dot(li.n, -rd) > 0;
+            } else if (l.shape < 0) {
                 const mi_sphere &sp = s.spheres[~l.shape];
                 SurfaceInteraction li;
                 float t, t2;
@@ -1981,10 +1987,12 @@ DEV void ShadingToWorld(const mi_instance &in, TriShading *ts) {
 }
 
 // Build the SurfaceInteraction of a recorded hit.
+// (DISKS: see ShapeSample, d_sampling.h)
+template <bool DISKS>
 DEV void HitInteraction(const DScene &s, int prim, const V3 &ro, const V3 &rd, float b0, float b1, float b2, SurfaceInteraction *si) {
     const mi_prim p = s.prims[prim];
     if (p.shape >= 0) TriInteraction(s, p.shape, b0, b1, b2, rd, si);
-    else { float t; SphereInteraction(s.spheres[~p.shape], ro, rd, kInfinity, si, &t); }
+    else { float t; QuadricInteraction<DISKS>(s, ~p.shape, ro, rd, kInfinity, si, &t); }
 }
 
 // (the shading kernel's dimensions start after the camera sample's, so dim >= 5 here)
@@ -2066,6 +2074,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
     }
     const uint32_t qi = blk * BLOCK + threadIdx.x;
     constexpr bool HALTON_ONLY = (TM & TM_SAMPLERS) == 0;
+    constexpr bool DISKS = TM_HOLDS_DISKS(TM);   // (a scene with disks is shaded by the general instances alone: ShadeInstanceOf)
     constexpr bool SIMPLE_SPECTRA = NL <= 2 && TM_SIMPLE_KINDS(TM);   // the straight-line spectral passes (d_bsdf.h, SimpleLobes)
     // more than two lobes: f is summed lobe by lobe into the lane's column of the spectrum tile (AccumulateF, d_bsdf.h)
     constexpr bool ACCUM = NL > 2 || (TM & TM_TEXTURED) != 0;   // (image-textured lobes too: their spectra quad by quad, TexturedQuad)
@@ -2106,7 +2115,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             if (needIsect) inst = pool.I(I_HITINST, slot);
             if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
         }
-        if (needIsect) { const float4 hr = pool.R(R_HIT, slot); HitInteraction(s, prim, roS, rdS, hr.y, hr.z, hr.w, &isect); }
+        if (needIsect) { const float4 hr = pool.R(R_HIT, slot); HitInteraction<DISKS>(s, prim, roS, rdS, hr.y, hr.z, hr.w, &isect); }
         SurfaceInteraction isectObj;
         if constexpr ((TM & TM_INSTANCES) != 0) {
             if (inst >= 0) { isectObj = isect; InteractionToWorld(s.instances[inst], &isect); }
@@ -2187,7 +2196,9 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                         const float4 hr = pool.R(R_HIT, slot);
                         TriTexCoords(s, shape, hr.y, hr.z, hr.w, inst >= 0 ? isectObj : isect, &u, &v, &tsh);
                         haveUV = true;
-                    } else
+                    } else if (DISKS && IsDisk(s, ~shape))
+                        haveUV = DiskTexCoords(s.disks[~shape - s.nSpheres], roS, rdS, &u, &v, &tsh);
+                    else
                         haveUV = SphereTexCoords(s.spheres[~shape], roS, rdS, &u, &v, &tsh);
                     if constexpr ((TM & TM_INSTANCES) != 0) {
                         if (inst >= 0) ShadingToWorld(s.instances[inst], &tsh);
@@ -2447,7 +2458,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                 float tShape = -1.f;   // a triangle light: where wi meets it
                                 if (!(sampledType & MI_BSDF_SPECULAR)) {
                                     const float lp = (TM_LIGHT(TM, MI_LIGHT_INFINITE) && light.type == MI_LIGHT_INFINITE) ? InfinitePdfLi(s, light, wi)
-                                                                                       : ShapePdf(s, light.shape, light.area, isect, wi, &tShape);
+                                                                                       : ShapePdf<DISKS>(s, light.shape, light.area, isect, wi, &tShape);
                                     if (lp == 0) go = false;
                                     else { float pf = 1 * sPdf, pg = 1 * lp; weight = (pf * pf) / (pf * pf + pg * pg); }
                                 }
@@ -2939,6 +2950,49 @@ __global__ void k_texture_lookup(DScene s, int tex, const float *q, uint32_t n, 
     out[3 * i] = v.r; out[3 * i + 1] = v.g; out[3 * i + 2] = v.b;
 }
 
+// ------------------------------------------------------------------ one quadric on its own (mi_pt_shape_probe)
+__global__ void k_shape_probe(DScene s, int q, int mode, const float *in, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool disk = IsDisk(s, q);
+    if (mode == 0) {
+        const float *r = in + 7 * (size_t)i;
+        float *o = out + MI_SHAPE_PROBE_HIT_FLOATS * (size_t)i;
+        for (int k = 0; k < MI_SHAPE_PROBE_HIT_FLOATS; ++k) o[k] = 0.f;
+        const V3 ro(r[0], r[1], r[2]), rd(r[3], r[4], r[5]);
+        float tT = 0.f, t = 0.f;
+        const bool hitT = QuadricHitT(s, q, ro, rd, r[6], &tT);   // (the any-hit form and the full one must agree)
+        SurfaceInteraction si;
+        if (!QuadricInteraction(s, q, ro, rd, r[6], &si, &t)) { o[0] = hitT ? -1.f : 0.f; return; }
+        float u = 0.f, v = 0.f;
+        TriShading ts;
+        if (disk) DiskTexCoords(s.disks[q - s.nSpheres], ro, rd, &u, &v, &ts);
+        else SphereTexCoords(s.spheres[q], ro, rd, &u, &v, &ts);
+        o[0] = (hitT && tT == t) ? 1.f : -1.f;
+        o[1] = t;
+        o[2] = si.p.x; o[3] = si.p.y; o[4] = si.p.z;
+        o[5] = si.n.x; o[6] = si.n.y; o[7] = si.n.z;
+        o[8] = u; o[9] = v;
+        o[10] = si.dpdu.x; o[11] = si.dpdu.y; o[12] = si.dpdu.z;
+        o[13] = ts.dpdv.x; o[14] = ts.dpdv.y; o[15] = ts.dpdv.z;
+        return;
+    }
+    // the reference point as Shape::SolidAngle makes it (shape.cpp:90-91): no normal, no error bound
+    const float *r = in + (mode == 1 ? 5 : 6) * (size_t)i;
+    Interaction ref;
+    ref.p = V3(r[0], r[1], r[2]);
+    ref.pError = V3(0, 0, 0); ref.n = V3(0, 0, 0); ref.wo = V3(0, 0, 1);
+    if (mode == 1) {
+        float *o = out + MI_SHAPE_PROBE_SAMPLE_FLOATS * (size_t)i;
+        float pdf = 0.f;
+        const Interaction it = ShapeSample(s, ~q, ref, r[3], r[4], &pdf);
+        o[0] = it.p.x; o[1] = it.p.y; o[2] = it.p.z; o[3] = it.n.x; o[4] = it.n.y; o[5] = it.n.z; o[6] = pdf;
+    } else {
+        const float area = disk ? DiskArea(s.disks[q - s.nSpheres]) : SphereArea(s.spheres[q]);
+        out[i] = ShapePdf(s, ~q, area, ref, V3(r[3], r[4], r[5]));
+    }
+}
+
 // ------------------------------------------------------------------ scalar helpers on their own (mi_pt_math_probe)
 __global__ void k_math_probe(int op, uint32_t n, const float *x, const float *y, float *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3269,13 +3323,15 @@ constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstanc
 // `types` and its longest lobe list `lobes` (the overflow class counts MI_MAX_BXDFS lobes; the miss class has neither
 // types nor lobes, so it takes the matte instance). `hot`: the lights and sampler bits of the scene's variant of the matte
 // and plastic instances.
-static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot) {
+// `disks`: the scene has disks, whose code only the instances compiled for every lobe, light and sampler hold (TM_HOLDS_DISKS):
+// no class of such a scene fits an instance compiled for a subset, so those are the code they were before disks.
+static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot, bool disks) {
     auto pick = [](int nl, unsigned tm) {
         for (int i = 0; i < N_SHADE_INSTANCES; ++i)
             if (kShadeInstances[i].nl == nl && kShadeInstances[i].tm == tm) return i;
         return -1;
     };
-    auto fits = [types](unsigned tm) { return (types & ~tm) == 0; };
+    auto fits = [types, disks](unsigned tm) { return !disks && (types & ~tm) == 0; };
     // (textured "disney" classes go to the eight-lobe instance whatever their lobe count: only that one reads the rules
     // that form their spectra from the colour -- LobeTexT::rules, d_bsdf.h)
     const unsigned disneyBits = (1u << MI_BXDF_DISNEY_DIFFUSE) | (1u << MI_BXDF_DISNEY_FAKE_SS) | (1u << MI_BXDF_DISNEY_RETRO) |
@@ -3315,7 +3371,8 @@ struct mi_pt {
     std::vector<int> textureTypes;
     bool hasAlphaMasks = false;      // picks the traversal kernels compiled with the alpha-mask test
     bool hasInstances = false;       // ... and with the TransformedPrimitive code (those carry the alpha-mask test too)
-    bool hasQuadrics = false;        // the scene has spheres: the quadric lists of rays can overflow (k_resolve_overflow is launched)
+    uint32_t nQuadrics = 0;          // n_spheres + n_disks (mi_pt_shape_probe)
+    bool hasQuadrics = false;        // the scene has spheres or disks: the quadric lists of rays can overflow (k_resolve_overflow is launched)
     bool hasInfiniteLight = false;   // picks the kernels compiled with the environment-light code
     unsigned shadeClasses[N_SHADE_INSTANCES] = {0};   // per k_shade instance: the shading classes it runs (ShadeInstanceOf)
     int numCUs = 256;
@@ -3454,9 +3511,12 @@ int CheckSceneDesc(const mi_scene_desc *d) {
             if (d->instances[p.instance - 1].root >= d->n_nodes) { g_err = "instance BVH root out of range"; return MI_ERR_INVALID; }
             continue;
         }
-        if (p.shape >= 0 ? (uint32_t)p.shape >= d->n_tris : (uint32_t)(~p.shape) >= d->n_spheres) { g_err = "primitive shape index out of range"; return MI_ERR_INVALID; }
+        if (p.shape >= 0 ? (uint32_t)p.shape >= d->n_tris : (uint64_t)(uint32_t)(~p.shape) >= (uint64_t)d->n_spheres + d->n_disks) { g_err = "primitive shape index out of range"; return MI_ERR_INVALID; }
         if (p.material >= (int)d->n_materials || p.area_light >= (int)d->n_lights) { g_err = "primitive material/light index out of range"; return MI_ERR_INVALID; }
     }
+    if ((d->n_spheres && !d->spheres) || (d->n_disks && !d->disks) || (uint64_t)d->n_spheres + d->n_disks > 0x7fffffffull) { g_err = "quadric arrays missing or too large"; return MI_ERR_INVALID; }
+    for (uint32_t i = 0; i < d->n_disks; ++i)
+        if (d->disks[i].kind != MI_QUADRIC_DISK) { g_err = "mi_disk.kind: only disks (0) are built"; return MI_ERR_UNSUPPORTED; }
     for (uint32_t i = 0; i < d->n_tris * 3; ++i)
         if (d->tri_indices[i] < 0 || (uint32_t)d->tri_indices[i] >= d->n_verts) { g_err = "triangle vertex index out of range"; return MI_ERR_INVALID; }
     for (uint32_t i = 0; i < d->n_tris; ++i)
@@ -3504,7 +3564,7 @@ int CheckSceneDesc(const mi_scene_desc *d) {
     int nInfinite = 0;
     for (uint32_t i = 0; i < d->n_lights; ++i) {
         const mi_light &l = d->lights[i];
-        if (l.type == MI_LIGHT_DIFFUSE_AREA && (l.shape >= 0 ? (uint32_t)l.shape >= d->n_tris : (uint32_t)(~l.shape) >= d->n_spheres)) { g_err = "area light shape index out of range"; return MI_ERR_INVALID; }
+        if (l.type == MI_LIGHT_DIFFUSE_AREA && (l.shape >= 0 ? (uint32_t)l.shape >= d->n_tris : (uint64_t)(uint32_t)(~l.shape) >= (uint64_t)d->n_spheres + d->n_disks)) { g_err = "area light shape index out of range"; return MI_ERR_INVALID; }
         if (l.type != MI_LIGHT_INFINITE) continue;
         if ((uint32_t)l.envmap >= d->n_envmaps) { g_err = "infinite light without environment map"; return MI_ERR_INVALID; }
         if (++nInfinite > 4) { g_err = "more than 4 infinite lights"; return MI_ERR_INVALID; }
@@ -3787,7 +3847,7 @@ int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, Sh
     }
     for (int c = 0; c < MAX_CLASSES; ++c) {
         if (!((sc.classMask >> c) & 1u)) continue;
-        const int i = ShadeInstanceOf(classTypes[c], classLobes[c], instanced, hot);
+        const int i = ShadeInstanceOf(classTypes[c], classLobes[c], instanced, hot, d->n_disks > 0);
         if (i < 0) { g_err = "no k_shade instance for shading class " + std::to_string(c); return MI_ERR_UNSUPPORTED; }
         sc.classInstance[c] = i;
         sc.shadeClasses[i] |= 1u << c;
@@ -3892,6 +3952,15 @@ std::vector<float4> BuildLightBounds(const mi_scene_desc *d) {
             for (int c = 0; c < 8; ++c) {
                 const float x = (c & 1) ? sp.radius : -sp.radius, y = (c & 2) ? sp.radius : -sp.radius, z = (c & 4) ? sp.z_max : sp.z_min;
                 const float *m = sp.o2w;
+                const float w = m[12] * x + m[13] * y + m[14] * z + m[15];
+                add((m[0] * x + m[1] * y + m[2] * z + m[3]) / w, (m[4] * x + m[5] * y + m[6] * z + m[7]) / w, (m[8] * x + m[9] * y + m[10] * z + m[11]) / w);
+            }
+            have = true;
+        } else if (l.type == MI_LIGHT_DIFFUSE_AREA && l.shape < 0 && (uint64_t)(uint32_t)(~l.shape) < (uint64_t)d->n_spheres + d->n_disks) {
+            const mi_disk &k = d->disks[(uint32_t)(~l.shape) - d->n_spheres];   // Disk::ObjectBound (disk.cpp:43-46) through ObjectToWorld
+            for (int c = 0; c < 4; ++c) {
+                const float x = (c & 1) ? k.radius : -k.radius, y = (c & 2) ? k.radius : -k.radius, z = k.height;
+                const float *m = k.o2w;
                 const float w = m[12] * x + m[13] * y + m[14] * z + m[15];
                 add((m[0] * x + m[1] * y + m[2] * z + m[3]) / w, (m[4] * x + m[5] * y + m[6] * z + m[7]) / w, (m[8] * x + m[9] * y + m[10] * z + m[11]) / w);
             }
@@ -4052,6 +4121,7 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     pt->hasAlphaMasks = h.hasAlphaMasks;
     pt->hasInstances = d->n_instances > 0;
     pt->hasQuadrics = h.hasQuadrics;
+    pt->nQuadrics = d->n_spheres + d->n_disks;
     pt->hasInfiniteLight = h.classes.hasInfiniteLight;
     memcpy(pt->shadeClasses, h.classes.shadeClasses, sizeof(pt->shadeClasses));
     pt->nTextures = d->n_textures;
@@ -4081,6 +4151,8 @@ int UploadScene(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     up(d->UV, (size_t)d->n_verts * 2, s.UV);
     up(d->meshes, d->n_meshes, s.meshes);
     up(d->spheres, d->n_spheres, s.spheres);
+    up(d->disks, d->n_disks, s.disks);
+    s.nSpheres = (int)d->n_spheres;
     up(d->materials, d->n_materials, s.materials);
     up(d->lights, d->n_lights, s.lights);
     up(&d->camera, 1, s.cameraMotion);
@@ -4714,6 +4786,26 @@ int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *querie
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(rgb, dout.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (quadric < 0 || (uint32_t)quadric >= pt->nQuadrics) { g_err = "mi_pt_shape_probe: quadric index out of range"; return MI_ERR_INVALID; }
+    if (mode < 0 || mode > 2) { g_err = "mi_pt_shape_probe: mode must be 0, 1 or 2"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_shape_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const size_t nIn = mode == 0 ? 7 : (mode == 1 ? 5 : 6);
+    const size_t nOut = mode == 0 ? MI_SHAPE_PROBE_HIT_FLOATS : (mode == 1 ? MI_SHAPE_PROBE_SAMPLE_FLOATS : 1);
+    HIPCHK(hipSetDevice(pt->device));
+    DevBuf dq, dout;
+    HIPCHK(dq.alloc((size_t)n * nIn * sizeof(float)));
+    HIPCHK(dout.alloc((size_t)n * nOut * sizeof(float)));
+    HIPCHK(hipMemcpy(dq.p, queries, (size_t)n * nIn * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_shape_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, (int)quadric, (int)mode, dq.as<float>(), n, dout.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * nOut * sizeof(float), hipMemcpyDeviceToHost));
     return MI_OK;
 }
 

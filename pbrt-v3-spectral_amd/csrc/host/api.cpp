@@ -12,7 +12,7 @@
 //   WorldEnd -> camera, film, sampler src/core/api.cpp:1617-1737,1750-1860
 // Out of scope here (reported as errors, never silently ignored): object
 // instancing, animated transforms, participating media, non-constant textures,
-// shapes other than trianglemesh / loopsubdiv / sphere.
+// shapes other than trianglemesh / plymesh / loopsubdiv / sphere / disk.
 #include <cctype>
 #include <chrono>
 #include <cstdio>
@@ -120,8 +120,9 @@ struct GraphicsState {
     bool reverseOrientation = false;
 };
 
+constexpr int kDiskBase = 1 << 30;
 struct PendingPrim {
-    int shape;  // >=0 tri, <0 ~sphere
+    int shape;  // >=0 tri, <0 ~sphere; a disk: ~(kDiskBase + its number) until WorldEnd knows how many spheres precede the disks
     int material;
     int light;
     Bounds3 bounds;
@@ -397,7 +398,7 @@ struct Api {
             // (after MakeShapes has made something, api.cpp:1370-1378: judged here by the shape's name, the shapes this front end
             // builds; a shape whose parameters turn out unusable at the ObjectInstance has taken its number all the same)
             uint32_t id = gs.currentMaterial->id;
-            const bool built = name == "trianglemesh" || name == "plymesh" || name == "loopsubdiv" || name == "sphere";
+            const bool built = name == "trianglemesh" || name == "plymesh" || name == "loopsubdiv" || name == "sphere" || name == "disk";
             if (built && ShapeMaySetMaterialParameters(params)) id = TakeMaterialIds(gs.currentMaterial->name, params, gs.currentMaterial->params);
             RecordedShape r{name, params, ctm, gs, id};
             r.gs.areaLight = "";
@@ -405,7 +406,7 @@ struct Api {
             return;
         }
         int firstTri = -1, nTris = 0;
-        int sphereIdx = -1;
+        int sphereIdx = -1, diskIdx = -1;
         if (name == "trianglemesh") {  // CreateTriangleMeshShape, triangle.cpp:642-740
             const std::vector<int> *vi = ParamSet::Find(params.ints, "indices");
             const std::vector<Vec3> *P = ParamSet::Find(params.point3s, "P");
@@ -487,6 +488,21 @@ struct Api {
             sphereIdx = (int)scene->spheres.size();
             scene->spheres.push_back(s);
             scene->stats.nSpheres++;
+        } else if (name == "disk") {  // CreateDiskShape, disk.cpp:140-150; Disk ctor disk.h:49-58 ("alpha" / "shadowalpha" are not read there)
+            mi_disk k{};
+            Transform w2o = Inverse(ctm);
+            std::memcpy(k.o2w, ctm.m.m, sizeof(k.o2w));
+            std::memcpy(k.w2o, w2o.m.m, sizeof(k.w2o));
+            k.height = params.FindOneFloat("height", 0.f);
+            k.radius = params.FindOneFloat("radius", 1.f);
+            k.inner_radius = params.FindOneFloat("innerradius", 0.f);
+            k.phi_max = Radians(Clamp(params.FindOneFloat("phimax", 360.f), 0, 360));
+            k.reverse_orientation = gs.reverseOrientation ? 1 : 0;
+            k.swaps_handedness = ctm.SwapsHandedness() ? 1 : 0;
+            k.kind = MI_QUADRIC_DISK;
+            diskIdx = (int)scene->disks.size();
+            scene->disks.push_back(k);
+            scene->stats.nDisks++;
         } else {
             Err("Shape \"" + name + "\" is outside the PathIntegrator hot-path scope (SURVEY 2 rows 13-14); skipped.");
             return;
@@ -513,6 +529,21 @@ struct Api {
                 if (ctm.HasScale()) Warn("Scaling detected in world to light transformation!");
             }
             Bounds3 ob(Vec3(-s.radius, -s.radius, s.z_min), Vec3(s.radius, s.radius, s.z_max));
+            pp.bounds = ctm.Bounds(ob);  // Shape::WorldBound, shape.cpp:54
+            pending.push_back(pp);
+        } else if (diskIdx >= 0) {
+            const mi_disk &k = scene->disks[diskIdx];
+            PendingPrim pp;
+            pp.shape = ~(kDiskBase + diskIdx);
+            pp.material = material;
+            pp.materialId = materialId; pp.instanceId = expandingInstance;
+            pp.light = -1;
+            if (gs.areaLight != "") {
+                float area = k.phi_max * 0.5 * (k.radius * k.radius - k.inner_radius * k.inner_radius);  // Disk::Area, disk.cpp:125-127
+                pp.light = MakeAreaLight(pp.shape, area);
+                if (ctm.HasScale()) Warn("Scaling detected in world to light transformation!");
+            }
+            Bounds3 ob(Vec3(-k.radius, -k.radius, k.height), Vec3(k.radius, k.radius, k.height));  // Disk::ObjectBound, disk.cpp:43-46
             pp.bounds = ctm.Bounds(ob);  // Shape::WorldBound, shape.cpp:54
             pending.push_back(pp);
         } else
@@ -1129,6 +1160,12 @@ void Api::WorldEnd() {
             scene->hlbvhOnDevice = false;
             scene->stats.interiorNodes = scene->stats.leafNodes = 0;
         }
+        // the quadrics share one index space, spheres first: a disk's number is known now that every sphere has been seen
+        const int nSph = (int)scene->spheres.size();
+        for (mi_prim &p : scene->prims)
+            if (p.shape < 0 && ~p.shape >= kDiskBase) p.shape = ~(~p.shape - kDiskBase + nSph);
+        for (mi_light &l : scene->lights)
+            if (l.type == MI_LIGHT_DIFFUSE_AREA && l.shape < 0 && ~l.shape >= kDiskBase) l.shape = ~(~l.shape - kDiskBase + nSph);
         for (const InstanceRec &ir : instanceRecs) {
             if (!accelOk) break;
             mi_instance mi{};
@@ -1683,6 +1720,7 @@ void HostScene::Finalize() {
     d.n_verts = (uint32_t)(P.size() / 3); d.P = P.data(); d.N = N.data(); d.UV = UV.data();
     d.n_meshes = (uint32_t)meshes.size(); d.meshes = meshes.data();
     d.n_spheres = (uint32_t)spheres.size(); d.spheres = spheres.data();
+    d.n_disks = (uint32_t)disks.size(); d.disks = disks.data();
     d.n_materials = (uint32_t)materials.size(); d.materials = materials.data();
     d.n_lights = (uint32_t)lights.size(); d.lights = lights.data();
     d.n_instances = (uint32_t)instances.size(); d.instances = instances.empty() ? nullptr : instances.data();

@@ -93,7 +93,7 @@ const mi_scene_desc *mi_scene_get_desc(const mi_scene *s) { return s ? &s->hs->d
 void mi_scene_get_stats(const mi_scene *s, mi_scene_stats *o) {
     if (!s || !o) return;
     const SceneStats &st = s->hs->stats;
-    o->n_triangles = st.nTriangles; o->n_spheres = st.nSpheres; o->n_meshes = st.nMeshes;
+    o->n_triangles = st.nTriangles; o->n_spheres = st.nSpheres; o->n_disks = st.nDisks; o->n_meshes = st.nMeshes;
     o->interior_nodes = st.interiorNodes; o->leaf_nodes = st.leafNodes;
     o->n_lights = st.nLights; o->n_materials = st.nMaterials;
     o->n_warnings = (int)s->hs->warnings.size(); o->n_errors = (int)s->hs->errors.size();

@@ -12,7 +12,7 @@
 namespace mipt {
 
 struct SceneStats {
-    int nTriangles = 0, nSpheres = 0, nMeshes = 0;
+    int nTriangles = 0, nSpheres = 0, nMeshes = 0, nDisks = 0;
     int interiorNodes = 0, leafNodes = 0;
     int nLights = 0, nMaterials = 0;
 };
@@ -41,6 +41,7 @@ struct HostScene {
     std::vector<float> P, N, UV;
     std::vector<mi_mesh> meshes;
     std::vector<mi_sphere> spheres;
+    std::vector<mi_disk> disks;   // quadric indices continue after the spheres (mi_prim.shape)
     std::vector<mi_material> materials;
     std::vector<mi_light> lights;
     std::vector<HostEnvMap> envStore;   // storage behind desc.envmaps

@@ -16,7 +16,7 @@
 namespace mipt {
 namespace {
 
-const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '7'};
+const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '8'};
 
 struct Out {
     FILE *f;
@@ -68,6 +68,7 @@ void Fields(IO &io, S &s) {   // the same walk writes and reads
     io.Str(s.filmFilename); io.Str(s.integratorName); io.Str(s.samplerName); io.Str(s.lightStrategy);
     io.Strs(s.warnings); io.Strs(s.errors);
     io.Vec(s.primMeta); io.Strs(s.instanceNames); io.Strs(s.namedMaterialNames); io.Vec(s.namedMaterialIds);   // Integrator "metadata" (kind and strategy travel in desc)
+    io.Vec(s.disks);       // Shape "disk" (ABI v14)
     io.Vec(s.lensStore);   // Camera "realistic" (the camera's type travels in desc)
 }
 
@@ -153,7 +154,7 @@ HostScene *LoadSceneCache(const std::string &path, std::string *err) {
     const mi_scene_desc &d = s->desc;
     bool consistent = in.ok && s->nodes.size() == d.n_nodes && s->prims.size() == d.n_prims && s->triIndices.size() == 3ull * d.n_tris &&
                       s->triMesh.size() == d.n_tris && s->P.size() == 3ull * d.n_verts && s->N.size() == 3ull * d.n_verts &&
-                      s->UV.size() == 2ull * d.n_verts && s->meshes.size() == d.n_meshes && s->spheres.size() == d.n_spheres &&
+                      s->UV.size() == 2ull * d.n_verts && s->meshes.size() == d.n_meshes && s->spheres.size() == d.n_spheres && s->disks.size() == d.n_disks &&
                       s->materials.size() == d.n_materials && s->lights.size() == d.n_lights && s->textures.size() == d.n_textures && s->instances.size() == d.n_instances &&
                       s->envStore.size() == d.n_envmaps && s->mipStore.size() == d.n_mipmaps && d.sampler.n_dims >= 0 && (int)s->primes.size() == d.sampler.n_dims &&
                       s->primeSums.size() == s->primes.size() && s->perms.size() == d.sampler.n_perms &&
