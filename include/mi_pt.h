@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define MI_NSPEC 31
-#define MI_ABI_VERSION 14
+#define MI_ABI_VERSION 15
 #define MI_MAX_BXDFS 8 /* BSDF::MaxBxDFs, src/core/reflection.h:196 */
 
 typedef enum mi_status {
@@ -627,6 +627,20 @@ int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *querie
 #define MI_SHAPE_PROBE_HIT_FLOATS 16
 #define MI_SHAPE_PROBE_SAMPLE_FLOATS 7
 int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, const float *queries, float *out);
+
+/* Parity tool for the lights (ABI v15): light `light` of the scene on its own, through the device functions the shading kernel
+ * calls for a next-event estimate and for the MIS weight of a BSDF sample. Host pointers. The reference point is built as
+ * Shape::SolidAngle builds one (no error bound, wo = +z) with the normal of the query; a zero normal is a bare point.
+ *   mode 0: Light::Sample_Li(ref, u). queries: 8 floats (ref.p[3], ref.n[3], u[2]); out: MI_LIGHT_PROBE_SAMPLE_FLOATS floats --
+ *           wi[3], pdf, pLight.p[3], pLight.n[3] (zero for every light but an area light), Li[MI_NSPEC]. Where Sample_Li
+ *           returns before it has a direction (pdf == 0 on an area light; mapPdf == 0 on the infinite light) all are 0; where
+ *           the sample is black (a one-sided emitter seen from behind) the Li bins are 0.
+ *   mode 1: Light::Pdf_Li(ref, wi). queries: 9 floats (ref.p[3], ref.n[3], wi[3]); out: 1 float. 0 for the delta lights,
+ *           Shape::Pdf(ref, wi) for an area light, InfiniteAreaLight::Pdf_Li for the infinite light.
+ *   mode 2: Light::Le(ray) of the infinite light -- queries: 3 floats (ray.d) -- and DiffuseAreaLight::L(n, w) of an area
+ *           light -- queries: 6 floats (n[3], w[3]); out: MI_NSPEC floats. MI_ERR_INVALID for the delta lights. */
+#define MI_LIGHT_PROBE_SAMPLE_FLOATS (10 + MI_NSPEC)
+int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const float *queries, float *out);
 
 /* Parity tool for the spatial light-selection strategy: the per-voxel Distribution1D tables mi_pt_create estimated on
  * the device (SpatialLightDistribution::ComputeDistribution, src/core/lightdistrib.cpp:232-300; the reference fills its

@@ -1256,6 +1256,47 @@ void oracle_trace(const mi_scene_desc *desc, const float *rays, uint32_t n, int 
     FillCounters(c, counters);
 }
 
+// One light on its own: the layouts of mi_pt_light_probe (include/mi_pt.h), answered by SampleLi, ShapePdf, InfinitePdfLi and
+// InfiniteLe above. Returns 0, or -1 for a bad light index or mode (mode 2 on a delta light included).
+int oracle_light_probe(const mi_scene_desc *desc, int light, int mode, uint32_t n, const float *queries, float *out) {
+    const mi_scene_desc &d = *desc;
+    if (light < 0 || (uint32_t)light >= d.n_lights || mode < 0 || mode > 2) return -1;
+    const mi_light &l = d.lights[light];
+    if (mode == 2 && IsDeltaLight(l)) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (mode == 2) {
+            float *o = out + (size_t)NS * i;
+            Spec L;
+            if (l.type == MI_LIGHT_INFINITE) {
+                const float *r = queries + 3 * (size_t)i;
+                L = InfiniteLe(d, l, V3(r[0], r[1], r[2]));
+            } else {   // DiffuseAreaLight::L(n, w), diffuse.h:56-58 (PrimLe)
+                const float *r = queries + 6 * (size_t)i;
+                L = (l.two_sided || Dot(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5])) > 0) ? Spec::From(l.L) : Spec(0.f);
+            }
+            for (int b = 0; b < NS; ++b) o[b] = L.c[b];
+            continue;
+        }
+        const float *r = queries + (mode == 0 ? 8 : 9) * (size_t)i;
+        Interaction ref;
+        ref.p = V3(r[0], r[1], r[2]);
+        ref.pError = V3(0, 0, 0); ref.n = V3(r[3], r[4], r[5]); ref.wo = V3(0, 0, 1);
+        if (mode == 0) {
+            float *o = out + (size_t)MI_LIGHT_PROBE_SAMPLE_FLOATS * i;
+            const Float u[2] = {r[6], r[7]};
+            const LightSample ls = SampleLi(d, l, ref, u);
+            o[0] = ls.wi.x; o[1] = ls.wi.y; o[2] = ls.wi.z; o[3] = ls.pdf;
+            o[4] = ls.pLight.p.x; o[5] = ls.pLight.p.y; o[6] = ls.pLight.p.z;
+            o[7] = ls.pLight.n.x; o[8] = ls.pLight.n.y; o[9] = ls.pLight.n.z;
+            for (int b = 0; b < NS; ++b) o[10 + b] = ls.Li.c[b];
+        } else {
+            const V3 wi(r[6], r[7], r[8]);
+            out[i] = IsDeltaLight(l) ? 0.f : (l.type == MI_LIGHT_INFINITE ? InfinitePdfLi(d, l, wi) : ShapePdf(d, l.shape, l.area, ref, wi));
+        }
+    }
+    return 0;
+}
+
 // libm evaluation mode of the oracle (o_math.h): 0 = the host's float functions, 1 = correctly rounded. Returns the previous mode.
 int oracle_set_libm(int mode) { const int old = g_libmMode; g_libmMode = mode ? 1 : 0; return old; }
 

@@ -18,6 +18,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 NSPEC = 31
+LIGHT_PROBE_SAMPLE_FLOATS = 10 + NSPEC   # MI_LIGHT_PROBE_SAMPLE_FLOATS
 MAX_BXDFS = 8
 PATH_RECORD_FLOATS = 96
 
@@ -284,6 +285,7 @@ def hip_lib():
         lib.mi_pt_trace_wavefront.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_texture_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_shape_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.mi_pt_light_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_light_distribution.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]
         lib.mi_pt_debug_path.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         lib.mi_pt_shade_instances.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -610,6 +612,26 @@ class PathIntegrator:
         rc = hip_lib().mi_pt_shape_probe(self._h, int(quadric), int(mode), q.shape[0], _fptr(q), _fptr(out))
         if rc != 0:
             raise RuntimeError("mi_pt_shape_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
+        return out[:, 0] if n_out == 1 else out
+
+    def light_probe(self, light, mode, queries):
+        """One light of the scene on its own (mi_pt_light_probe). queries: [n, k] float32. mode 0: k = 8 (ref.p, ref.n, u) ->
+        [n, LIGHT_PROBE_SAMPLE_FLOATS] wi, pdf, pLight.p, pLight.n, Li[31] of Light::Sample_Li; mode 1: k = 9 (ref.p, ref.n,
+        wi) -> [n] Light::Pdf_Li; mode 2: k = 3 (d; infinite light: Le) or k = 6 (n, w; area light: L) -> [n, 31]. A bad light
+        index or mode is the library's to refuse: RuntimeError with its message."""
+        q = np.ascontiguousarray(queries, np.float32)
+        q = q.reshape(len(q), -1)
+        light, mode = int(light), int(mode)
+        n_out = {0: LIGHT_PROBE_SAMPLE_FLOATS, 1: 1}.get(mode, NSPEC)
+        want = {0: 8, 1: 9}.get(mode)
+        if mode == 2 and 0 <= light < self.scene.desc.n_lights:   # mi_light_type: 0 = an area light, 3 = the infinite light
+            want = {0: 6, 3: 3}.get(int(self.scene.desc.lights[light].type))
+        if want is not None and q.shape[1] != want:
+            raise ValueError("light_probe mode %d takes %d floats per query for this light" % (mode, want))
+        out = np.zeros((q.shape[0], n_out), np.float32)
+        rc = hip_lib().mi_pt_light_probe(self._h, int(light), int(mode), q.shape[0], _fptr(q), _fptr(out))
+        if rc != 0:
+            raise RuntimeError("mi_pt_light_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
         return out[:, 0] if n_out == 1 else out
 
 

@@ -2993,6 +2993,45 @@ __global__ void k_shape_probe(DScene s, int q, int mode, const float *in, uint32
     }
 }
 
+// ------------------------------------------------------------------ one light on its own (mi_pt_light_probe)
+// SampleLi / LiBin / ShapeSample with the full mask, as the general k_shade instance holds them; InfinitePdfLi, ShapePdf and
+// InfiniteLe as its MIS branch calls them. The reference point: no error bound, wo = +z, the query's normal.
+__global__ void k_light_probe(DScene s, int light, int mode, const float *in, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const mi_light &l = s.lights[light];
+    if (mode == 2) {
+        float *o = out + MI_NSPEC * (size_t)i;
+        if (l.type == MI_LIGHT_INFINITE) {
+            const float *r = in + 3 * (size_t)i;
+            const IllumRGB le = InfiniteLe(s, l, V3(r[0], r[1], r[2]));
+            for (int b = 0; b < MI_NSPEC; ++b) o[b] = IllumBin(s, le, b);
+        } else {   // DiffuseAreaLight::L(n, w), diffuse.h:56-58: the test k_shade makes where a path meets an emitter
+            const float *r = in + 6 * (size_t)i;
+            const bool emits = l.two_sided || Dot(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5])) > 0;
+            for (int b = 0; b < MI_NSPEC; ++b) o[b] = emits ? l.L[b] : 0.f;
+        }
+        return;
+    }
+    const float *r = in + (mode == 0 ? 8 : 9) * (size_t)i;
+    Interaction ref;
+    ref.p = V3(r[0], r[1], r[2]);
+    ref.pError = V3(0, 0, 0); ref.n = V3(r[3], r[4], r[5]); ref.wo = V3(0, 0, 1);
+    if (mode == 0) {
+        float *o = out + MI_LIGHT_PROBE_SAMPLE_FLOATS * (size_t)i;
+        for (int k = 0; k < MI_LIGHT_PROBE_SAMPLE_FLOATS; ++k) o[k] = 0.f;
+        const LightSample ls = SampleLi<TM_ALL>(s, l, ref, r[6], r[7]);
+        if (ls.black && ls.pdf == 0) return;   // Sample_Li returned before it had a direction
+        o[0] = ls.wi.x; o[1] = ls.wi.y; o[2] = ls.wi.z; o[3] = ls.pdf;
+        o[4] = ls.pLight.p.x; o[5] = ls.pLight.p.y; o[6] = ls.pLight.p.z;
+        if (l.type == MI_LIGHT_DIFFUSE_AREA) { o[7] = ls.pLight.n.x; o[8] = ls.pLight.n.y; o[9] = ls.pLight.n.z; }
+        if (!ls.black) for (int b = 0; b < MI_NSPEC; ++b) o[10 + b] = LiBin<TM_ALL>(s, l, ls, b);
+    } else {
+        const V3 wi(r[6], r[7], r[8]);
+        out[i] = IsDeltaLight(l) ? 0.f : (l.type == MI_LIGHT_INFINITE ? InfinitePdfLi(s, l, wi) : ShapePdf<true>(s, l.shape, l.area, ref, wi));
+    }
+}
+
 // ------------------------------------------------------------------ scalar helpers on their own (mi_pt_math_probe)
 __global__ void k_math_probe(int op, uint32_t n, const float *x, const float *y, float *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3372,6 +3411,7 @@ struct mi_pt {
     bool hasAlphaMasks = false;      // picks the traversal kernels compiled with the alpha-mask test
     bool hasInstances = false;       // ... and with the TransformedPrimitive code (those carry the alpha-mask test too)
     uint32_t nQuadrics = 0;          // n_spheres + n_disks (mi_pt_shape_probe)
+    std::vector<int> lightTypes;     // mi_light.type of every light (mi_pt_light_probe)
     bool hasQuadrics = false;        // the scene has spheres or disks: the quadric lists of rays can overflow (k_resolve_overflow is launched)
     bool hasInfiniteLight = false;   // picks the kernels compiled with the environment-light code
     unsigned shadeClasses[N_SHADE_INSTANCES] = {0};   // per k_shade instance: the shading classes it runs (ShadeInstanceOf)
@@ -4122,6 +4162,7 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     pt->hasInstances = d->n_instances > 0;
     pt->hasQuadrics = h.hasQuadrics;
     pt->nQuadrics = d->n_spheres + d->n_disks;
+    for (uint32_t i = 0; i < d->n_lights; ++i) pt->lightTypes.push_back(d->lights[i].type);
     pt->hasInfiniteLight = h.classes.hasInfiniteLight;
     memcpy(pt->shadeClasses, h.classes.shadeClasses, sizeof(pt->shadeClasses));
     pt->nTextures = d->n_textures;
@@ -4803,6 +4844,29 @@ int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, cons
     HIPCHK(dout.alloc((size_t)n * nOut * sizeof(float)));
     HIPCHK(hipMemcpy(dq.p, queries, (size_t)n * nIn * sizeof(float), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_shape_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, (int)quadric, (int)mode, dq.as<float>(), n, dout.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * nOut * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (light < 0 || (size_t)light >= pt->lightTypes.size()) { g_err = "mi_pt_light_probe: light index out of range"; return MI_ERR_INVALID; }
+    if (mode < 0 || mode > 2) { g_err = "mi_pt_light_probe: mode must be 0, 1 or 2"; return MI_ERR_INVALID; }
+    const int type = pt->lightTypes[light];
+    const bool delta = type == MI_LIGHT_POINT || type == MI_LIGHT_DISTANT || type == MI_LIGHT_SPOT;
+    if (mode == 2 && delta) { g_err = "mi_pt_light_probe: mode 2 (Le / L) on a delta light"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_light_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const size_t nIn = mode == 0 ? 8 : (mode == 1 ? 9 : (type == MI_LIGHT_INFINITE ? 3 : 6));
+    const size_t nOut = mode == 0 ? MI_LIGHT_PROBE_SAMPLE_FLOATS : (mode == 1 ? 1 : MI_NSPEC);
+    HIPCHK(hipSetDevice(pt->device));
+    DevBuf dq, dout;
+    HIPCHK(dq.alloc((size_t)n * nIn * sizeof(float)));
+    HIPCHK(dout.alloc((size_t)n * nOut * sizeof(float)));
+    HIPCHK(hipMemcpy(dq.p, queries, (size_t)n * nIn * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_light_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, (int)light, (int)mode, dq.as<float>(), n, dout.as<float>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, dout.p, (size_t)n * nOut * sizeof(float), hipMemcpyDeviceToHost));

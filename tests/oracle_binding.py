@@ -38,6 +38,7 @@ def lib():
         l.oracle_light_voxel.argtypes = [D, C.POINTER(C.c_int32), F, F]
         l.oracle_light_table.argtypes = [D, C.c_int, F, F]
         l.oracle_path_log.argtypes = [D, C.c_int, C.c_int, C.c_int64, C.c_int, F]
+        l.oracle_light_probe.argtypes = [D, C.c_int, C.c_int, C.c_uint32, F, F]
         _lib = l
     return _lib
 
@@ -112,6 +113,18 @@ def path_log(scene, px, py, sample, max_records=64):
     rec = np.zeros((max_records, pt.PATH_RECORD_FLOATS), np.float32)
     n = lib().oracle_path_log(scene.desc_ptr, int(px), int(py), int(sample), max_records, _f(rec))
     return rec[:n]
+
+
+def light_probe(scene, light, mode, queries):
+    """oracle_light_probe: the layouts of PathIntegrator.light_probe (mi_pt_light_probe), answered by the oracle's SampleLi,
+    ShapePdf, InfinitePdfLi and InfiniteLe. ValueError for a bad light index or mode."""
+    q = np.ascontiguousarray(queries, np.float32)
+    q = q.reshape(len(q), -1)
+    n_out = {0: pt.LIGHT_PROBE_SAMPLE_FLOATS, 1: 1}.get(int(mode), pt.NSPEC)
+    out = np.zeros((q.shape[0], n_out), np.float32)
+    if lib().oracle_light_probe(scene.desc_ptr, int(light), int(mode), q.shape[0], _f(q), _f(out)) != 0:
+        raise ValueError("oracle_light_probe: bad light index or mode")
+    return out[:, 0] if n_out == 1 else out
 
 
 def set_libm(mode):

@@ -25,9 +25,9 @@ def _world_bound(s):
     return np.array(list(n.bmin), np.float32), np.array(list(n.bmax), np.float32)
 
 
-def test_abi_version_is_14(pt):
+def test_abi_version_is_15(pt):
     s = _scene(pt, TRI)
-    assert s.desc.abi_version == 14
+    assert s.desc.abi_version == 15
     assert "n_disks" in s.stats and s.stats["n_disks"] == 0 and s.desc.n_disks == 0
 
 
@@ -178,7 +178,7 @@ def test_scene_cache_round_trip(pt, tmp_path):
     path = str(tmp_path / "scene.cache")
     s.save_cache(path)
     t = pt.Scene(cache=path)
-    assert t.stats == s.stats and t.desc.n_disks == 2 and t.desc.abi_version == 14
+    assert t.stats == s.stats and t.desc.n_disks == 2 and t.desc.abi_version == 15
     for i in range(2):
         a, b = s.desc.disks[i], t.desc.disks[i]
         assert bytes(a) == bytes(b)
