@@ -70,8 +70,31 @@ typedef struct mi_prim {
 typedef struct mi_instance {
     float i2w[16], w2i[16];
     uint32_t root;
-    uint32_t pad[3];
+    uint32_t motion;      /* index + 1 into mi_scene_desc.motions: the instance moves; 0 = static */
+    uint32_t instance_id; /* SurfaceInteraction::instanceId of a hit reached through it: the 1-based number of its
+                           * ObjectInstance call; 0 for the wrapper of a moving Shape (api.cpp:1363-1430) */
+    uint32_t pad;
 } mi_instance;
+
+/* The AnimatedTransform of a moving TransformedPrimitive (src/core/transform.cpp:396-411, 1144-1224; object motion, built by
+ * the front end only with MIPT_OBJECT_MOTION=1 in the environment). The instance's i2w / w2i are the start member (times <=
+ * transform_start), i2w_end / w2i_end the end member with its stored inverse (times >= transform_end). Between the two
+ * times a ray of time t is carried by Interpolate(t): m = Translate(Lerp T) * Slerp(dt, R[0], R[1]).ToTransform() *
+ * Transform(Lerp S), dt = (t - transform_start) / (transform_end - transform_start), and by that product's own mInv =
+ * Inverse(Lerp S) * (the un-transposed quaternion matrix) * Translate(-Lerp T), Inverse being the reference's Gauss-Jordan
+ * (transform.cpp:82-136). T, R, S as in mi_camera: R = {x, y, z, w}, R[1] already negated onto the shorter arc; S the upper
+ * 3x3 of the scale matrix, row major. has_rotation: Dot(R[0], R[1]) < 0.9995 after that flip (the
+ * reference's hasRotation, transform.cpp:411; only the world bound asks). Members that are equal make no record. The
+ * version number stays 15: a description without motion records is laid out and read exactly as before (the two words of
+ * mi_instance were padding, kept 0; the new array is appended), and a hand-built v15 instance with instance_id 0 still
+ * reports its index + 1 where it has no motion record. */
+typedef struct mi_motion {
+    float i2w_end[16], w2i_end[16];
+    float T[2][3], R[2][4], S[2][9];
+    float transform_start, transform_end;
+    int32_t has_rotation;
+    int32_t pad;
+} mi_motion;
 
 /* Per TriangleMesh flags (src/shapes/triangle.cpp:54-92). */
 #define MI_MESH_HAS_N 1u
@@ -435,7 +458,8 @@ typedef enum mi_metadata_strategy {
  * 0 for a primitive without a material (the reference dereferences a null pointer there, primitive.cpp:125).
  * instance_id: the 1-based number of the ObjectInstance call the primitive was created by (api.cpp:1589-1614,
  * primitive.cpp:89), 0 outside instances -- and 0 in every entry of a scene whose instances are TransformedPrimitives
- * (mi_instance): there the id is the hit's instance + 1. */
+ * (mi_instance): there the id is the instance's own (mi_instance.instance_id; without one and without a motion record, the
+ * hit's instance + 1). */
 typedef struct mi_prim_meta {
     uint32_t material_id, instance_id;
 } mi_prim_meta;
@@ -468,6 +492,7 @@ typedef struct mi_scene_desc {
     int32_t camera_type;           /* ABI v13: mi_camera_type of `camera` */
     const mi_lens *lens;           /* ABI v13: MI_CAMERA_REALISTIC: the lens system; NULL for a perspective camera */
     uint32_t n_disks; const mi_disk *disks; /* ABI v14: quadric indices [n_spheres, n_spheres + n_disks) */
+    uint32_t n_motions; const mi_motion *motions; /* object motion: the records mi_instance.motion points into */
 } mi_scene_desc;
 
 /* Counters with the reference's STAT names (src/core/integrator.cpp:48,
@@ -558,6 +583,9 @@ const char *mi_pt_last_error(void);
  * hits: n x {prim (int32 as float bits), t, b0, b1} ; any_hit!=0 -> IntersectP
  * semantics (prim = 0/-1 only). Host pointers. */
 int mi_pt_trace(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits);
+/* The same with a time per ray: n x {o[3], d[3], tMax, time} (8 floats). The time decides the transform of a moving
+ * instance (mi_motion); mi_pt_trace's rays take the shutter-open time. */
+int mi_pt_trace_timed(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits);
 
 /* The same question answered by the kernels a render launches (mi_pt_trace runs a plain per-ray routine, k_trace): ray i is
  * loaded into slot i of a path pool and a work list as the pipeline leaves it, traversed by the persistent wavefront kernel
@@ -581,6 +609,9 @@ int mi_pt_trace(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hi
  * the hit primitive as the traversal kernel left it, before the quadric step (int32 bits; -2 = the ray was never answered;
  * mode 1, whose kernel keeps one answer word per queue entry: 0 = occluded, -1 = not)}. Host pointers; n <= 2^24. */
 int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra);
+/* The same with a time per ray (8 floats per ray, as mi_pt_trace_timed): it goes into the pool's time plane, where the
+ * render's kernels read it. mi_pt_trace_wavefront's rays take the shutter-open time. */
+int mi_pt_trace_wavefront_timed(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra);
 
 /* Parity tool for the camera: sample i = {px, py, sample number} (three int32) goes through the device functions k_generate
  * calls -- CameraSampleDims, then CameraRay -- and out receives 8 floats per sample: o[3], d[3], tMax, time. (time is

@@ -35,7 +35,15 @@ class Prim(C.Structure):
 
 
 class Instance(C.Structure):
-    _fields_ = [("i2w", C.c_float * 16), ("w2i", C.c_float * 16), ("root", C.c_uint32), ("pad", C.c_uint32 * 3)]
+    _fields_ = [("i2w", C.c_float * 16), ("w2i", C.c_float * 16), ("root", C.c_uint32), ("motion", C.c_uint32),
+                ("instance_id", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class Motion(C.Structure):
+    """mi_motion: the AnimatedTransform of a moving instance (MIPT_OBJECT_MOTION=1)."""
+    _fields_ = [("i2w_end", C.c_float * 16), ("w2i_end", C.c_float * 16),
+                ("T", (C.c_float * 3) * 2), ("R", (C.c_float * 4) * 2), ("S", (C.c_float * 9) * 2),
+                ("transform_start", C.c_float), ("transform_end", C.c_float), ("has_rotation", C.c_int32), ("pad", C.c_int32)]
 
 
 class Mesh(C.Structure):
@@ -169,7 +177,8 @@ class SceneDesc(C.Structure):
                 ("n_instances", C.c_uint32), ("instances", C.POINTER(Instance)),
                 ("prim_meta", C.POINTER(PrimMeta)),
                 ("camera_type", C.c_int32), ("lens", C.POINTER(Lens)),
-                ("n_disks", C.c_uint32), ("disks", C.POINTER(Disk))]
+                ("n_disks", C.c_uint32), ("disks", C.POINTER(Disk)),
+                ("n_motions", C.c_uint32), ("motions", C.POINTER(Motion))]
 
 
 class Counters(C.Structure):
@@ -283,6 +292,8 @@ def hip_lib():
         lib.mi_pt_camera_rays_ex.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_int32, C.POINTER(C.c_float)]
         lib.mi_pt_math_probe.argtypes = [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_trace_wavefront.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.mi_pt_trace_timed.argtypes = lib.mi_pt_trace.argtypes
+        lib.mi_pt_trace_wavefront_timed.argtypes = lib.mi_pt_trace_wavefront.argtypes
         lib.mi_pt_texture_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_shape_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_light_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -530,10 +541,13 @@ class PathIntegrator:
         return p.value, int(n.value)
 
     def trace(self, rays, any_hit=False):
+        """rays [n, 7] = o, d, tMax, or [n, 8] with each ray's time in the eighth column (it decides the transform of a
+        moving instance; without it a ray takes the shutter-open time)."""
         rays = np.ascontiguousarray(rays, np.float32)
         n = rays.shape[0]
         hits = np.zeros((n, 4), np.float32)
-        rc = hip_lib().mi_pt_trace(self._h, _fptr(rays), n, 1 if any_hit else 0, _fptr(hits))
+        fn = hip_lib().mi_pt_trace_timed if rays.shape[1] == 8 else hip_lib().mi_pt_trace
+        rc = fn(self._h, _fptr(rays), n, 1 if any_hit else 0, _fptr(hits))
         if rc != 0:
             raise RuntimeError("mi_pt_trace failed: %s" % hip_lib().mi_pt_last_error().decode())
         return hits
@@ -568,7 +582,8 @@ class PathIntegrator:
         n = rays.shape[0]
         hits = np.zeros((n, 4), np.float32)
         extra = np.zeros((n, 4), np.float32)
-        rc = hip_lib().mi_pt_trace_wavefront(self._h, _fptr(rays), n, int(mode), _fptr(hits), _fptr(extra))
+        fn = hip_lib().mi_pt_trace_wavefront_timed if rays.shape[1] == 8 else hip_lib().mi_pt_trace_wavefront   # (rays [n, 8]: a time per ray)
+        rc = fn(self._h, _fptr(rays), n, int(mode), _fptr(hits), _fptr(extra))
         if rc != 0:
             raise RuntimeError("mi_pt_trace_wavefront failed: %s" % hip_lib().mi_pt_last_error().decode())
         return hits, extra.view(np.int32)

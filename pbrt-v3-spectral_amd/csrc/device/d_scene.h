@@ -107,6 +107,12 @@ struct DScene {
     int maxDepth;
     float rrThreshold;
     int nBands, bandDelta;  // spectralpath: paths per camera sample, bins per band (1, 31 for "path")
+    // object motion (appended: the kernels of scenes without instances read nothing of it and keep their code). motions: the
+    // device copy of mi_scene_desc.motions, null when no instance moves -- then no kernel looks at mi_instance::motion.
+    // timePlane: the pool's float plane that holds each path's ray time (Ray::time: the camera ray's, carried by every ray
+    // the path spawns), allocated and written only when motions is set.
+    const mi_motion *motions;
+    int timePlane;
 };
 
 struct Interaction {
@@ -441,7 +447,9 @@ DEV Ray XfRay(const float *m, const Ray &r) {
 // (quaternion.h:87-97 over geometry.h:245-249); ToTransform's matrix is the transpose of the one it writes down
 // (quaternion.cpp:41-59). The two matrix products are written out without the terms that multiply an exact 0 or 1 of
 // Translate's and the scale's fourth row and column: the same values, up to the sign of a zero.
-DEV void InterpolateCameraToWorld(const mi_camera *__restrict__ cam, float time, float *m) {
+// (REC: mi_camera, or the mi_motion of a moving instance -- the same fields under the same names)
+template <typename REC>
+DEV void InterpolateCameraToWorld(const REC *__restrict__ cam, float time, float *m) {
     const float dt = (time - cam->transform_start) / (cam->transform_end - cam->transform_start);
     const float tx = (1 - dt) * cam->T[0][0] + dt * cam->T[1][0], ty = (1 - dt) * cam->T[0][1] + dt * cam->T[1][1],
                 tz = (1 - dt) * cam->T[0][2] + dt * cam->T[1][2];
@@ -491,6 +499,164 @@ DEV void MovingCameraToWorld(const mi_camera *__restrict__ cam, float time, floa
     for (int i = 0; i < 16; ++i) {
         const float a = cam->camera_to_world[i], b = cam->camera_to_world_end[i];
         m[i] = atStart ? a : (atEnd ? b : mid[i]);
+    }
+}
+
+// ------------------------------------------------------------------ moving instances (object motion)
+// A TransformedPrimitive's AnimatedTransform at a ray's time (TransformedPrimitive::Intersect, primitive.cpp:78-92:
+// PrimitiveToWorld.Interpolate(r.time, &InterpolatedPrimToWorld), transform.cpp:1144-1169): the start member with its stored
+// inverse up to transform_start, the end member from transform_end on, between them the product Translate(trans) *
+// rotate.ToTransform() * Transform(scale) and ITS mInv. Two routines, one matrix each, both out of line and returning their
+// sixteen values in registers: a callee that wrote through a pointer into the caller's frame would move the caller's
+// matrices to private memory (the disk notes of DESIGN.md), and sixteen registers is what a call returns directly.
+struct Mat44 { float v[16]; };
+__device__ __attribute__((noinline)) Mat44 MovingInstanceToWorld(const mi_instance *__restrict__ in, const mi_motion *__restrict__ mo, float time) {
+    const bool atStart = time <= mo->transform_start, atEnd = time >= mo->transform_end;
+    float mid[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mid[i] = 0.f;
+    if (!atStart && !atEnd) InterpolateCameraToWorld(mo, time, mid);
+    Mat44 r;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float a = in->i2w[i], b = mo->i2w_end[i];
+        r.v[i] = atStart ? a : (atEnd ? b : mid[i]);
+    }
+    return r;
+}
+DEV float Sel3(int k, float a, float b, float c) { return k == 0 ? a : (k == 1 ? b : c); }
+// Inverse(Matrix4x4) (transform.cpp:82-136: Gauss-Jordan with full pivoting, the last of equal maxima is the pivot, its
+// reciprocal a double division rounded to float) of a matrix whose fourth row and column are (0, 0, 0, 1), on its 3x3 block
+// alone: the border's 1 competes for the pivot but, whenever it is taken, scales by 1 and eliminates with factor 0, and the
+// block's own pivots are found among the same candidates in the same order either way -- the block of the 4x4 routine's
+// result, bit for bit (tests/test_object_motion_frontend.py holds the numpy restatement of both to that). Rows and columns
+// are chosen at run time: every access is a select between registers, no array is indexed by a run-time value.
+DEV void InverseScale3(float *a) {
+    int red = 0, pr0 = 0, pc0 = 0, pr1 = 0, pc1 = 0, pr2 = 0, pc2 = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        float big = 0.f;
+        int pr = 0, pc = 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const bool take = !((red >> j) & 1) && !((red >> k) & 1) && absf(a[3 * j + k]) >= big;
+                big = take ? absf(a[3 * j + k]) : big; pr = take ? j : pr; pc = take ? k : pc;
+            }
+        }
+        red |= 1 << pc;
+        float rowP[3], rowC[3];   // the rows pr and pc; after the swap the pivot row (at pc) is rowP
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { rowP[k] = Sel3(pr, a[k], a[3 + k], a[6 + k]); rowC[k] = Sel3(pc, a[k], a[3 + k], a[6 + k]); }
+        const float pivinv = (float)(1. / (double)Sel3(pc, rowP[0], rowP[1], rowP[2]));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rowP[k] = (k == pc ? 1.f : rowP[k]) * pivinv;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            float row[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) row[k] = (j == pr) ? rowC[k] : a[3 * j + k];   // (row j after the swap, j != pc)
+            const float save = Sel3(pc, row[0], row[1], row[2]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float v = (k == pc ? 0.f : row[k]) - rowP[k] * save;
+                a[3 * j + k] = (j == pc) ? rowP[k] : v;
+            }
+        }
+        if (i == 0) { pr0 = pr; pc0 = pc; } else if (i == 1) { pr1 = pr; pc1 = pc; } else { pr2 = pr; pc2 = pc; }
+    }
+#pragma unroll
+    for (int i = 2; i >= 0; --i) {   // the column swaps, last pivot first
+        const int pr = i == 0 ? pr0 : (i == 1 ? pr1 : pr2), pc = i == 0 ? pc0 : (i == 1 ? pc1 : pc2);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float x = Sel3(pr, a[3 * j], a[3 * j + 1], a[3 * j + 2]), y = Sel3(pc, a[3 * j], a[3 * j + 1], a[3 * j + 2]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a[3 * j + k] = (k == pr) ? y : ((k == pc) ? x : a[3 * j + k]);
+        }
+    }
+}
+// mInv of Translate(trans) * rotate.ToTransform() * Transform(scale) (Transform::operator*, transform.cpp:244-246, twice):
+// Inverse(scale) * (ToTransform's un-transposed matrix * Translate(-trans)), each product in Matrix4x4::Mul's order without
+// the terms that multiply an exact 0 or 1 -- the same values, up to the sign of a zero.
+DEV void InterpolateWorldToInstance(const mi_motion *__restrict__ mo, float time, float *mi) {
+    const float dt = (time - mo->transform_start) / (mo->transform_end - mo->transform_start);
+    const float tx = (1 - dt) * mo->T[0][0] + dt * mo->T[1][0], ty = (1 - dt) * mo->T[0][1] + dt * mo->T[1][1],
+                tz = (1 - dt) * mo->T[0][2] + dt * mo->T[1][2];
+    const float ax = mo->R[0][0], ay = mo->R[0][1], az = mo->R[0][2], aw = mo->R[0][3];
+    const float bx = mo->R[1][0], by = mo->R[1][1], bz = mo->R[1][2], bw = mo->R[1][3];
+    const float cosTheta = (ax * bx + ay * by + az * bz) + aw * bw;
+    float x, y, z, w;   // Slerp, as in InterpolateCameraToWorld
+    if (cosTheta > .9995f) {
+        x = ax * (1 - dt) + bx * dt; y = ay * (1 - dt) + by * dt; z = az * (1 - dt) + bz * dt; w = aw * (1 - dt) + bw * dt;
+        const float len = __builtin_sqrtf((x * x + y * y + z * z) + w * w), inv = 1.f / len;
+        x *= inv; y *= inv; z *= inv; w /= len;
+    } else {
+        const float theta = acosF(clampf(cosTheta, -1.f, 1.f));
+        const float thetap = theta * dt;
+        float px = bx - ax * cosTheta, py = by - ay * cosTheta, pz = bz - az * cosTheta, pw = bw - aw * cosTheta;
+        const float len = __builtin_sqrtf((px * px + py * py + pz * pz) + pw * pw), inv = 1.f / len;
+        px *= inv; py *= inv; pz *= inv; pw /= len;
+        const float c = cosF(thetap), sn = sinF(thetap);
+        x = ax * c + px * sn; y = ay * c + py * sn; z = az * c + pz * sn; w = aw * c + pw * sn;
+    }
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = x * w, wy = y * w, wz = z * w;
+    float q[9];   // ToTransform's `m` as written down (the inverse of the rotation), row major
+    q[0] = 1 - 2 * (yy + zz); q[1] = 2 * (xy + wz);     q[2] = 2 * (xz - wy);
+    q[3] = 2 * (xy - wz);     q[4] = 1 - 2 * (xx + zz); q[5] = 2 * (yz + wx);
+    q[6] = 2 * (xz + wy);     q[7] = 2 * (yz - wx);     q[8] = 1 - 2 * (xx + yy);
+    float p3[3];  // the fourth column of q * Translate(-trans)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p3[i] = q[3 * i] * -tx + q[3 * i + 1] * -ty + q[3 * i + 2] * -tz;
+    float sc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) sc[i] = lerpf(dt, mo->S[0][i], mo->S[1][i]);
+    InverseScale3(sc);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) mi[4 * i + j] = sc[3 * i] * q[j] + sc[3 * i + 1] * q[3 + j] + sc[3 * i + 2] * q[6 + j];
+        mi[4 * i + 3] = sc[3 * i] * p3[0] + sc[3 * i + 1] * p3[1] + sc[3 * i + 2] * p3[2];
+    }
+    mi[12] = 0.f; mi[13] = 0.f; mi[14] = 0.f; mi[15] = 1.f;
+}
+__device__ __attribute__((noinline)) Mat44 MovingWorldToInstance(const mi_instance *__restrict__ in, const mi_motion *__restrict__ mo, float time) {
+    const bool atStart = time <= mo->transform_start, atEnd = time >= mo->transform_end;
+    float mid[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mid[i] = 0.f;
+    if (!atStart && !atEnd) InterpolateWorldToInstance(mo, time, mid);
+    Mat44 r;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float a = in->w2i[i], b = mo->w2i_end[i];
+        r.v[i] = atStart ? a : (atEnd ? b : mid[i]);
+    }
+    return r;
+}
+// WorldToInstance / InstanceToWorld of instance k for a ray of the given time, as values: the record's own matrices where
+// the instance does not move (s.motions is null in a scene where none does: a uniform branch).
+DEV void InstanceW2I(const DScene &s, int k, float time, float *m) {
+    const mi_instance *in = &s.instances[k];
+    if (s.motions && in->motion) {
+        const Mat44 r = MovingWorldToInstance(in, &s.motions[in->motion - 1], time);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m[i] = r.v[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m[i] = in->w2i[i];
+    }
+}
+DEV void InstanceI2W(const DScene &s, int k, float time, float *m) {
+    const mi_instance *in = &s.instances[k];
+    if (s.motions && in->motion) {
+        const Mat44 r = MovingInstanceToWorld(in, &s.motions[in->motion - 1], time);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m[i] = r.v[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m[i] = in->i2w[i];
     }
 }
 

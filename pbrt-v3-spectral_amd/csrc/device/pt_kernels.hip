@@ -236,6 +236,12 @@ struct Pool {
     DEV float4 &R(int plane, uint32_t slot) const { return plane < R_HIT ? r[RecordIndex(plane, slot)] : r[ScalarIndex(plane, slot)]; }
     DEV int &I(int plane, uint32_t slot) const { return i[ScalarIndex(plane, slot)]; }
 };
+// Ray::time of the slot's path: the camera ray's, which every ray the path spawns keeps (Interaction::SpawnRay[To] pass the
+// interaction's time on, interaction.h:64-86). A plane of its own that exists only in scenes with moving instances and is
+// read only where a ray meets an instance; elsewhere the shutter-open time, which nothing then depends on.
+DEV float PathTime(const DScene &s, const Pool &pool, uint32_t slot) { return s.motions ? pool.F(s.timePlane, slot) : s.camera.shutter_open; }
+// SurfaceInteraction::instanceId of a hit reached through instance k (primitive.cpp:89; the wrapper of a moving shape: 0)
+DEV unsigned InstanceIdOf(const mi_instance &in, int k) { return in.instance_id ? in.instance_id : (in.motion ? 0u : (unsigned)k + 1u); }
 
 // Statistics are striped: STAT_STRIPES copies, each on its own 128-B line, picked by block
 // index, so the per-wave atomics of a launch do not all serialise on one L2 line; the host
@@ -598,9 +604,10 @@ constexpr int MAX_PENDING_SPHERES = 3;
 // of ResolveQuadrics). TOP: the world's tree, whose leaves may hold object instances -- a TransformedPrimitive
 // (primitive.cpp:78-99) takes the ray to the instance's space and traverses the object's tree with it, above the entries
 // the world's traversal has on the stack (`floor`); a hit inside hands its tMax back to the world ray.
-template <bool ANY, int W, bool TOP>
+// MOTION: the scene has moving instances (the entry takes Interpolate(time)); without it the code is the static one.
+template <bool ANY, int W, bool TOP, bool MOTION = false>
 DEV bool TraverseTree(const DScene &s, int rootRecord, bool rootHit, const V3 &ro, const V3 &rd, float &tMax, int floor, int inst,
-                      Hit *hit, unsigned &nodeCount, unsigned &triCount) {
+                      Hit *hit, unsigned &nodeCount, unsigned &triCount, float time) {
     const int lane = threadIdx.x;
     RayCtx r;
     InitRayCtx(r, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z);
@@ -619,14 +626,20 @@ DEV bool TraverseTree(const DScene &s, int rootRecord, bool rootHit, const V3 &r
             if constexpr (TOP && W == 4) {
                 if (pf & PRIM_FLAG_INSTANCE) {
                     const int k = __float_as_int(primTri[3 * prim + 1].w);
-                    const Ray ir = XfRay(s.instances[k].w2i, Ray(ro, rd, tMax));   // Inverse(InstanceToWorld)(r)
+                    Ray ir;   // Inverse(InstanceToWorld)(r), at the ray's time
+                    if constexpr (MOTION) {
+                        float w2i[16];
+                        InstanceW2I(s, k, time, w2i);
+                        ir = XfRay(w2i, Ray(ro, rd, tMax));
+                    } else
+                        ir = XfRay(s.instances[k].w2i, Ray(ro, rd, tMax));
                     RayCtx rc;
                     InitRayCtx(rc, ir.o.x, ir.o.y, ir.o.z, ir.d.x, ir.d.y, ir.d.z);
                     const float4 bMin = s.instRootBounds[2 * k], bMax = s.instRootBounds[2 * k + 1];
                     float tBox, tIn = ir.tMax;
                     ++nodeCount;
                     const bool boxHit = BoxTest(rc, bMin.x, bMin.y, bMin.z, bMax.x, bMax.y, bMax.z, tIn, &tBox);
-                    if (TraverseTree<ANY, W, false>(s, s.instWideRoot[k], boxHit, ir.o, ir.d, tIn, st.sp, k, hit, nodeCount, triCount)) {
+                    if (TraverseTree<ANY, W, false>(s, s.instWideRoot[k], boxHit, ir.o, ir.d, tIn, st.sp, k, hit, nodeCount, triCount, time)) {
                         if (ANY) return true;
                         tMax = tIn;   // r.tMax = ray.tMax
                         found = true;
@@ -663,19 +676,19 @@ DEV bool TraverseTree(const DScene &s, int rootRecord, bool rootHit, const V3 &r
     return found;
 }
 // INST: compiled for scenes with object instances (the nested traversal costs the calling kernel ~40 VGPRs)
-template <bool ANY, int W, bool INST>
-DEV bool TraverseW(const DScene &s, const V3 &ro, const V3 &rd, float tMax, Hit *hit, unsigned &nodeCount, unsigned &triCount) {
+template <bool ANY, int W, bool INST, bool MOTION = false>
+DEV bool TraverseW(const DScene &s, const V3 &ro, const V3 &rd, float tMax, Hit *hit, unsigned &nodeCount, unsigned &triCount, float time) {
     RayCtx r;
     InitRayCtx(r, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z);
     TravState st;
     StartTraversal(s, r, tMax, st, nodeCount);
-    return TraverseTree<ANY, W, INST>(s, 0, st.cur >= 0, ro, rd, tMax, 0, -1, hit, nodeCount, triCount);
+    return TraverseTree<ANY, W, INST, MOTION>(s, 0, st.cur >= 0, ro, rd, tMax, 0, -1, hit, nodeCount, triCount, time);
 }
 
-template <bool ANY, bool INST>
-DEV bool Traverse(const DScene &s, const V3 &ro, const V3 &rd, float tMax, Hit *hit, unsigned &nodeCount, unsigned &triCount) {
-    if (s.bvhWidth == 4) return TraverseW<ANY, 4, INST>(s, ro, rd, tMax, hit, nodeCount, triCount);
-    return TraverseW<ANY, 2, false>(s, ro, rd, tMax, hit, nodeCount, triCount);
+template <bool ANY, bool INST, bool MOTION = false>
+DEV bool Traverse(const DScene &s, const V3 &ro, const V3 &rd, float tMax, Hit *hit, unsigned &nodeCount, unsigned &triCount, float time) {
+    if (s.bvhWidth == 4) return TraverseW<ANY, 4, INST, MOTION>(s, ro, rd, tMax, hit, nodeCount, triCount, time);
+    return TraverseW<ANY, 2, false>(s, ro, rd, tMax, hit, nodeCount, triCount, time);
 }
 
 template <bool DISKS = true>
@@ -728,7 +741,10 @@ constexpr int TRAV_CHUNK = MIPT_TRAV_CHUNK;  // work-list entries a wave reserve
 // Inverse(InstanceToWorld)(ray) and walks the object's tree above that entry; popping the entry reloads the world ray from
 // the pool and resumes the leaf -- with the instance ray's tMax if something was hit inside (`r.tMax = ray.tMax`). The
 // sequence of box tests, primitive tests and tMax updates per ray is the reference's recursion unrolled.
-template <int MODE, bool ALPHA, int W, bool INST = false>
+// MOTION (with INST): the scene has moving instances -- the entry into an instance takes Interpolate(ray time) (InstanceW2I);
+// the instances of scenes whose instances all stand still are compiled without that code (measured: with it behind a
+// launch-uniform branch an instanced static frame cost 3.3 % more, profiles/object_motion_static_cost.jsonl).
+template <int MODE, bool ALPHA, int W, bool INST = false, bool MOTION = false>
 // MODE 3: the MIS rays again, as a visibility query (scenes without instances and without an alpha mask on an emitter's own mesh: DScene::misAny). The estimator
 // reads one bit of a MIS ray -- is the closest hit the sampled light's shape (integrator.cpp:196-203) -- so k_shade hands
 // over the span [tLo, tHi] of the ray in which that shape can be hit and the shape's primitive, and this walks the tree as the
@@ -982,7 +998,13 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                     // TransformedPrimitive::Intersect[P]: the ray in the instance's space, then the object's BVH from its root
                     const int k = __float_as_int(primTri[3 * prim + 1].w);
                     StackPush<!ANY>(spill, lane, st.sp, leafOff, -(leafCnt + 1), tMax);
-                    const Ray ir = XfRay(s.instances[k].w2i, Ray(V3(r.ox, r.oy, r.oz), V3(r.dx, r.dy, r.dz), tMax));
+                    Ray ir;
+                    if constexpr (MOTION) {
+                        float w2i[16];   // (a moving instance: the slot's ray time, read here alone)
+                        InstanceW2I(s, k, PathTime(s, pool, slot), w2i);
+                        ir = XfRay(w2i, Ray(V3(r.ox, r.oy, r.oz), V3(r.dx, r.dy, r.dz), tMax));
+                    } else
+                        ir = XfRay(s.instances[k].w2i, Ray(V3(r.ox, r.oy, r.oz), V3(r.dx, r.dy, r.dz), tMax));
                     InitRayCtx(r, ir.o.x, ir.o.y, ir.o.z, ir.d.x, ir.d.y, ir.d.z);
                     triRay = MakeTriRay(ir.d);
                     tMax = ir.tMax;
@@ -1148,12 +1170,12 @@ DEV bool ResolveQuadrics(const DScene &s, const Pool &pool, uint32_t slot, const
     return true;
 }
 // (*h is written only when something is hit)
-template <bool ANY, bool INST>
-DEV bool Retraverse(const DScene &s, const V3 &ro, const V3 &rd, float tMax, Hit *h) {
+template <bool ANY, bool INST, bool MOTION = false>
+DEV bool Retraverse(const DScene &s, const V3 &ro, const V3 &rd, float tMax, Hit *h, float time) {
     Hit h2;
     h2.prim = -1; h2.t = 0; h2.b0 = h2.b1 = h2.b2 = 0;
     unsigned n2 = 0, t2 = 0;  // statistics were already counted by k_trav
-    const bool found = Traverse<ANY, INST>(s, ro, rd, tMax, &h2, n2, t2);
+    const bool found = Traverse<ANY, INST, MOTION>(s, ro, rd, tMax, &h2, n2, t2, time);
     if (found) *h = h2;
     return found;
 }
@@ -1364,12 +1386,12 @@ DEV void LoadMisRay(const Pool &pool, uint32_t slot, V3 &ro, V3 &rd, Hit &h, boo
     have = true;
 }
 // The closest hit of a MIS ray after its quadrics (h, when found). OVF: the list overflowed, the ray is traversed again.
-template <bool INST, bool OVF>
+template <bool INST, bool OVF, bool MOTION = false>
 DEV bool MisClosestHit(const DScene &s, const Pool &pool, uint32_t slot, int npend, V3 &ro, V3 &rd, Hit &h, bool &haveRay) {
     bool found = h.prim >= 0;
     if (npend != 0) {
         LoadMisRay(pool, slot, ro, rd, h, haveRay);
-        if constexpr (OVF) found = Retraverse<false, INST>(s, ro, rd, kInfinity, &h);
+        if constexpr (OVF) found = Retraverse<false, INST, MOTION>(s, ro, rd, kInfinity, &h, MOTION ? PathTime(s, pool, slot) : 0.f);
         else found = ResolveQuadrics<false>(s, pool, slot, ro, rd, kInfinity, &h, found, npend);
     }
     return found;
@@ -1377,7 +1399,7 @@ DEV bool MisClosestHit(const DScene &s, const Pool &pool, uint32_t slot, int npe
 
 // One MIS ray's commit. OVF = false (k_resolve_mis): a ray whose quadric list overflowed goes to k_resolve_overflow, which
 // runs this again with OVF = true.
-template <bool INST, bool OVF>
+template <bool INST, bool OVF, bool MOTION = false>
 DEV void ResolveMisSlot(const DScene &s, const Pool &pool, DevCounters *ctr, uint32_t slot, int hitPrim, int npend, unsigned &zero) {
     int flags = pool.I(I_FLAGS, slot);
     V3 ro, rd;
@@ -1385,7 +1407,7 @@ DEV void ResolveMisSlot(const DScene &s, const Pool &pool, DevCounters *ctr, uin
     h.prim = hitPrim; h.t = 0.f; h.b0 = h.b1 = h.b2 = 0.f;
     bool haveRay = false;
     if (!OVF && (npend & PEND_OVERFLOW)) { pool.ovfQ[2 * (size_t)pool.n + atomicAdd(&ctr->ovfCount[2].v, 1u)] = slot; return; }
-    const bool found = MisClosestHit<INST, OVF>(s, pool, slot, npend, ro, rd, h, haveRay);
+    const bool found = MisClosestHit<INST, OVF, MOTION>(s, pool, slot, npend, ro, rd, h, haveRay);
     bool added = false;
     const int misLight = s.nLights > 1 ? pool.I(I_MISLIGHT, slot) : 0;
     if (!found && s.lights[misLight].type == MI_LIGHT_INFINITE) added |= AddMisContribution(pool, slot, flags);   // Li = light.Le(ray), integrator.cpp:204
@@ -1478,7 +1500,7 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_mis(DScene s, Pool pool, DevC
 // resolve kernel would have (mode 0: hit record + shading queue; 1: occlusion + L += the light sample; 2: the MIS commit).
 // A fixed small grid walks the queue; it is empty for all but quadric-heavy scenes.
 constexpr int OVERFLOW_GRID = 512;
-template <bool INST>
+template <bool INST, bool MOTION = false>
 __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool, DevCounters *ctr, int mode) {
     const unsigned count = ctr->ovfCount[mode].v;
     unsigned zero = 0, pathLen = 0;
@@ -1488,7 +1510,7 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool,
             const float4 r0 = pool.R(R_RAY0, slot), r1 = pool.R(R_RAY1, slot);
             Hit h;
             h.prim = -1; h.t = 0.f; h.b0 = h.b1 = h.b2 = 0.f;
-            const bool found = Retraverse<false, INST>(s, V3(r0.x, r0.y, r0.z), V3(r1.x, r1.y, r1.z), r0.w, &h);
+            const bool found = Retraverse<false, INST, MOTION>(s, V3(r0.x, r0.y, r0.z), V3(r1.x, r1.y, r1.z), r0.w, &h, MOTION ? PathTime(s, pool, slot) : 0.f);
             const int prim = found ? h.prim : -1;
             pool.I(I_HITPRIM, slot) = prim;
             pool.R(R_HIT, slot) = HitRecord(h);
@@ -1502,10 +1524,10 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool,
         } else if (mode == 1) {
             const float4 r0 = pool.R(R_SH0, slot), r1 = pool.R(R_SH1, slot);
             Hit h;
-            const bool occluded = Retraverse<true, INST>(s, PackedRayO(r0), PackedRayD(r0, r1), 1 - kShadowEpsilon, &h);
+            const bool occluded = Retraverse<true, INST, MOTION>(s, PackedRayO(r0), PackedRayD(r0, r1), 1 - kShadowEpsilon, &h, MOTION ? PathTime(s, pool, slot) : 0.f);
             pool.I(I_FLAGS, slot) = CommitShadowVerdict(pool.I(I_FLAGS, slot), occluded, zero);
         } else
-            ResolveMisSlot<INST, true>(s, pool, ctr, slot, -1, PEND_OVERFLOW, zero);   // (re-traversed from scratch)
+            ResolveMisSlot<INST, true, MOTION>(s, pool, ctr, slot, -1, PEND_OVERFLOW, zero);   // (re-traversed from scratch)
     }
     CountAdd(&Stats(ctr).zeroRadiancePaths, zero);
     CountAdd(&Stats(ctr).pathLengthSum, pathLen);
@@ -1565,7 +1587,9 @@ DEV void CameraRay(const DScene &s, float pFilmX, float pFilmY, float lensU, flo
 // P_WEIGHT and multiplied into the sample at the flush. A sample of weight 0 is a camera ray that traces nothing: its slot is
 // finished here (L = 0), stays out of the extend list, counts as alive -- the host's next iteration flushes it -- and a
 // "spectralpath" band that is vignetted restarts as the next band like any finished one.
-template <bool MOVING, bool REAL>
+// TIME: the scene has moving instances: the ray's time -- Lerp(time sample, shutterOpen, shutterClose), perspective.cpp:141 --
+// goes to the pool's time plane (PathTime), so the time sample is evaluated in front of a camera that stands still too.
+template <bool MOVING, bool REAL, bool TIME = false>
 __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *film, DevCounters *ctr, WorkDesc wd) {
     __shared__ float sL[BLOCK * 33];
     __shared__ float sFilter[256];  // the 16x16 filter table, one LDS copy per block
@@ -1877,7 +1901,8 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
             float u0, u1, lu, lv;
             int dimAfter;
             float tu = 0.f;
-            const uint64_t index = CameraSampleDims<MOVING>(s, px, py, sampleNum, &u0, &u1, &lu, &lv, &dimAfter, &tu);
+            const uint64_t index = CameraSampleDims<MOVING || TIME>(s, px, py, sampleNum, &u0, &u1, &lu, &lv, &dimAfter, &tu);
+            if constexpr (TIME) pool.F(s.timePlane, slot) = lerpf(tu, s.camera.shutter_open, s.camera.shutter_close);
             float pfx = (float)px + u0, pfy = (float)py + u1;
             Ray ray;
             bool traced = true;   // REAL: the ray got through the lens (GenerateRayDifferential's weight > 0: Li is called)
@@ -1958,6 +1983,10 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
 // The k_generate of a scene's camera: a uniform choice per launch.
 using GenerateKernel = void (*)(DScene, Pool, float *, DevCounters *, WorkDesc);
 static GenerateKernel GenerateKernelOf(const DScene &s) {
+    if (s.motions) {
+        if (s.cameraType == MI_CAMERA_REALISTIC) return s.camera.animated ? k_generate<true, true, true> : k_generate<false, true, true>;
+        return s.camera.animated ? k_generate<true, false, true> : k_generate<false, false, true>;
+    }
     if (s.cameraType == MI_CAMERA_REALISTIC) return s.camera.animated ? k_generate<true, true> : k_generate<false, true>;
     return s.camera.animated ? k_generate<true, false> : k_generate<false, false>;
 }
@@ -1966,8 +1995,7 @@ static GenerateKernel GenerateKernelOf(const DScene &s) {
 
 // Transform::operator()(const SurfaceInteraction&), transform.cpp:262-297, with an instance's InstanceToWorld: the fields the
 // path reads (SurfaceInteraction) and the ones textures and bump mapping read besides (TriShading).
-DEV void InteractionToWorld(const mi_instance &in, SurfaceInteraction *si) {
-    const float *m = in.i2w, *mInv = in.w2i;
+DEV void InteractionToWorld(const float *m, const float *mInv, SurfaceInteraction *si) {
     V3 pErr;
     si->p = XfPointErr2(m, si->p, si->pError, &pErr);
     si->pError = pErr;
@@ -1978,8 +2006,8 @@ DEV void InteractionToWorld(const mi_instance &in, SurfaceInteraction *si) {
     si->shDpdu = XfVector(m, si->shDpdu);
     si->shN = Faceforward(si->shN, si->n);
 }
-DEV void ShadingToWorld(const mi_instance &in, TriShading *ts) {
-    const float *m = in.i2w, *mInv = in.w2i;
+DEV void InteractionToWorld(const mi_instance &in, SurfaceInteraction *si) { InteractionToWorld(in.i2w, in.w2i, si); }
+DEV void ShadingToWorld(const float *m, const float *mInv, TriShading *ts) {
     ts->dpdv = XfVector(m, ts->dpdv);
     ts->shDpdv = XfVector(m, ts->shDpdv);
     ts->dndu = XfNormal(mInv, ts->dndu);
@@ -2061,7 +2089,9 @@ DEV void StoreSpectrumLines(SpectrumTile &t, const Pool &pool, int spectrum, uin
 // k_shade's own note beside the flags it is forming: the vertex has a dark MIS ray, which goes to the MIS queue but not into
 // the state word (StateWord keeps FLAG_BITS bits).
 constexpr int SHADE_DARK_RAY = 1 << FLAG_BITS;
-template <int NL, unsigned TM, bool LENS = false>
+// MOTION (TM_INSTANCES instances only): the scene has moving instances -- a hit inside one is carried by the two matrices of
+// Interpolate(ray time), held as values. The MOTION = false instances read the instance's record in place, as before.
+template <int NL, unsigned TM, bool LENS = false, bool MOTION = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT_SHADE_WAVES_PER_EU, 8))) k_shade(DScene s, Pool pool, DevCounters *ctr, unsigned classes) {
     // the grid covers the queues of `classes` back to back, each padded to whole blocks
     unsigned blk = blockIdx.x, count = 0;
@@ -2111,14 +2141,26 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
         // world by InstanceToWorld (TransformedPrimitive::Intersect, primitive.cpp:78-92)
         int inst = -1;
         V3 roS = ro, rdS = rd;   // the ray in the space the hit shape was intersected in
+        float instW2I[MOTION ? 16 : 1], instI2W[MOTION ? 16 : 1];
         if constexpr ((TM & TM_INSTANCES) != 0) {
             if (needIsect) inst = pool.I(I_HITINST, slot);
-            if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
+            if constexpr (MOTION) {
+                if (inst >= 0) {   // (both matrices of Interpolate(ray.time), kept for the shading frame below)
+                    const float time = PathTime(s, pool, slot);
+                    InstanceW2I(s, inst, time, instW2I);
+                    InstanceI2W(s, inst, time, instI2W);
+                    const Ray ir = XfRay(instW2I, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d;
+                }
+            } else if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
         }
         if (needIsect) { const float4 hr = pool.R(R_HIT, slot); HitInteraction<DISKS>(s, prim, roS, rdS, hr.y, hr.z, hr.w, &isect); }
         SurfaceInteraction isectObj;
         if constexpr ((TM & TM_INSTANCES) != 0) {
-            if (inst >= 0) { isectObj = isect; InteractionToWorld(s.instances[inst], &isect); }
+            if (inst >= 0) {
+                isectObj = isect;
+                if constexpr (MOTION) InteractionToWorld(instI2W, instW2I, &isect);
+                else InteractionToWorld(s.instances[inst], &isect);
+            }
         }
         // emitted light at the vertex, path.cpp:91-101
         if ((bounces == 0 || (flags & F_SPECULAR)) && found) {
@@ -2201,7 +2243,10 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                     else
                         haveUV = SphereTexCoords(s.spheres[~shape], roS, rdS, &u, &v, &tsh);
                     if constexpr ((TM & TM_INSTANCES) != 0) {
-                        if (inst >= 0) ShadingToWorld(s.instances[inst], &tsh);
+                        if (inst >= 0) {
+                            if constexpr (MOTION) ShadingToWorld(instI2W, instW2I, &tsh);
+                            else ShadingToWorld(s.instances[inst].i2w, s.instances[inst].w2i, &tsh);
+                        }
                     }
                 }
                 if (haveUV) {
@@ -3052,17 +3097,22 @@ __global__ void k_math_probe(int op, uint32_t n, const float *x, const float *y,
 }
 
 // ------------------------------------------------------------------ standalone traversal (mi_pt_trace)
-__global__ void __launch_bounds__(BLOCK) k_trace(DScene s, const float *rays, uint32_t n, int anyHit, float *hits) {
+// stride: floats per ray -- 7, or 8 with the ray's time behind tMax (mi_pt_trace_timed)
+__global__ void __launch_bounds__(BLOCK) k_trace(DScene s, const float *rays, uint32_t n, int anyHit, float *hits, int stride) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    const float *r = rays + (size_t)i * 7;
+    const float *r = rays + (size_t)i * stride;
     V3 ro(r[0], r[1], r[2]), rd(r[3], r[4], r[5]);
     unsigned nodes = 0, tris = 0;
     Hit h;
     h.prim = -1; h.t = 0; h.b0 = h.b1 = h.b2 = 0;
     int prim;
-    if (anyHit) prim = Traverse<true, true>(s, ro, rd, r[6], &h, nodes, tris) ? 0 : -1;
-    else prim = Traverse<false, true>(s, ro, rd, r[6], &h, nodes, tris) ? h.prim : -1;
+    const float time = stride == 8 ? r[7] : s.camera.shutter_open;   // (a ray without a time of its own: the shutter-open time)
+    if (s.motions) {   // (uniform)
+        if (anyHit) prim = Traverse<true, true, true>(s, ro, rd, r[6], &h, nodes, tris, time) ? 0 : -1;
+        else prim = Traverse<false, true, true>(s, ro, rd, r[6], &h, nodes, tris, time) ? h.prim : -1;
+    } else if (anyHit) prim = Traverse<true, true>(s, ro, rd, r[6], &h, nodes, tris, time) ? 0 : -1;
+    else prim = Traverse<false, true>(s, ro, rd, r[6], &h, nodes, tris, time) ? h.prim : -1;
     float *o = hits + (size_t)i * 4;
     o[0] = __int_as_float(prim);
     o[1] = (prim >= 0 && !anyHit) ? h.t : 0.f;
@@ -3074,7 +3124,9 @@ __global__ void __launch_bounds__(BLOCK) k_trace(DScene s, const float *rays, ui
 // Loads ray i into slot i of the pool exactly as k_generate / k_shade leave a path ray (mode 0), an NEE shadow ray (1) or a
 // BSDF-sampled MIS ray (2), and lists it in that mode's work list. The shadow mode's flags make k_resolve_shadow's commit
 // readable without a spectrum: the candidate line "holds L + the light sample" (F_CAND), so an unoccluded ray flips F_L_IN_B and clears F_L_ZERO.
-__global__ void __launch_bounds__(BLOCK) k_trace_load(Pool pool, DevCounters *ctr, const float *rays, uint32_t n, int mode) {
+// timePlane >= 0: the scene has moving instances; a ray of 8 floats brings its time, the others take the given one (the
+// shutter-open time).
+__global__ void __launch_bounds__(BLOCK) k_trace_load(Pool pool, DevCounters *ctr, const float *rays, uint32_t n, int mode, int timePlane, float time, int stride) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i == 0) {
         if (mode == 0) { ctr->primCount.v = n; ctr->contCount.v = 0; }
@@ -3084,7 +3136,7 @@ __global__ void __launch_bounds__(BLOCK) k_trace_load(Pool pool, DevCounters *ct
     if (i >= pool.n) return;
     int flags = 0;
     if (i < n) {
-        const float *r = rays + (size_t)i * 7;
+        const float *r = rays + (size_t)i * stride;
         if (mode == 0) {
             pool.R(R_RAY0, i) = make_float4(r[0], r[1], r[2], r[6]);
             pool.R(R_RAY1, i) = make_float4(r[3], r[4], r[5], 1.f);
@@ -3097,6 +3149,7 @@ __global__ void __launch_bounds__(BLOCK) k_trace_load(Pool pool, DevCounters *ct
             (mode == 1 ? pool.shadowQ : pool.misQ)[i] = i;
             flags = mode == 1 ? (F_ALIVE | F_NEE | F_SHADOW | F_L_ZERO | F_CAND | F_NEE_NZ) : (F_ALIVE | F_NEE | F_MIS);
         }
+        if (timePlane >= 0) pool.F(timePlane, i) = stride == 8 ? r[7] : time;
         pool.I(I_HITPRIM, i) = -2;   // (every ray must be answered: k_trav overwrites this)
         if (mode == 1) pool.shadowQ[pool.n + i] = 0xfffffffeu;   // (... a shadow or MIS ray's answer lies beside its queue entry)
         if (mode >= 2) { pool.misQ[pool.n + 2 * (size_t)i] = mode == 3 ? 0xfffffffdu : 0xfffffffeu; pool.misQ[pool.n + 2 * (size_t)i + 1] = 0u; }
@@ -3127,7 +3180,7 @@ __global__ void __launch_bounds__(BLOCK) k_trace_raw(Pool pool, uint32_t n, int 
 // The committed answer. Mode 0: the planes as k_resolve_extend / k_resolve_overflow left them. Mode 1: k_resolve_shadow's
 // verdict (see k_trace_load). Mode 2: k_resolve_mis consumes its hit in place (ResolveMisSlot), so its quadric step
 // (MisClosestHit) is run here.
-template <bool INST>
+template <bool INST, bool MOTION = false>
 __global__ void __launch_bounds__(BLOCK) k_trace_read(DScene s, Pool pool, uint32_t n, int mode, float *hits, float *extra) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -3143,7 +3196,7 @@ __global__ void __launch_bounds__(BLOCK) k_trace_read(DScene s, Pool pool, uint3
         bool haveRay = false;
         LoadMisRay(pool, i, ro, rd, h, haveRay);   // (at once: the hit is recorded here whether it has quadrics or not)
         const int npend = (int)pool.misQ[pool.n + 2 * (size_t)i + 1];
-        const bool found = (npend & PEND_OVERFLOW) ? MisClosestHit<INST, true>(s, pool, i, npend, ro, rd, h, haveRay)
+        const bool found = (npend & PEND_OVERFLOW) ? MisClosestHit<INST, true, MOTION>(s, pool, i, npend, ro, rd, h, haveRay)
                                                    : MisClosestHit<INST, false>(s, pool, i, npend, ro, rd, h, haveRay);
         prim = found ? h.prim : -1;
         hr = HitRecord(h);
@@ -3187,7 +3240,7 @@ DEV float4 MetadataQuad(const float4 &v, int c) {
     if (c == 0) return v;
     return make_float4(v.w, v.w, v.w, c == NQ - 1 ? 0.f : v.w);
 }
-template <bool INST>
+template <bool INST, bool MOTION = false>
 __global__ void __launch_bounds__(BLOCK) k_commit_metadata(DScene s, Pool pool, const mi_prim_meta *__restrict__ primMeta, int strategy) {
     const uint32_t slot = blockIdx.x * BLOCK + threadIdx.x;
     const int word = slot < pool.n ? pool.I(I_FLAGS, slot) : 0;
@@ -3200,7 +3253,7 @@ __global__ void __launch_bounds__(BLOCK) k_commit_metadata(DScene s, Pool pool, 
                 unsigned id = strategy == MI_METADATA_MATERIAL ? primMeta[prim].material_id : primMeta[prim].instance_id;
                 if (INST && strategy == MI_METADATA_MESH) {
                     const int inst = pool.I(I_HITINST, slot);
-                    if (inst >= 0) id = (unsigned)inst + 1u;
+                    if (inst >= 0) id = InstanceIdOf(s.instances[inst], inst);
                 }
                 const float v = (float)id;   // L = Spectrum(isect.materialId) / Spectrum(isect.instanceId), metadata.cpp:71-75
                 val = make_float4(v, v, v, v);
@@ -3209,13 +3262,24 @@ __global__ void __launch_bounds__(BLOCK) k_commit_metadata(DScene s, Pool pool, 
                 const V3 ro(ray0.x, ray0.y, ray0.z), rd(ray1.x, ray1.y, ray1.z);
                 int inst = -1;
                 V3 roS = ro, rdS = rd;   // the ray in the space the hit shape was intersected in (as in k_shade)
+                float instW2I[MOTION ? 16 : 1], instI2W[MOTION ? 16 : 1];
                 if (INST) {
                     inst = pool.I(I_HITINST, slot);
-                    if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
+                    if constexpr (MOTION) {
+                        if (inst >= 0) {
+                            const float time = PathTime(s, pool, slot);
+                            InstanceW2I(s, inst, time, instW2I);
+                            InstanceI2W(s, inst, time, instI2W);
+                            const Ray ir = XfRay(instW2I, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d;
+                        }
+                    } else if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
                 }
                 SurfaceInteraction isect;
                 HitInteraction(s, prim, roS, rdS, hr.y, hr.z, hr.w, &isect);
-                if (INST) { if (inst >= 0) InteractionToWorld(s.instances[inst], &isect); }
+                if (INST) {
+                    if constexpr (MOTION) { if (inst >= 0) InteractionToWorld(instI2W, instW2I, &isect); }
+                    else if (inst >= 0) InteractionToWorld(s.instances[inst], &isect);
+                }
                 if (strategy == MI_METADATA_DEPTH) {
                     const V3 toIntersect = isect.p - ro;   // metadata.cpp:68-69
                     const float v = toIntersect.Length();
@@ -3280,6 +3344,11 @@ constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_
     X(2, MI_MAX_BXDFS, TM_FULL) \
     X(2, 2, TM_ALL) \
     X(1, MI_MAX_BXDFS, TM_ALL)
+// The MOTION = true twins of the instances that hold the instance code (TM_INSTANCES), each with its LENS twin: a launch takes
+// them where the scene has moving instances (LaunchShade). Not part of the plan's table either.
+#define MIPT_SHADE_MOTION_INSTANCES(X) \
+    X(2, 2, TM_ALL) \
+    X(1, MI_MAX_BXDFS, TM_ALL)
 #ifdef MIPT_PART   // each part defines its own instances and declares the others
 #if MIPT_PART == 1
 #define MIPT_SHADE_IN_1
@@ -3300,6 +3369,9 @@ constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_
 MIPT_SHADE_INSTANCES(MIPT_SHADE_INSTANCE)
 #define MIPT_SHADE_LENS_INSTANCE(P_, NL_, TM_) MIPT_SHADE_IN_##P_ template __global__ void k_shade<NL_, (TM_), true>(DScene, Pool, DevCounters *, unsigned);
 MIPT_SHADE_LENS_INSTANCES(MIPT_SHADE_LENS_INSTANCE)
+#define MIPT_SHADE_MOTION_INSTANCE(P_, NL_, TM_) MIPT_SHADE_IN_##P_ template __global__ void k_shade<NL_, (TM_), false, true>(DScene, Pool, DevCounters *, unsigned); \
+                                                 MIPT_SHADE_IN_##P_ template __global__ void k_shade<NL_, (TM_), true, true>(DScene, Pool, DevCounters *, unsigned);
+MIPT_SHADE_MOTION_INSTANCES(MIPT_SHADE_MOTION_INSTANCE)
 #endif
 
 }  // namespace dptk
@@ -3347,13 +3419,19 @@ struct ShadeInstance {
     unsigned tm;
     void (*kernel)(DScene, Pool, DevCounters *, unsigned);
     void (*kernelLens)(DScene, Pool, DevCounters *, unsigned);   // the LENS twin of an instance that reads image textures, or null
+    void (*kernelMotion)(DScene, Pool, DevCounters *, unsigned), (*kernelMotionLens)(DScene, Pool, DevCounters *, unsigned);   // the MOTION twins of an instance with the instance code, or null
 };
+template <int NL, unsigned TM, bool LENS>
+constexpr auto MotionShadeKernel() -> void (*)(DScene, Pool, DevCounters *, unsigned) {
+    if constexpr ((TM & TM_INSTANCES) != 0) return k_shade<NL, TM, LENS, true>;
+    else return nullptr;
+}
 template <int NL, unsigned TM>
 constexpr auto LensShadeKernel() -> void (*)(DScene, Pool, DevCounters *, unsigned) {
     if constexpr ((TM & TM_TEXTURED) != 0) return k_shade<NL, TM, true>;
     else return nullptr;
 }
-#define MIPT_SHADE_ENTRY(P_, NL_, TM_) {NL_, (TM_), k_shade<NL_, (TM_)>, LensShadeKernel<NL_, (TM_)>()},
+#define MIPT_SHADE_ENTRY(P_, NL_, TM_) {NL_, (TM_), k_shade<NL_, (TM_)>, LensShadeKernel<NL_, (TM_)>(), MotionShadeKernel<NL_, (TM_), false>(), MotionShadeKernel<NL_, (TM_), true>()},
 static const ShadeInstance kShadeInstances[] = {MIPT_SHADE_INSTANCES(MIPT_SHADE_ENTRY)};
 #undef MIPT_SHADE_ENTRY
 constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstances[0]);
@@ -3477,7 +3555,9 @@ int Alloc(mi_pt *pt, size_t bytes, T **dst, const char *what) {
 // Spectral quad planes of a path slot: spectralpath keeps one set more, the stitched spectrum of the camera sample (Q_LCA).
 int QuadPlanes(const DScene &s) { return Q_COUNT + (s.nBands > 1 ? NQ : 0); }
 // Float planes of a path slot: a realistic camera keeps the ray weight (P_WEIGHT).
-int FloatPlanes(const DScene &s) { return P_COUNT + (s.cameraType == MI_CAMERA_REALISTIC ? 1 + (s.lensDiff ? N_LENSDIFF : 0) : 0); }
+int FloatPlanes(const DScene &s) { return P_COUNT + (s.cameraType == MI_CAMERA_REALISTIC ? 1 + (s.lensDiff ? N_LENSDIFF : 0) : 0) + (s.motions ? 1 : 0); }
+// (the time plane of a scene with moving instances: the last one)
+int TimePlaneOf(const DScene &s) { return s.motions ? FloatPlanes(s) - 1 : 0; }
 // Samples per pixel of one pass.
 long long PassSpp(const mi_pt *pt, const mi_render_params *rp) { return rp->spp_override > 0 ? rp->spp_override : pt->spp; }
 
@@ -3554,6 +3634,9 @@ int CheckSceneDesc(const mi_scene_desc *d) {
         if (p.shape >= 0 ? (uint32_t)p.shape >= d->n_tris : (uint64_t)(uint32_t)(~p.shape) >= (uint64_t)d->n_spheres + d->n_disks) { g_err = "primitive shape index out of range"; return MI_ERR_INVALID; }
         if (p.material >= (int)d->n_materials || p.area_light >= (int)d->n_lights) { g_err = "primitive material/light index out of range"; return MI_ERR_INVALID; }
     }
+    if ((d->n_instances && !d->instances) || (d->n_motions && !d->motions)) { g_err = "instance or motion array missing"; return MI_ERR_INVALID; }
+    for (uint32_t k = 0; k < d->n_instances; ++k)   // (every instance, referenced by a primitive or not)
+        if (d->instances[k].motion > d->n_motions) { g_err = "instance motion index out of range"; return MI_ERR_INVALID; }
     if ((d->n_spheres && !d->spheres) || (d->n_disks && !d->disks) || (uint64_t)d->n_spheres + d->n_disks > 0x7fffffffull) { g_err = "quadric arrays missing or too large"; return MI_ERR_INVALID; }
     for (uint32_t i = 0; i < d->n_disks; ++i)
         if (d->disks[i].kind != MI_QUADRIC_DISK) { g_err = "mi_disk.kind: only disks (0) are built"; return MI_ERR_UNSUPPORTED; }
@@ -4135,6 +4218,7 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     s.camera = d->camera;
     s.cameraType = d->camera_type;
     s.lens = nullptr;   // (UploadScene: the device copy)
+    s.motions = nullptr; s.timePlane = 0;   // (UploadScene, when an instance moves)
     s.lensDiff = 0;
     if (d->camera_type == MI_CAMERA_REALISTIC)
         for (uint32_t i = 0; i < d->n_materials; ++i) if (d->materials[i].textured) s.lensDiff = 1;
@@ -4185,6 +4269,7 @@ int UploadScene(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     up(h.primTri.data(), h.primTri.size(), s.primTri);
     up(d->prims, d->n_prims, s.prims);
     if (d->n_instances) up(d->instances, d->n_instances, s.instances);
+    if (d->n_motions) { up(d->motions, d->n_motions, s.motions); s.timePlane = TimePlaneOf(s); }
     up(d->tri_indices, (size_t)d->n_tris * 3, s.triIndices);
     up(d->tri_mesh, d->n_tris, s.triMesh);
     up(d->P, (size_t)d->n_verts * 3, s.P);
@@ -4318,7 +4403,8 @@ using SceneKernel = void (*)(DScene, Pool, DevCounters *);
 // (BuildBvhTables) and never MODE 3 (misAny is 0 for them): three instances serve them.
 template <int MODE>
 SceneKernel TravKernel(const mi_pt *pt) {
-    if (pt->hasInstances) return k_trav<MODE >= 3 ? 2 : MODE, true, 4, true>;   // (never asked for MODE 3 or 4)
+    if (pt->hasInstances)   // (never asked for MODE 3 or 4)
+        return pt->scene.motions ? k_trav<MODE >= 3 ? 2 : MODE, true, 4, true, true> : k_trav<MODE >= 3 ? 2 : MODE, true, 4, true>;
     const bool w4 = pt->scene.bvhWidth == 4;
     if (pt->hasAlphaMasks) return w4 ? k_trav<MODE, true, 4> : k_trav<MODE, true, 2>;
     return w4 ? k_trav<MODE, false, 4> : k_trav<MODE, false, 2>;
@@ -4434,12 +4520,12 @@ void LaunchResolve(mi_pt *pt, SubRenderer &sub, int mode, dim3 grid) {
     if (mode != 0) grid = QueueGrid(pt, pt->resolveBlocksPerCU[mode], grid.x);   // (k_resolve_extend takes the pool's slots, not a queue)
     hipLaunchKernelGGL(kResolve[mode][inst ? 1 : 0], grid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr);
     if (pt->hasQuadrics || (mode == 2 && pt->scene.misAny))
-        hipLaunchKernelGGL((inst ? k_resolve_overflow<true> : k_resolve_overflow<false>), dim3(OVERFLOW_GRID), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, mode);
+        hipLaunchKernelGGL((inst ? (pt->scene.motions ? k_resolve_overflow<true, true> : k_resolve_overflow<true>) : k_resolve_overflow<false>), dim3(OVERFLOW_GRID), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, mode);
 }
 
 // The last stage of a metadata pass (instead of LaunchShade and the shadow and MIS stages): every slot, one per thread.
 void LaunchMetadataCommit(mi_pt *pt, SubRenderer &sub, dim3 grid) {
-    hipLaunchKernelGGL((pt->hasInstances ? k_commit_metadata<true> : k_commit_metadata<false>), grid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool,
+    hipLaunchKernelGGL((pt->hasInstances ? (pt->scene.motions ? k_commit_metadata<true, true> : k_commit_metadata<true>) : k_commit_metadata<false>), grid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool,
                        pt->primMeta, pt->metaStrategy);
 }
 
@@ -4480,7 +4566,9 @@ int LaunchShade(mi_pt *pt, SubRenderer &sub, dim3 grid) {
         const unsigned long long blocks = pt->shadeGridPool ? (unsigned long long)grid.x + MAX_CLASSES : ShadeGridBlocks(counts, pt->shadeClasses[i]);
         if (blocks == 0) continue;
         const bool lens = pt->scene.lensDiff && kShadeInstances[i].kernelLens;   // (a realistic camera in front of textures: the twin that loads the stored differentials)
-        hipLaunchKernelGGL(lens ? kShadeInstances[i].kernelLens : kShadeInstances[i].kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, pt->shadeClasses[i]);
+        const bool motion = pt->scene.motions && kShadeInstances[i].kernelMotion;   // (moving instances: the twin that interpolates)
+        hipLaunchKernelGGL(motion ? (lens ? kShadeInstances[i].kernelMotionLens : kShadeInstances[i].kernelMotion)
+                                  : (lens ? kShadeInstances[i].kernelLens : kShadeInstances[i].kernel), dim3((unsigned)blocks), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, pt->shadeClasses[i]);
         ++sub.shadeLaunches;
         sub.shadeBlocks += blocks;
     }
@@ -5122,20 +5210,23 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
     return MI_OK;
 }
 
-int mi_pt_trace(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits) {
+static int TraceRays(mi_pt *pt, const float *rays, int stride, uint32_t n, int any_hit, float *hits) {
     if (!pt || !rays || !hits) { g_err = "null argument"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
     HIPCHK(hipSetDevice(pt->device));
     DevBuf dr, dh;
-    HIPCHK(dr.alloc((size_t)n * 7 * sizeof(float)));
+    HIPCHK(dr.alloc((size_t)n * stride * sizeof(float)));
     HIPCHK(dh.alloc((size_t)n * 4 * sizeof(float)));
-    HIPCHK(hipMemcpy(dr.p, rays, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_trace, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, dr.as<float>(), n, any_hit, dh.as<float>());
+    HIPCHK(hipMemcpy(dr.p, rays, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_trace, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, dr.as<float>(), n, any_hit, dh.as<float>(), stride);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(hits, dh.p, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return MI_OK;
 }
+
+int mi_pt_trace(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits) { return TraceRays(pt, rays, 7, n, any_hit, hits); }
+int mi_pt_trace_timed(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits) { return TraceRays(pt, rays, 8, n, any_hit, hits); }
 
 int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, const float *y, float *out) {
     if (!x || !y || !out || op < 0 || op > 5) { g_err = "mi_pt_math_probe: bad argument"; return MI_ERR_INVALID; }
@@ -5156,7 +5247,7 @@ int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, con
     return MI_OK;
 }
 
-int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra) {
+static int TraceWavefront(mi_pt *pt, const float *rays, int stride, uint32_t n, int mode, float *hits, float *extra) {
     if (!pt || !rays || !hits) { g_err = "null argument"; return MI_ERR_INVALID; }
     if (mode < 0 || mode > 3) { g_err = "mi_pt_trace_wavefront: mode must be 0 (path rays), 1 (shadow rays), 2 (MIS rays) or 3 (MIS rays as visibility queries)"; return MI_ERR_INVALID; }
     if (mode == 3 && !pt->scene.misAny) { g_err = "mi_pt_trace_wavefront: mode 3 needs a scene without instances and without an alpha mask on an emitter's mesh (others keep the closest-hit form of the MIS rays)"; return MI_ERR_INVALID; }
@@ -5165,9 +5256,9 @@ int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, fl
     // the kernels fix what the render fixes: a shadow ray ends at 1 - ShadowEpsilon (Interaction::SpawnRayTo), a BSDF-sampled
     // ray never ends (SpawnRay)
     for (uint32_t i = 0; i < n && mode == 3; ++i)
-        if (!(rays[(size_t)i * 7 + 6] > 0)) { g_err = "mi_pt_trace_wavefront: mode 3 rays carry the end of the emitter's span, tMax > 0"; return MI_ERR_INVALID; }
+        if (!(rays[(size_t)i * stride + 6] > 0)) { g_err = "mi_pt_trace_wavefront: mode 3 rays carry the end of the emitter's span, tMax > 0"; return MI_ERR_INVALID; }
     for (uint32_t i = 0; i < n && (mode == 1 || mode == 2); ++i) {
-        const float tMax = rays[(size_t)i * 7 + 6];
+        const float tMax = rays[(size_t)i * stride + 6];
         if (mode == 1 ? tMax != 1 - kShadowEpsilon : !std::isinf(tMax) || tMax < 0) {
             g_err = mode == 1 ? "mi_pt_trace_wavefront: shadow rays (mode 1) carry tMax = 1 - 0.0001f" : "mi_pt_trace_wavefront: MIS rays (mode 2) carry tMax = +infinity";
             return MI_ERR_INVALID;
@@ -5183,25 +5274,27 @@ int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, fl
     if (rc != MI_OK) return rc;
     struct PoolGuard { SubRenderer &sub; ~PoolGuard() { FreePool(sub.pool); sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0; } } guard{sub};   // the next render sizes its own
     DevBuf dr, dh, dx;
-    HIPCHK(dr.alloc((size_t)n * 7 * sizeof(float)));
+    HIPCHK(dr.alloc((size_t)n * stride * sizeof(float)));
     HIPCHK(dh.alloc((size_t)n * 4 * sizeof(float)));
     HIPCHK(dx.alloc((size_t)n * 4 * sizeof(float)));
-    HIPCHK(hipMemcpy(dr.p, rays, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dr.p, rays, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(sub.ctr, 0, sizeof(DevCounters), st));
     const dim3 grid(poolN / BLOCK), block(BLOCK);
     const dim3 chunkGrid(grid.x / SLOT_CHUNKS);
     const dim3 travGrid(std::min<unsigned>(grid.x, (unsigned)pt->numCUs * TRAV_BLOCKS_PER_CU));
-    hipLaunchKernelGGL(k_trace_load, grid, block, 0, st, sub.pool, sub.ctr, dr.as<float>(), n, mode);
+    hipLaunchKernelGGL(k_trace_load, grid, block, 0, st, sub.pool, sub.ctr, dr.as<float>(), n, mode, s.motions ? s.timePlane : -1, s.camera.shutter_open, stride);
     LaunchTraversal(pt, sub, mode, travGrid, true);   // (mode 2: the closest-hit kernel, whose records this call returns)
     hipLaunchKernelGGL(k_trace_raw, grid, block, 0, st, sub.pool, n, mode, dx.as<float>());
     if (mode < 2) LaunchResolve(pt, sub, mode, mode == 0 ? chunkGrid : grid);   // (modes 2 and 3: k_trace_read resolves the hit)
-    hipLaunchKernelGGL((pt->hasInstances ? k_trace_read<true> : k_trace_read<false>), grid, block, 0, st, s, sub.pool, n, mode, dh.as<float>(), dx.as<float>());
+    hipLaunchKernelGGL((pt->hasInstances ? (s.motions ? k_trace_read<true, true> : k_trace_read<true>) : k_trace_read<false>), grid, block, 0, st, s, sub.pool, n, mode, dh.as<float>(), dx.as<float>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(hits, dh.p, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
     if (extra) HIPCHK(hipMemcpy(extra, dx.p, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return MI_OK;
 }
+int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra) { return TraceWavefront(pt, rays, 7, n, mode, hits, extra); }
+int mi_pt_trace_wavefront_timed(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra) { return TraceWavefront(pt, rays, 8, n, mode, hits, extra); }
 
 void mi_pt_destroy(mi_pt *pt) {
     if (!pt) return;

@@ -161,11 +161,15 @@ struct Api {
     struct RecordedShape { std::string name; ParamSet params; Transform ctm; GraphicsState gs; uint32_t materialId; };
     std::map<std::string, std::vector<RecordedShape>> instances;
     std::vector<RecordedShape> *currentInstance = nullptr;
-    struct ObjectDef { std::vector<PendingPrim> prims; Bounds3 bounds; bool created = false; int root = -1; };
+    // wrapper: the primitives of one moving Shape (api.cpp:1389-1428), behind BVHAccel's default parameters
+    struct ObjectDef { std::vector<PendingPrim> prims; Bounds3 bounds; bool created = false; int root = -1; bool wrapper = false; };
     std::map<std::string, ObjectDef> objectDefs;
     std::vector<std::string> objectOrder;                 // objects in the order they were first instanced
-    struct InstanceRec { std::string object; Transform i2w; };
+    // moving: i2w / i2wEnd are the members of an AnimatedTransform over the TransformTimes (MIPT_OBJECT_MOTION=1)
+    struct InstanceRec { std::string object; Transform i2w; uint32_t instanceId = 0; bool moving = false; Transform i2wEnd; };
     std::vector<InstanceRec> instanceRecs;
+    bool objectMotion = false;   // MIPT_OBJECT_MOTION=1: shapes and instances under an animated CTM become moving primitives
+    int nMovingShapes = 0;
     std::vector<std::string> instanceNames;   // one per ObjectInstance call that created something, in file order
     bool expandInstances = false;
     // Material::materialId (material.h:54): every Material object the reference constructs takes the next number of a counter
@@ -203,6 +207,7 @@ struct Api {
 
     Api(HostScene *s, const LoadOverrides &o) : scene(s), ov(o) {
         if (const char *e = getenv("MIPT_INSTANCES")) expandInstances = std::string(e) == "expand";
+        if (const char *e = getenv("MIPT_OBJECT_MOTION")) objectMotion = std::string(e) == "1";
         // default material: matte with default params (GraphicsState ctor, api.cpp:214-222)
         ParamSet empty;
         gs.currentMaterial = std::make_shared<MaterialInstance>();
@@ -391,7 +396,11 @@ struct Api {
         if (state != World) { Err("Scene description must be inside world block; \"Shape\" not allowed. Ignoring."); return; }
         // (the reference wraps such a shape in a TransformedPrimitive with an AnimatedTransform, api.cpp:1363-1430: moving
         // primitives need per-ray times in traversal and are outside this path's scope)
-        if (CtmIsAnimated() && !recorded) Err("Shape \"" + name + "\": animated transforms of shapes are outside the hot-path scope; using the start transform");
+        if (CtmIsAnimated() && !recorded) {
+            if (objectMotion && !currentInstance) { MovingShape(name, params); return; }
+            // (without the switch; and a moving shape inside an object: a TransformedPrimitive inside an instance)
+            Err("Shape \"" + name + "\": animated transforms of shapes are outside the hot-path scope; using the start transform");
+        }
         if (currentInstance) {   // api.cpp:1431-1435
             if (gs.areaLight != "") Warn("Area lights not supported with object instancing");
             // the reference creates the shape and its material here (GetMaterialForShape, api.cpp:1378), so the id is taken here
@@ -571,10 +580,11 @@ struct Api {
         auto it = instances.find(name);
         if (it == instances.end()) { Err("Unable to find instance named \"" + name + "\""); return; }
         // (api.cpp:1594-1610 gives the TransformedPrimitive an AnimatedTransform; see Shape)
-        if (CtmIsAnimated()) Err("ObjectInstance \"" + name + "\": animated transforms of instances are outside the hot-path scope; using the start transform");
+        const bool moving = objectMotion && CtmIsAnimated();   // (a moving instance is never expanded)
+        if (CtmIsAnimated() && !moving) Err("ObjectInstance \"" + name + "\": animated transforms of instances are outside the hot-path scope; using the start transform");
         const Transform instanceToWorld = ctm;
         const GraphicsState saved = gs;
-        if (expandInstances) {
+        if (expandInstances && !moving) {
             if (it->second.empty()) return;   // api.cpp:1588
             instanceNames.push_back(name);
             expandingInstance = (uint32_t)instanceNames.size();   // the copies carry the instance id themselves
@@ -606,15 +616,83 @@ struct Api {
             for (const PendingPrim &pp : od.prims) od.bounds = Union(od.bounds, pp.bounds);
         }
         if (od.prims.empty()) return;   // api.cpp:1580
-        instanceRecs.push_back(InstanceRec{name, instanceToWorld});
         instanceNames.push_back(name);   // nObjectInstancesUsed / renderOptions->instanceNames, api.cpp:1589, 1614
+        AddInstance(name, od.bounds, instanceToWorld, moving ? ctmEnd : instanceToWorld, (uint32_t)instanceNames.size());
+    }
+    // The TransformedPrimitive of an object: static when the members are equal (AnimatedTransform::actuallyAnimated).
+    void AddInstance(const std::string &object, const Bounds3 &objectBounds, const Transform &start, const Transform &end, uint32_t instanceId) {
+        InstanceRec rec;
+        rec.object = object; rec.i2w = start; rec.instanceId = instanceId;
+        rec.moving = start != end; rec.i2wEnd = end;
+        instanceRecs.push_back(rec);
         PendingPrim pp;
         pp.shape = 0;
         pp.material = -1;
         pp.light = -1;
         pp.instance = (int)instanceRecs.size();
-        pp.bounds = instanceToWorld.Bounds(od.bounds);   // TransformedPrimitive::WorldBound: MotionBounds of a static transform
+        // TransformedPrimitive::WorldBound: MotionBounds, of a static transform its Bounds
+        pp.bounds = rec.moving ? MotionBounds(objectBounds, start, end) : start.Bounds(objectBounds);
         pending.push_back(pp);
+    }
+    // AnimatedTransform::MotionBounds (transform.cpp:1196-1208). Without rotation: the union of the two members' bounds, as
+    // the reference. With rotation the reference bounds every corner's path through the roots of its derivative
+    // (BoundPointMotion over ~650 lines of generated coefficients); here a bound of our own: the corner c is carried to
+    // T(dt) + R(dt) S(dt) c, S(dt) c lies on the segment from S0 c to S1 c and is no longer than the longer of the two, a
+    // rotation keeps that length and no coordinate of a vector exceeds its length -- so every coordinate stays within
+    // r = max |S_i c| of the translation's own segment. r is computed in double and widened by 1e-4 (the float rounding of
+    // the interpolated matrix and its quaternion's unit length: ~1e-6), and the two members' exact bounds (the boundary
+    // rules) are joined in. Looser than the reference's: the world tree may differ, the closest hit does not.
+    Bounds3 MotionBounds(const Bounds3 &b, const Transform &start, const Transform &end) {
+        const Bounds3 ends = Union(start.Bounds(b), end.Bounds(b));
+        const AnimatedDecomposition ad = DecomposePair(start, end);
+        const float *R0 = ad.d[0].R, *R1 = ad.d[1].R;
+        const bool hasRotation = (R0[0] * R1[0] + R0[1] * R1[1] + R0[2] * R1[2]) + R0[3] * R1[3] < 0.9995f;
+        if (!hasRotation) return ends;
+        double r = 0;
+        for (int corner = 0; corner < 8; ++corner) {
+            const double c[3] = {(corner & 1) ? b.pMax.x : b.pMin.x, (corner & 2) ? b.pMax.y : b.pMin.y, (corner & 4) ? b.pMax.z : b.pMin.z};
+            for (int i = 0; i < 2; ++i) {
+                double l2 = 0;
+                for (int row = 0; row < 3; ++row) {
+                    const double v = ad.d[i].S[3 * row] * c[0] + ad.d[i].S[3 * row + 1] * c[1] + ad.d[i].S[3 * row + 2] * c[2];
+                    l2 += v * v;
+                }
+                r = std::max(r, std::sqrt(l2));
+            }
+        }
+        const float rf = std::nextafter((float)(r * 1.0001), std::numeric_limits<float>::infinity());
+        Bounds3 path;
+        for (int a = 0; a < 3; ++a) {
+            const float lo = std::min(ad.d[0].T[a], ad.d[1].T[a]) - rf, hi = std::max(ad.d[0].T[a], ad.d[1].T[a]) + rf;
+            (a == 0 ? path.pMin.x : a == 1 ? path.pMin.y : path.pMin.z) = std::nextafter(lo, -std::numeric_limits<float>::infinity());
+            (a == 0 ? path.pMax.x : a == 1 ? path.pMax.y : path.pMax.z) = std::nextafter(hi, std::numeric_limits<float>::infinity());
+        }
+        return Union(ends, path);
+    }
+    // A Shape under an animated CTM outside ObjectBegin (api.cpp:1389-1428): its shapes are made with the identity transform
+    // and without an area light, and one TransformedPrimitive carries them -- here an instance of an object of its own, with
+    // instance id 0 and no entry in the instance names.
+    void MovingShape(const std::string &name, const ParamSet &params) {
+        if (gs.areaLight != "") Warn("Ignoring currently set area light when creating animated shape");
+        const Transform start = ctm, end = ctmEnd;
+        const std::string savedLight = gs.areaLight;
+        gs.areaLight = "";
+        ctm = ctmEnd = Transform();
+        std::vector<PendingPrim> world, made;
+        world.swap(pending);
+        Shape(name, params);
+        made.swap(pending);
+        pending.swap(world);
+        ctm = start; ctmEnd = end;
+        gs.areaLight = savedLight;
+        if (made.empty()) return;   // api.cpp:1399
+        const std::string object = std::string("\x01moving shape ") + std::to_string(nMovingShapes++);   // (no ObjectBegin can spell it)
+        ObjectDef &od = objectDefs[object];
+        od.created = true; od.wrapper = true;
+        od.prims.swap(made);
+        for (const PendingPrim &pp : od.prims) od.bounds = Union(od.bounds, pp.bounds);
+        objectOrder.push_back(object);
+        AddInstance(object, od.bounds, start, end, 0);
     }
 
     void LightSource(const std::string &name, const ParamSet &ps) {  // MakeLight, api.cpp:747-771
@@ -1135,6 +1213,8 @@ void Api::WorldEnd() {
             std::vector<mi_bvh_node> onodes;
             std::vector<int> oorder;
             int oi = 0, ol = 0;
+            if (od.wrapper) accelOk = BuildBVH(ob, 1, SplitMethod::SAH, &onodes, &oorder, &oi, &ol, &accelErr);   // std::make_shared<BVHAccel>(prims), api.cpp:1423
+            else
             accelOk = method == SplitMethod::HLBVH ? BuildHLBVH(ob, maxPrims, &onodes, &oorder, &oi, &ol, &accelErr)
                                                    : BuildBVH(ob, maxPrims, method, &onodes, &oorder, &oi, &ol, &accelErr);
             if (!accelOk) break;
@@ -1146,7 +1226,7 @@ void Api::WorldEnd() {
                 mi_prim p{};
                 p.shape = pp.shape; p.material = pp.material; p.area_light = pp.light; p.instance = 0;
                 scene->prims.push_back(p);
-                scene->primMeta.push_back(mi_prim_meta{pp.materialId, 0u});   // (the instance id is the hit's instance + 1)
+                scene->primMeta.push_back(mi_prim_meta{pp.materialId, 0u});   // (the instance id is the instance's own: mi_instance.instance_id)
             }
             od.root = baseNode;
             scene->stats.interiorNodes += oi;
@@ -1172,6 +1252,22 @@ void Api::WorldEnd() {
             std::memcpy(mi.i2w, ir.i2w.m.m, sizeof(float) * 16);
             std::memcpy(mi.w2i, ir.i2w.mInv.m, sizeof(float) * 16);
             mi.root = (uint32_t)objectDefs[ir.object].root;
+            mi.instance_id = ir.instanceId;
+            if (ir.moving) {   // AnimatedTransform(&InstanceToWorld[0], transformStartTime, &InstanceToWorld[1], transformEndTime)
+                mi_motion mo{};
+                std::memcpy(mo.i2w_end, ir.i2wEnd.m.m, sizeof(float) * 16);
+                std::memcpy(mo.w2i_end, ir.i2wEnd.mInv.m, sizeof(float) * 16);
+                const AnimatedDecomposition ad = DecomposePair(ir.i2w, ir.i2wEnd);
+                for (int i = 0; i < 2; ++i) {
+                    std::memcpy(mo.T[i], ad.d[i].T, sizeof(ad.d[i].T));
+                    std::memcpy(mo.R[i], ad.d[i].R, sizeof(ad.d[i].R));
+                    std::memcpy(mo.S[i], ad.d[i].S, sizeof(ad.d[i].S));
+                }
+                mo.transform_start = transformStart; mo.transform_end = transformEnd;
+                mo.has_rotation = (mo.R[0][0] * mo.R[1][0] + mo.R[0][1] * mo.R[1][1] + mo.R[0][2] * mo.R[1][2]) + mo.R[0][3] * mo.R[1][3] < 0.9995f ? 1 : 0;
+                scene->motions.push_back(mo);
+                mi.motion = (uint32_t)scene->motions.size();
+            }
             scene->instances.push_back(mi);
         }
     }
@@ -1724,6 +1820,7 @@ void HostScene::Finalize() {
     d.n_materials = (uint32_t)materials.size(); d.materials = materials.data();
     d.n_lights = (uint32_t)lights.size(); d.lights = lights.data();
     d.n_instances = (uint32_t)instances.size(); d.instances = instances.empty() ? nullptr : instances.data();
+    d.n_motions = (uint32_t)motions.size(); d.motions = motions.empty() ? nullptr : motions.data();
     d.prim_meta = primMeta.size() == prims.size() && !primMeta.empty() ? primMeta.data() : nullptr;
     d.lens = (d.camera_type == MI_CAMERA_REALISTIC && !lensStore.empty()) ? lensStore.data() : nullptr;
     d.light_distrib.func = ldFunc.empty() ? nullptr : ldFunc.data();

@@ -51,6 +51,7 @@ struct HostScene {
     std::vector<mi_texture> textures;
     std::vector<mi_lens> lensStore;       // Camera "realistic": the one record behind desc.lens (empty for a perspective camera)
     std::vector<mi_instance> instances;   // ObjectInstance as TransformedPrimitive (their BVHs follow the world's in `nodes`)
+    std::vector<mi_motion> motions;       // MIPT_OBJECT_MOTION=1: the AnimatedTransforms of the moving instances (mi_instance.motion)
     // Integrator "metadata": the ids of every primitive (parallel to prims) and the names behind them
     std::vector<mi_prim_meta> primMeta;
     std::vector<std::string> instanceNames;        // ObjectInstance calls in file order: instance id k + 1

@@ -70,6 +70,7 @@ void Fields(IO &io, S &s) {   // the same walk writes and reads
     io.Vec(s.primMeta); io.Strs(s.instanceNames); io.Strs(s.namedMaterialNames); io.Vec(s.namedMaterialIds);   // Integrator "metadata" (kind and strategy travel in desc)
     io.Vec(s.disks);       // Shape "disk" (ABI v14)
     io.Vec(s.lensStore);   // Camera "realistic" (the camera's type travels in desc)
+    io.Vec(s.motions);     // object motion (mi_instance.motion points into it)
 }
 
 }  // namespace
@@ -155,7 +156,7 @@ HostScene *LoadSceneCache(const std::string &path, std::string *err) {
     bool consistent = in.ok && s->nodes.size() == d.n_nodes && s->prims.size() == d.n_prims && s->triIndices.size() == 3ull * d.n_tris &&
                       s->triMesh.size() == d.n_tris && s->P.size() == 3ull * d.n_verts && s->N.size() == 3ull * d.n_verts &&
                       s->UV.size() == 2ull * d.n_verts && s->meshes.size() == d.n_meshes && s->spheres.size() == d.n_spheres && s->disks.size() == d.n_disks &&
-                      s->materials.size() == d.n_materials && s->lights.size() == d.n_lights && s->textures.size() == d.n_textures && s->instances.size() == d.n_instances &&
+                      s->materials.size() == d.n_materials && s->lights.size() == d.n_lights && s->textures.size() == d.n_textures && s->instances.size() == d.n_instances && s->motions.size() == d.n_motions &&
                       s->envStore.size() == d.n_envmaps && s->mipStore.size() == d.n_mipmaps && d.sampler.n_dims >= 0 && (int)s->primes.size() == d.sampler.n_dims &&
                       s->primeSums.size() == s->primes.size() && s->perms.size() == d.sampler.n_perms &&
                       (s->primMeta.empty() || s->primMeta.size() == d.n_prims) && s->namedMaterialIds.size() == s->namedMaterialNames.size() &&
