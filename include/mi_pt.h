@@ -267,10 +267,19 @@ typedef struct mi_texture {   /* spectrum textures: RGB pyramid; float textures:
     int32_t type;           /* mi_tex_type */
     int32_t aa_none;        /* checkerboard: "aamode" "none" (point sampled) instead of the closed-form box filter */
     float spec1[MI_NSPEC], spec2[MI_NSPEC]; /* checkerboard: "tex1" / "tex2" (constant spectra) */
+    int32_t octaves;        /* noise textures ("fbm", "wrinkled"): "octaves", 0..32 */
+    float omega;            /* noise textures ("fbm", "wrinkled"): "roughness" */
+    float w2t[16];          /* noise textures: IdentityMapping3D's WorldToTexture, row major */
 } mi_texture;
 /* MI_TEX_CHECKERBOARD: Checkerboard2DTexture<Spectrum> over UVMapping2D (src/textures/checkerboard.h:47-86): the value is
  * (1 - a) * spec1 + a * spec2 with a = 0 / 1 inside a check and the box-filtered area fraction across an edge. */
-typedef enum mi_tex_type { MI_TEX_IMAGEMAP = 0, MI_TEX_CHECKERBOARD = 1 } mi_tex_type;
+/* MI_TEX_FBM / MI_TEX_WRINKLED / MI_TEX_WINDY: the 3-D noise textures over IdentityMapping3D (src/textures/{fbm,wrinkled,windy}.h,
+ * src/core/texture.cpp:157-251), evaluated at the hit point with its world-space footprint dpdx / dpdy. No pyramid: mipmap is -1.
+ * A float one yields the value times post_scale, a spectrum one Spectrum(value). Not legal as a mesh's alpha_tex / shadow_alpha_tex.
+ * (spec1 / spec2 of such a record are ignored: the device copy carries 0 and 1 there, the compact form Spectrum(value) is expanded from.) */
+typedef enum mi_tex_type { MI_TEX_IMAGEMAP = 0, MI_TEX_CHECKERBOARD = 1, MI_TEX_FBM = 2, MI_TEX_WRINKLED = 3, MI_TEX_WINDY = 4 } mi_tex_type;
+#define MI_TEX_IS_NOISE(type) ((type) >= MI_TEX_FBM && (type) <= MI_TEX_WINDY)
+#define MI_NOISE_MAX_OCTAVES 32
 
 /* ---- lights */
 typedef enum mi_light_type {
@@ -645,6 +654,12 @@ int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, con
  * `tex` for n queries on the device. queries: 6 floats each (s, t, dsdx, dtdx, dsdy, dtdy) in texture space, i.e. after
  * the UVMapping2D; rgb: 3 floats per query. */
 int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *rgb);
+
+/* Parity tool for the noise textures: Texture<Float>::Evaluate(si) of noise texture `tex` (MI_TEX_FBM / WRINKLED / WINDY) for n
+ * queries, through the device functions k_shade calls. queries: 9 floats each -- the interaction's world p, dpdx, dpdy; out: 1
+ * float per query, the value times post_scale (no material clamp). MI_ERR_INVALID for any other texture type
+ * (mi_pt_texture_lookup answers for image textures). Host pointers. */
+int mi_pt_texture_probe(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *out);
 
 /* Parity tool for the quadrics (ABI v14): quadric `quadric` of the scene (the index space of mi_prim.shape: spheres, then
  * disks) on its own, through the device functions the traversal, shading and light-sampling code call. Host pointers.

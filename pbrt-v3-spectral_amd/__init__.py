@@ -89,7 +89,11 @@ class MipMap(C.Structure):
 class Texture(C.Structure):
     _fields_ = [("mipmap", C.c_int32), ("filter", C.c_int32), ("max_aniso", C.c_float),
                 ("su", C.c_float), ("sv", C.c_float), ("du", C.c_float), ("dv", C.c_float), ("post_scale", C.c_float),
-                ("type", C.c_int32), ("aa_none", C.c_int32), ("spec1", C.c_float * NSPEC), ("spec2", C.c_float * NSPEC)]
+                ("type", C.c_int32), ("aa_none", C.c_int32), ("spec1", C.c_float * NSPEC), ("spec2", C.c_float * NSPEC),
+                ("octaves", C.c_int32), ("omega", C.c_float), ("w2t", C.c_float * 16)]
+
+
+TEX_IMAGEMAP, TEX_CHECKERBOARD, TEX_FBM, TEX_WRINKLED, TEX_WINDY = range(5)   # mi_tex_type
 
 
 class Light(C.Structure):
@@ -247,6 +251,8 @@ def host_lib():
         lib.mi_scene_write_metadata_names.argtypes = [C.c_void_p, C.c_char_p]
         lib.mi_scene_free.argtypes = [C.c_void_p]
         lib.mi_scene_last_error.restype = C.c_char_p
+        lib.mi_noise_perm.argtypes = [C.POINTER(C.c_int32)]
+        lib.mi_noise_perm.restype = None
         lib.mi_film_write_dat.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float]
         lib.mi_film_read_dat.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float),
                                          C.c_uint64]
@@ -296,6 +302,7 @@ def hip_lib():
         lib.mi_pt_trace_wavefront_timed.argtypes = lib.mi_pt_trace_wavefront.argtypes
         lib.mi_pt_texture_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_shape_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.mi_pt_texture_probe.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_light_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_light_distribution.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]
         lib.mi_pt_debug_path.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -617,6 +624,16 @@ class PathIntegrator:
             raise RuntimeError("mi_pt_texture_lookup failed: %s" % hip_lib().mi_pt_last_error().decode())
         return out
 
+    def texture_probe(self, tex, queries):
+        """A noise texture's value on the device (mi_pt_texture_probe): queries [n, 9] = the interaction's world (p, dpdx, dpdy)
+        -> [n], Texture<Float>::Evaluate times post_scale. A texture of another type is an error."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, 9)
+        out = np.zeros(q.shape[0], np.float32)
+        rc = hip_lib().mi_pt_texture_probe(self._h, int(tex), q.shape[0], _fptr(q), _fptr(out))
+        if rc != 0:
+            raise RuntimeError("mi_pt_texture_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
+        return out
+
     def shape_probe(self, quadric, mode, queries):
         """One quadric of the scene on its own (mi_pt_shape_probe; index space of mi_prim.shape: spheres, then disks).
         mode 0: queries [n, 7] rays (o, d, tMax) -> [n, 16] hit, t, p, n, uv, dpdu, dpdv; mode 1: [n, 5] (ref, u) -> [n, 7]
@@ -777,6 +794,13 @@ def CreateIntegrator(scene, device=0):
     if int(scene.desc.integrator.kind) == INTEGRATOR_METADATA:
         return MetadataIntegrator(scene, device)
     return PathIntegrator(scene, device)
+
+
+def noise_perm():
+    """The permutation table behind the noise textures (mi_noise_perm): [512] int32, the permutation of 0..255 twice."""
+    out = np.zeros(512, np.int32)
+    host_lib().mi_noise_perm(out.ctypes.data_as(C.POINTER(C.c_int32)))
+    return out
 
 
 def write_dat(filename, film, scale=1.0):

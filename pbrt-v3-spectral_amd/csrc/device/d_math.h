@@ -45,6 +45,7 @@ static DEV_CALL float acosF(float x) { return (float)acos((double)x); }
 static DEV_CALL float atan2F(float y, float x) { return (float)atan2((double)y, (double)x); }
 static DEV_CALL float logF(float x) { return (float)log((double)x); }
 static DEV_CALL float powF(float x, float y) { return (float)pow((double)x, (double)y); }
+DEV float Log2F(float x) { const float invLog2 = 1.442695040888963387004650940071; return logF(x) * invLog2; }
 
 // x / d for many x and one d: one IEEE reciprocal, then per quotient a multiply and two
 // fused corrections (q = x*r; rem = fma(-q, d, x); q += rem*r). With r the correctly

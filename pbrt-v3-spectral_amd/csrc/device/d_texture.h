@@ -8,6 +8,7 @@
 // spectral loops need them, like every other spectrum on this path.
 #pragma once
 #include "d_sampling.h"
+#include "d_noise.h"
 
 namespace dpt {
 
@@ -57,7 +58,10 @@ DEV CamDifferentials CameraDifferentials(const DScene &s, const float *c2w, floa
     return c;
 }
 
-struct TexDifferentials { float dudx, dvdx, dudy, dvdy; };
+struct TexDifferentials {
+    float dudx, dvdx, dudy, dvdy;
+    V3 dpdx, dpdy;   // si.dpdx / si.dpdy: the world-space footprint the 3-D (noise) textures read
+};
 
 DEV bool SolveLinearSystem2x2(const float A[2][2], const float B[2], float *x0, float *x1) {  // transform.cpp:41-49
     float det = A[0][0] * A[1][1] - A[0][1] * A[1][0];
@@ -71,6 +75,7 @@ DEV bool SolveLinearSystem2x2(const float A[2][2], const float B[2], float *x0, 
 DEV TexDifferentials ComputeDifferentials(const V3 &p, const V3 &n, const V3 &dpdu, const V3 &dpdv, const CamDifferentials &ray) {
     TexDifferentials t;
     t.dudx = t.dvdx = t.dudy = t.dvdy = 0;
+    t.dpdx = t.dpdy = V3(0, 0, 0);
     float d = Dot(n, V3(p.x, p.y, p.z));
     float tx = -(Dot(n, ray.rxOrigin) - d) / Dot(n, ray.rxDirection);
     if (isinff(tx) || isnanf_(tx)) return t;
@@ -78,6 +83,8 @@ DEV TexDifferentials ComputeDifferentials(const V3 &p, const V3 &n, const V3 &dp
     float ty = -(Dot(n, ray.ryOrigin) - d) / Dot(n, ray.ryDirection);
     if (isinff(ty) || isnanf_(ty)) return t;
     V3 py = ray.ryOrigin + ty * ray.ryDirection;
+    t.dpdx = px - p;
+    t.dpdy = py - p;
     int dim0, dim1;
     if (absf(n.x) > absf(n.y) && absf(n.x) > absf(n.z)) { dim0 = 1; dim1 = 2; }
     else if (absf(n.y) > absf(n.z)) { dim0 = 0; dim1 = 2; }
@@ -167,7 +174,6 @@ DEV RGB3 MipTriangle(const mi_mipmap &m, int level, float st0, float st1) {  // 
     return (1 - ds) * (1 - dt) * MipTexel(m, level, s0, t0) + (1 - ds) * dt * MipTexel(m, level, s0, t0 + 1) +
            ds * (1 - dt) * MipTexel(m, level, s0 + 1, t0) + ds * dt * MipTexel(m, level, s0 + 1, t0 + 1);
 }
-DEV float Log2F(float x) { const float invLog2 = 1.442695040888963387004650940071; return logF(x) * invLog2; }
 DEV RGB3 MipLookupWidth(const mi_mipmap &m, float st0, float st1, float width, bool noFiltering) {  // mipmap.h:238-266
     if (noFiltering) {
         float s = st0 * MipUSize(m, 0) - 0.5f;
@@ -299,22 +305,28 @@ DEV bool DiskTexCoords(const mi_disk &k, const V3 &ro, const V3 &rd, float *u, f
     return true;
 }
 
-// Texture<Float>::Evaluate(si) of float image texture `tex`
-DEV float EvalFloatImageTexture(const DScene &s, int tex, float u, float v, const TexDifferentials &td) {
+// Texture<Float>::Evaluate(si) of float texture `tex`: an image texture at (u, v), or (NOISE: the instance holds that code)
+// a noise texture at the world point p, both with the footprint in td
+template <bool NOISE>
+DEV float EvalFloatImageTexture(const DScene &s, int tex, float u, float v, const V3 &p, const TexDifferentials &td) {
     const mi_texture &t = s.textures[tex];
+    if constexpr (NOISE) {
+        if (MI_TEX_IS_NOISE(t.type)) return NoiseTextureValue(t, p, td.dpdx, td.dpdy) * t.post_scale;
+    }
     const mi_mipmap &m = s.mipmaps[t.mipmap];
     return MipLookup(s, m, t.su * u + t.du, t.sv * v + t.dv, t.su * td.dudx, t.sv * td.dvdx, t.su * td.dudy, t.sv * td.dvdy, t.filter, t.max_aniso).r * t.post_scale;
 }
-// Material::Bump (material.cpp:47-84) with a uv-mapped displacement: updates the interaction's shading normal and
-// shading dpdu (what the BSDF frame is built from).
+// Material::Bump (material.cpp:47-84): updates the interaction's shading normal and shading dpdu (what the BSDF frame is
+// built from). The shifted evaluations move uv and (for a 3-D displacement, NOISE) p; the footprint stays the interaction's.
+template <bool NOISE>
 DEV void Bump(const DScene &s, int tex, float u, float v, const TexDifferentials &td, const TriShading &tsh, SurfaceInteraction *si) {
     float du = .5f * (absf(td.dudx) + absf(td.dudy));
     if (du == 0) du = .0005f;
-    const float uDisplace = EvalFloatImageTexture(s, tex, u + du, v, td);
+    const float uDisplace = EvalFloatImageTexture<NOISE>(s, tex, u + du, v, NOISE ? si->p + du * si->shDpdu : si->p, td);
     float dv = .5f * (absf(td.dvdx) + absf(td.dvdy));
     if (dv == 0) dv = .0005f;
-    const float vDisplace = EvalFloatImageTexture(s, tex, u, v + dv, td);
-    const float displace = EvalFloatImageTexture(s, tex, u, v, td);
+    const float vDisplace = EvalFloatImageTexture<NOISE>(s, tex, u, v + dv, NOISE ? si->p + dv * tsh.shDpdv : si->p, td);
+    const float displace = EvalFloatImageTexture<NOISE>(s, tex, u, v, si->p, td);
     const V3 dpdu = si->shDpdu + (uDisplace - displace) / du * si->shN + displace * tsh.dndu;
     const V3 dpdv = tsh.shDpdv + (vDisplace - displace) / dv * si->shN + displace * tsh.dndv;
     V3 n = Normalize(Cross(dpdu, dpdv));   // SetShadingGeometry(..., false), interaction.cpp:76-93
@@ -338,8 +350,17 @@ DEV float CheckerboardArea2(float st0, float st1, float dx0, float dx1, float dy
     if (ds > 1 || dt > 1) area2 = .5f;
     return area2;
 }
-DEV IllumRGB EvalImageTexture(const DScene &s, int tex, float u, float v, const TexDifferentials &td) {
+template <bool NOISE>
+DEV IllumRGB EvalImageTexture(const DScene &s, int tex, float u, float v, const V3 &p, const TexDifferentials &td) {
     const mi_texture &t = s.textures[tex];
+    if constexpr (NOISE) {
+        if (MI_TEX_IS_NOISE(t.type)) {   // Spectrum(v), the same value in every bin: the checkerboard's form over the record's
+            IllumRGB q;                  // spec1 = 0, spec2 = 1 (UploadTextures) -- (1 - v) * 0 + v * 1 is v, so TexBin stays as it is
+            q.i1 = -1; q.i2 = tex; q.w1 = q.w2 = 0.f;
+            q.w0 = NoiseTextureValue(t, p, td.dpdx, td.dpdy);
+            return q;
+        }
+    }
     if (t.type == MI_TEX_CHECKERBOARD) {
         IllumRGB q;
         q.i1 = -1; q.i2 = tex; q.w1 = q.w2 = 0.f;

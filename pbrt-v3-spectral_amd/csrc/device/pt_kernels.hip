@@ -2105,6 +2105,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
     const uint32_t qi = blk * BLOCK + threadIdx.x;
     constexpr bool HALTON_ONLY = (TM & TM_SAMPLERS) == 0;
     constexpr bool DISKS = TM_HOLDS_DISKS(TM);   // (a scene with disks is shaded by the general instances alone: ShadeInstanceOf)
+    constexpr bool NOISE = TM_HOLDS_NOISE(TM);   // (likewise the textured classes of a scene with noise textures)
     constexpr bool SIMPLE_SPECTRA = NL <= 2 && TM_SIMPLE_KINDS(TM);   // the straight-line spectral passes (d_bsdf.h, SimpleLobes)
     // more than two lobes: f is summed lobe by lobe into the lane's column of the spectrum tile (AccumulateF, d_bsdf.h)
     constexpr bool ACCUM = NL > 2 || (TM & TM_TEXTURED) != 0;   // (image-textured lobes too: their spectra quad by quad, TexturedQuad)
@@ -2252,6 +2253,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                 if (haveUV) {
                     TexDifferentials td;
                     td.dudx = td.dvdx = td.dudy = td.dvdy = 0;
+                    td.dpdx = td.dpdy = V3(0, 0, 0);
                     if (flags & F_DIFF) {   // SurfaceInteraction::ComputeDifferentials, interaction.cpp:99-143
                         if constexpr (LENS) {   // the lens camera's, from its offset rays: k_generate stored them
                             CamDifferentials cd;
@@ -2282,15 +2284,15 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                         td = ComputeDifferentials(isect.p, isect.n, isect.dpdu, tsh.dpdv, cd);
                         }
                     }
-                    if (mat->bump_tex >= 0) Bump(s, mat->bump_tex, u, v, td, tsh, &isect);   // `if (bumpMap) Bump(bumpMap, si)`
+                    if (mat->bump_tex >= 0) Bump<NOISE>(s, mat->bump_tex, u, v, td, tsh, &isect);   // `if (bumpMap) Bump(bumpMap, si)`
                     // `rough = roughness->Evaluate(*si); if (remapRoughness) rough = RoughnessToAlpha(rough)` (plastic.cpp:57-62 ...)
                     float rawU = mat->bxdf[0].p[6], rawV = mat->bxdf[0].p[7];   // (MI_ROUGH_GLASS: the values before the remap)
                     if (mat->rough_flags & MI_ROUGH_DISNEY) {   // `Float rough = roughness->Evaluate(*si)`, disney.cpp:491
                         fr.ov.disney = true;
-                        fr.ov.rough = EvalFloatImageTexture(s, mat->rough_tex[0], u, v, td);
+                        fr.ov.rough = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[0], u, v, isect.p, td);
                     } else
                     if (mat->rough_tex[0] >= 0) {
-                        const float rv = EvalFloatImageTexture(s, mat->rough_tex[0], u, v, td);
+                        const float rv = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[0], u, v, isect.p, td);
                         fr.ov.u = (mat->rough_flags & MI_ROUGH_REMAP) ? RoughnessToAlpha(rv) : rv;
                         fr.ov.onU = true;
                         rawU = rv;
@@ -2298,14 +2300,14 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                     if (mat->rough_tex[1] >= 0) {
                         if (mat->rough_tex[1] == mat->rough_tex[0]) { fr.ov.v = fr.ov.u; rawV = rawU; }
                         else {
-                            const float rv = EvalFloatImageTexture(s, mat->rough_tex[1], u, v, td);
+                            const float rv = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[1], u, v, isect.p, td);
                             fr.ov.v = (mat->rough_flags & MI_ROUGH_REMAP) ? RoughnessToAlpha(rv) : rv;
                             rawV = rv;
                         }
                         fr.ov.onV = true;
                     }
                     if (mat->sigma_tex >= 0) {   // `Float sig = Clamp(sigma->Evaluate(*si), 0, 90)`, matte.cpp:57; OrenNayar's constructor
-                        const float sig = clampf(EvalFloatImageTexture(s, mat->sigma_tex, u, v, td), 0.f, 90.f);
+                        const float sig = clampf(EvalFloatImageTexture<NOISE>(s, mat->sigma_tex, u, v, isect.p, td), 0.f, 90.f);
                         if (sig == 0) fr.ov.sigMode = 2;
                         else {
                             const float sigma = (kPi / 180) * sig, sigma2 = sigma * sigma;
@@ -2320,13 +2322,13 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                         if (ltx.tex_R < 0 && ltx.tex_S < 0) { mask |= 1u << i; continue; }
                         if (i >= NL) continue;
                         if (ltx.tex_R >= 0) {
-                            lt.r[i] = EvalImageTexture(s, ltx.tex_R, u, v, td);
+                            lt.r[i] = EvalImageTexture<NOISE>(s, ltx.tex_R, u, v, isect.p, td);
                             if (ltx.rule == MI_LOBE_METAL) lt.hasK |= 1u << i;   // (k's texture: the lobe's R stays the constant)
                             else lt.hasR |= 1u << i;
                             if (ltx.flags & MI_LOBE_TEX_MUL_R) lt.mulR |= 1u << i;
                         }
                         if (ltx.tex_S >= 0) {
-                            lt.s[i] = EvalImageTexture(s, ltx.tex_S, u, v, td);
+                            lt.s[i] = EvalImageTexture<NOISE>(s, ltx.tex_S, u, v, isect.p, td);
                             lt.hasS |= 1u << i;
                             if (ltx.flags & MI_LOBE_TEX_MUL_S) lt.mulS |= 1u << i;
                         }
@@ -2995,6 +2997,17 @@ __global__ void k_texture_lookup(DScene s, int tex, const float *q, uint32_t n, 
     out[3 * i] = v.r; out[3 * i + 1] = v.g; out[3 * i + 2] = v.b;
 }
 
+// mi_pt_texture_probe: a noise texture's value for an interaction given by its world p, dpdx and dpdy, as k_shade asks for it
+__global__ void k_texture_probe(DScene s, int tex, const float *q, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = q + 9 * (size_t)i;
+    TexDifferentials td;
+    td.dudx = td.dvdx = td.dudy = td.dvdy = 0;
+    td.dpdx = V3(r[3], r[4], r[5]); td.dpdy = V3(r[6], r[7], r[8]);
+    out[i] = EvalFloatImageTexture<true>(s, tex, 0.f, 0.f, V3(r[0], r[1], r[2]), td);
+}
+
 // ------------------------------------------------------------------ one quadric on its own (mi_pt_shape_probe)
 __global__ void k_shape_probe(DScene s, int q, int mode, const float *in, uint32_t n, float *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3442,7 +3455,9 @@ constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstanc
 // and plastic instances.
 // `disks`: the scene has disks, whose code only the instances compiled for every lobe, light and sampler hold (TM_HOLDS_DISKS):
 // no class of such a scene fits an instance compiled for a subset, so those are the code they were before disks.
-static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot, bool disks) {
+// `noise`: the scene has noise textures, whose code only the general texture-evaluating instances hold (TM_HOLDS_NOISE): every
+// textured class of such a scene goes there, and the textured matte and plastic instances are the code they were before.
+static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot, bool disks, bool noise) {
     auto pick = [](int nl, unsigned tm) {
         for (int i = 0; i < N_SHADE_INSTANCES; ++i)
             if (kShadeInstances[i].nl == nl && kShadeInstances[i].tm == tm) return i;
@@ -3468,8 +3483,8 @@ static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned h
         if (fits(TM_DISNEY)) return pick(MI_MAX_BXDFS, TM_DISNEY | TM_LIGHTS_ALL | TM_SAMPLERS);
         return pick(lobes <= 4 ? 4 : MI_MAX_BXDFS, TM_GENERIC);
     }
-    if (lobes <= 2 && fits(TM_DIFFUSE | TM_TEXTURED)) return pick(2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS);
-    if (lobes <= 2 && fits(TM_PLASTIC | TM_TEXTURED)) return pick(2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS);
+    if (!noise && lobes <= 2 && fits(TM_DIFFUSE | TM_TEXTURED)) return pick(2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS);
+    if (!noise && lobes <= 2 && fits(TM_PLASTIC | TM_TEXTURED)) return pick(2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS);
     return pick(texturedDisney ? MI_MAX_BXDFS : lobes <= 2 ? 2 : lobes <= 4 ? 4 : MI_MAX_BXDFS, TM_FULL);
 }
 
@@ -3650,17 +3665,18 @@ int CheckSceneDesc(const mi_scene_desc *d) {
         const mi_material &m = d->materials[i];
         if (m.n_bxdfs < 0 || m.n_bxdfs > MI_MAX_BXDFS) { g_err = "material lobe count out of range"; return MI_ERR_INVALID; }
         if (m.bump_tex >= (int)d->n_textures || m.bump_tex < -1) { g_err = "mi_material.bump_tex out of range"; return MI_ERR_INVALID; }
-        for (int k = 0; k < 2; ++k) {   // roughness maps: float image textures with a pyramid behind them (EvalFloatImageTexture)
+        for (int k = 0; k < 2; ++k) {   // roughness maps: float image textures with a pyramid behind them, or noise textures (EvalFloatImageTexture)
             const int rt = m.rough_tex[k];
             if (rt < -1 || rt >= (int)d->n_textures) { g_err = "mi_material.rough_tex out of range"; return MI_ERR_INVALID; }
-            if (rt >= 0 && (d->textures[rt].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[rt].mipmap >= d->n_mipmaps)) {
-                g_err = "mi_material.rough_tex must name an image texture with a mipmap"; return MI_ERR_INVALID;
+            if (rt >= 0 && !MI_TEX_IS_NOISE(d->textures[rt].type) && (d->textures[rt].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[rt].mipmap >= d->n_mipmaps)) {
+                g_err = "mi_material.rough_tex must name an image texture with a mipmap or a noise texture"; return MI_ERR_INVALID;
             }
         }
         // (ABI v10) the sigma map, the lobe rules and the glass switch: what the shading kernels index with them
         if (m.sigma_tex < -1 || m.sigma_tex >= (int)d->n_textures ||
-            (m.sigma_tex >= 0 && (d->textures[m.sigma_tex].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[m.sigma_tex].mipmap >= d->n_mipmaps))) {
-            g_err = "mi_material.sigma_tex must be -1 or name an image texture with a mipmap"; return MI_ERR_INVALID;
+            (m.sigma_tex >= 0 && !MI_TEX_IS_NOISE(d->textures[m.sigma_tex].type) &&
+             (d->textures[m.sigma_tex].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[m.sigma_tex].mipmap >= d->n_mipmaps))) {
+            g_err = "mi_material.sigma_tex must be -1 or name an image texture with a mipmap or a noise texture"; return MI_ERR_INVALID;
         }
         for (int k = 0; k < m.n_bxdfs; ++k) {
             const mi_lobe_tex &lt = m.tex[k];
@@ -3672,8 +3688,17 @@ int CheckSceneDesc(const mi_scene_desc *d) {
             g_err = "MI_ROUGH_GLASS: lobe 0 must be the FresnelSpecular one"; return MI_ERR_INVALID;
         }
     }
-    for (uint32_t i = 0; i < d->n_textures; ++i)
-        if (d->textures[i].type == MI_TEX_IMAGEMAP && (uint32_t)d->textures[i].mipmap >= d->n_mipmaps) { g_err = "mi_texture.mipmap out of range"; return MI_ERR_INVALID; }
+    for (uint32_t i = 0; i < d->n_textures; ++i) {
+        const mi_texture &t = d->textures[i];
+        if (t.type < MI_TEX_IMAGEMAP || t.type > MI_TEX_WINDY) { g_err = "mi_texture.type is not a mi_tex_type"; return MI_ERR_INVALID; }
+        if (t.type == MI_TEX_IMAGEMAP && (uint32_t)t.mipmap >= d->n_mipmaps) { g_err = "mi_texture.mipmap out of range"; return MI_ERR_INVALID; }
+        // (the octave loops run per lane: bounded here as the front end bounds them)
+        if (MI_TEX_IS_NOISE(t.type) && (t.octaves < 0 || t.octaves > MI_NOISE_MAX_OCTAVES)) { g_err = "mi_texture.octaves outside 0..32"; return MI_ERR_INVALID; }
+    }
+    // the traversal kernels hold no noise code: a mask is an image texture
+    for (uint32_t i = 0; i < d->n_meshes; ++i)
+        for (int a : {d->meshes[i].alpha_tex, d->meshes[i].shadow_alpha_tex})
+            if (a >= 0 && d->textures[a].type != MI_TEX_IMAGEMAP) { g_err = "mi_mesh alpha textures must be image textures"; return MI_ERR_INVALID; }
     for (uint32_t i = 0; i < d->n_mipmaps; ++i) {
         const mi_mipmap &m = d->mipmaps[i];
         if (m.n_levels < 1 || m.n_levels > MI_MAX_MIP_LEVELS || !m.texels || m.width < 1 || m.height < 1) { g_err = "malformed mi_mipmap"; return MI_ERR_INVALID; }
@@ -3951,6 +3976,8 @@ int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, Sh
     int (&classLobes)[MAX_CLASSES] = sc.classLobes;
     unsigned (&classTypes)[MAX_CLASSES] = sc.classTypes;
     std::vector<std::vector<int>> signatures;
+    bool noise = false;
+    for (uint32_t i = 0; i < d->n_textures; ++i) noise |= MI_TEX_IS_NOISE(d->textures[i].type);
     for (uint32_t i = 0; i < d->n_materials; ++i) {
         const mi_material &m = d->materials[i];
         std::vector<int> sig;
@@ -3970,7 +3997,7 @@ int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, Sh
     }
     for (int c = 0; c < MAX_CLASSES; ++c) {
         if (!((sc.classMask >> c) & 1u)) continue;
-        const int i = ShadeInstanceOf(classTypes[c], classLobes[c], instanced, hot, d->n_disks > 0);
+        const int i = ShadeInstanceOf(classTypes[c], classLobes[c], instanced, hot, d->n_disks > 0, noise);
         if (i < 0) { g_err = "no k_shade instance for shading class " + std::to_string(c); return MI_ERR_UNSUPPORTED; }
         sc.classInstance[c] = i;
         sc.shadeClasses[i] |= 1u << c;
@@ -4316,7 +4343,13 @@ int UploadScene(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
         up(texels, nTexels * 3, m.texels);
     }
     if (!mips.empty()) up(mips.data(), mips.size(), s.mipmaps);
-    if (d->n_textures) up(d->textures, (size_t)d->n_textures, s.textures);
+    // (a spectrum noise value v reaches the lobes in the checkerboard's compact form: (1 - v) * spec1 + v * spec2 with spec1 = 0,
+    // spec2 = 1 is v in every bin -- EvalImageTexture, TexBin)
+    std::vector<mi_texture> texs(d->textures, d->textures + d->n_textures);
+    for (mi_texture &t : texs)
+        if (MI_TEX_IS_NOISE(t.type))
+            for (int b = 0; b < MI_NSPEC; ++b) { t.spec1[b] = 0.f; t.spec2[b] = 1.f; }
+    if (!texs.empty()) up(texs.data(), texs.size(), s.textures);
     up(h.ewaWeights.data(), h.ewaWeights.size(), s.ewaWeights);
     return up.rc;
 }
@@ -4915,6 +4948,24 @@ int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *querie
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(rgb, dout.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi_pt_texture_probe(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
+    if (!MI_TEX_IS_NOISE(pt->textureTypes[tex])) { g_err = "mi_pt_texture_probe: not a noise texture"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_texture_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    HIPCHK(hipSetDevice(pt->device));
+    DevBuf dq, dout;
+    HIPCHK(dq.alloc((size_t)n * 9 * sizeof(float)));
+    HIPCHK(dout.alloc((size_t)n * sizeof(float)));
+    HIPCHK(hipMemcpy(dq.p, queries, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_texture_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, (int)tex, dq.as<float>(), n, dout.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return MI_OK;
 }
 

@@ -304,7 +304,13 @@ struct Api {
         const std::string texName = params.FindTexture(param);
         if (texName != "") {
             auto it = gs.textures.floatImageTex.find(texName);
-            if (it != gs.textures.floatImageTex.end()) return it->second;
+            if (it != gs.textures.floatImageTex.end()) {
+                if (MI_TEX_IS_NOISE(scene->textures[it->second].type)) {   // (it would put the noise into the traversal kernels)
+                    Err("Noise texture \"" + texName + "\" as \"" + param + "\" of a shape is outside the hot-path scope; the shape is left unmasked");
+                    return -1;
+                }
+                return it->second;
+            }
             auto c = gs.textures.floatTex.find(texName);
             if (c == gs.textures.floatTex.end()) { Err("Couldn't find float texture \"" + texName + "\" for \"" + param + "\" parameter"); return -1; }
             if (c->second != 0.f) return -1;   // a constant that is never 0 masks nothing
@@ -772,8 +778,9 @@ struct Api {
     void Texture(const std::string &name, const std::string &type, const std::string &texname, const ParamSet &ps) {
         // Every texture on this path evaluates to a constant, so "scale" and "mix" of such textures fold into
         // constants with the reference's arithmetic (src/textures/scale.h:56-58, mix.h:57-61, scale.cpp, mix.cpp).
-        if (texname != "constant" && texname != "scale" && texname != "mix" && texname != "imagemap" && texname != "checkerboard") {
-            Err("Texture class \"" + texname + "\" is outside the hot-path scope (\"constant\", \"scale\", \"mix\", \"imagemap\", \"checkerboard\")");
+        const bool isNoise = texname == "fbm" || texname == "wrinkled" || texname == "windy";
+        if (texname != "constant" && texname != "scale" && texname != "mix" && texname != "imagemap" && texname != "checkerboard" && !isNoise) {
+            Err("Texture class \"" + texname + "\" is outside the hot-path scope (\"constant\", \"scale\", \"mix\", \"imagemap\", \"checkerboard\", \"fbm\", \"wrinkled\", \"windy\")");
             return;
         }
         ParamSet empty;
@@ -781,6 +788,38 @@ struct Api {
         const bool isFloat = type == "float", isSpec = type == "color" || type == "spectrum";
         if (!isFloat && !isSpec) { Err("Texture type \"" + type + "\" unknown."); return; }
         WarnIfAnimated("Texture");   // api.cpp:1231, 1249
+        if (isNoise) {   // Create{FBm,Wrinkled,Windy}{Float,Spectrum}Texture, src/textures/{fbm,wrinkled,windy}.cpp
+            mi_texture t{};
+            t.type = texname == "fbm" ? MI_TEX_FBM : (texname == "wrinkled" ? MI_TEX_WRINKLED : MI_TEX_WINDY);
+            t.mipmap = -1;
+            t.su = t.sv = 1.f; t.post_scale = 1.f; t.max_aniso = 8.f;
+            t.octaves = 8; t.omega = .5f;
+            if (t.type != MI_TEX_WINDY) {
+                t.octaves = ps.FindOneInt("octaves", 8);
+                t.omega = ps.FindOneFloat("roughness", .5f);
+                if (t.octaves < 0) { Err("Texture \"" + name + "\": \"octaves\" " + std::to_string(t.octaves) + " is negative"); return; }
+                if (t.octaves > MI_NOISE_MAX_OCTAVES) {   // the octave loop runs per lane: keep it bounded
+                    Warn("Texture \"" + name + "\": \"octaves\" " + std::to_string(t.octaves) + " clamped to " + std::to_string(MI_NOISE_MAX_OCTAVES) + " on this path");
+                    t.octaves = MI_NOISE_MAX_OCTAVES;
+                }
+            }
+            // IdentityMapping3D(tex2world): WorldToTexture = Inverse(tex2world), tex2world = the CTM here (curTransform[0], api.cpp:1233)
+            std::memcpy(t.w2t, ctm.mInv.m, sizeof(t.w2t));
+            // (it binds wherever an image texture of its type binds; the shape masks refuse it, AlphaTexture)
+            if (isFloat) {
+                gs.textures.floatTex.erase(name);
+                gs.textures.floatImageTex[name] = (int)scene->textures.size();
+            } else {
+                gs.textures.spectrumTex.erase(name);
+                gs.textures.scaledImageTex.erase(name);
+                gs.textures.imageTex[name] = (int)scene->textures.size();
+            }
+            scene->textures.push_back(t);
+            std::vector<std::string> unused;
+            ps.ReportUnused(&unused);
+            for (auto &u : unused) Warn("Parameter \"" + u + "\" not used");
+            return;
+        }
         if (texname == "checkerboard") {  // CreateCheckerboardSpectrumTexture, checkerboard.cpp:99-150
             if (isFloat) { Err("Texture \"" + name + "\": float \"checkerboard\" textures are outside the hot-path scope"); return; }
             if (ps.FindOneInt("dimension", 2) != 2) { Err("Texture \"" + name + "\": 3D \"checkerboard\" textures are outside the hot-path scope"); return; }

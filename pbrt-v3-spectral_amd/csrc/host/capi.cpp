@@ -136,6 +136,13 @@ void mi_scene_free(mi_scene *s) {
 
 const char *mi_scene_last_error(void) { return g_err.c_str(); }
 
+void mi_noise_perm(int32_t out[512]) {
+    static const unsigned char perm[512] = {
+#include "noise_perm.inc"
+    };
+    for (int i = 0; i < 512; ++i) out[i] = perm[i];
+}
+
 int mi_film_write_dat(const char *filename, int w, int h, const float *film_sum, float scale) {
     if (!filename || !film_sum || w <= 0 || h <= 0) { g_err = "bad argument"; return MI_ERR_INVALID; }
     std::string err;

@@ -16,7 +16,7 @@
 namespace mipt {
 namespace {
 
-const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '8'};
+const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '9'};   // 09: mi_texture grew (noise textures) under an unchanged ABI number
 
 struct Out {
     FILE *f;
