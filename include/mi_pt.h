@@ -289,6 +289,12 @@ typedef enum mi_light_type {
     MI_LIGHT_INFINITE,         /* src/lights/infinite.cpp (environment light; mi_envmap) */
     MI_LIGHT_SPOT              /* src/lights/spot.cpp: pos, L = I, w2l, cos_total_width, cos_falloff_start */
 } mi_light_type;
+/* src/lights/projection.cpp: the sixth light type, a point light whose intensity is an image seen through a perspective
+ * frustum: pos, L = I * scale, w2l (all of WorldToLight's 3x3, scale included), cos_total_width, and the fields from
+ * `screen` on. It stands outside the enum because the enum's values are also the bit numbers 24 + type of a k_shade mask,
+ * and bits 24..28 are taken: the projection has no mask bit, its code is held by the general instances (TM_HOLDS_PROJECTION)
+ * and a scene with such a light is shaded by those alone. */
+#define MI_LIGHT_PROJECTION 5
 
 typedef struct mi_light {
     int32_t type;
@@ -302,7 +308,16 @@ typedef struct mi_light {
     float world_center[3];
     int32_t envmap;    /* infinite: index into mi_scene_desc.envmaps */
     float l2w[9], w2l[9]; /* infinite, spot: rotation part of LightToWorld / WorldToLight, row major */
-    float cos_total_width, cos_falloff_start; /* spot */
+    float cos_total_width, cos_falloff_start; /* spot; projection: cos_total_width (only Power() reads it) */
+    /* MI_LIGHT_PROJECTION (appended; read for that type only, 0 in the records of the other lights) */
+    float screen[4];     /* screenBounds {pMin.x, pMin.y, pMax.x, pMax.y}: [-aspect, aspect] x [-1, 1] for aspect > 1, else
+                          * [-1, 1] x [-1 / aspect, 1 / aspect]; aspect from the file's own resolution, 1 without a map */
+    float proj[16];      /* lightProjection = Perspective(fov, hither, yon).m, row major; yon = 1e30f */
+    float hither;        /* 1e-3f: directions with wl.z < hither are behind the light */
+    int32_t proj_map;    /* index into mi_scene_desc.envmaps of projectionMap's level 0 (a record without a distribution:
+                          * nu = nv = 0, null tables), -1 = no map: Projection is Spectrum(1) inside the frustum */
+    float proj_centre[MI_NSPEC]; /* Spectrum(projectionMap->Lookup((.5,.5), .5), Illuminant), Spectrum(1) without a map:
+                                  * Power() = proj_centre * L * 2 pi (1 - cos_total_width); the render does not read it */
 } mi_light;
 
 /* InfiniteAreaLight::Lmap (level 0 of the MIPMap<RGBSpectrum>, after the reference's power-of-two resampling)
@@ -312,7 +327,8 @@ typedef struct mi_light {
 typedef struct mi_envmap {
     int32_t width, height;     /* Lmap->Width(), Height() */
     const float *rgb;          /* [height * width * 3] */
-    int32_t nu, nv;            /* Distribution2D: nu = 2 * width, nv = 2 * height */
+    int32_t nu, nv;            /* Distribution2D: nu = 2 * width, nv = 2 * height. A projection light's map
+                                * (mi_light.proj_map) has no distribution: nu = nv = 0 and the five tables NULL */
     const float *cond_func;    /* [nv * nu]       pConditionalV[v]->func */
     const float *cond_cdf;     /* [nv * (nu + 1)] pConditionalV[v]->cdf */
     const float *cond_func_int;/* [nv]            pConditionalV[v]->funcInt */
@@ -680,8 +696,10 @@ int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, cons
  *   mode 0: Light::Sample_Li(ref, u). queries: 8 floats (ref.p[3], ref.n[3], u[2]); out: MI_LIGHT_PROBE_SAMPLE_FLOATS floats --
  *           wi[3], pdf, pLight.p[3], pLight.n[3] (zero for every light but an area light), Li[MI_NSPEC]. Where Sample_Li
  *           returns before it has a direction (pdf == 0 on an area light; mapPdf == 0 on the infinite light) all are 0; where
- *           the sample is black (a one-sided emitter seen from behind) the Li bins are 0.
- *   mode 1: Light::Pdf_Li(ref, wi). queries: 9 floats (ref.p[3], ref.n[3], wi[3]); out: 1 float. 0 for the delta lights,
+ *           the sample is black (a one-sided emitter seen from behind; a projection light seen from behind it or from outside
+ *           its frustum) the Li bins are 0.
+ *   mode 1: Light::Pdf_Li(ref, wi). queries: 9 floats (ref.p[3], ref.n[3], wi[3]); out: 1 float. 0 for the delta lights (point,
+ *           distant, spot, projection),
  *           Shape::Pdf(ref, wi) for an area light, InfiniteAreaLight::Pdf_Li for the infinite light.
  *   mode 2: Light::Le(ray) of the infinite light -- queries: 3 floats (ray.d) -- and DiffuseAreaLight::L(n, w) of an area
  *           light -- queries: 6 floats (n[3], w[3]); out: MI_NSPEC floats. MI_ERR_INVALID for the delta lights. */

@@ -100,7 +100,13 @@ class Light(C.Structure):
     _fields_ = [("type", C.c_int32), ("shape", C.c_int32), ("two_sided", C.c_int32), ("area", C.c_float),
                 ("L", C.c_float * NSPEC), ("pos", C.c_float * 3), ("dir", C.c_float * 3),
                 ("world_radius", C.c_float), ("world_center", C.c_float * 3), ("envmap", C.c_int32),
-                ("l2w", C.c_float * 9), ("w2l", C.c_float * 9), ("cos_total_width", C.c_float), ("cos_falloff_start", C.c_float)]
+                ("l2w", C.c_float * 9), ("w2l", C.c_float * 9), ("cos_total_width", C.c_float), ("cos_falloff_start", C.c_float),
+                # the projection light (LIGHT_PROJECTION): screen bounds, lightProjection, hither, the map (-1: none), Power()'s map factor
+                ("screen", C.c_float * 4), ("proj", C.c_float * 16), ("hither", C.c_float), ("proj_map", C.c_int32),
+                ("proj_centre", C.c_float * NSPEC)]
+
+
+LIGHT_PROJECTION = 5   # MI_LIGHT_PROJECTION: the light type that has no bit in the k_shade masks (LIGHT_TYPES names those)
 
 
 class EnvMap(C.Structure):

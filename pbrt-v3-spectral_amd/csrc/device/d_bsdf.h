@@ -294,6 +294,9 @@ constexpr unsigned TM_TEXTURED = 1u << 30;  // some lobe takes its spectrum from
 constexpr unsigned TM_LIGHTS_ALL = 0x1fu << 24;
 // the instances that hold the disk's code: the general ones, compiled for every lobe, Fresnel kind, light and sampler (TM_GENERIC, TM_FULL, TM_ALL)
 #define TM_HOLDS_DISKS(tm) ((((tm) | TM_INSTANCES | TM_TEXTURED)) == TM_ALL)
+// the instances that hold the projection light's code (MI_LIGHT_PROJECTION has no light bit: 24..28 are taken, 29 is TM_INSTANCES):
+// the same general ones; a scene with such a light is shaded by them alone (ShadeInstanceOf)
+#define TM_HOLDS_PROJECTION(tm) TM_HOLDS_DISKS(tm)
 // the instances that hold the noise textures' code: the general ones that evaluate textures (TM_FULL, TM_ALL)
 #define TM_HOLDS_NOISE(tm) ((((tm) | TM_INSTANCES)) == TM_ALL)
 constexpr unsigned TM_LIGHTS_NO_ENV = TM_LIGHTS_ALL & ~(1u << (24 + MI_LIGHT_INFINITE));

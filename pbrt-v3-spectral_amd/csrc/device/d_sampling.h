@@ -355,7 +355,11 @@ DEV float ShapePdf(const DScene &s, int shape, float area, const Interaction &re
     return pdf;
 }
 
-DEV bool IsDeltaLight(const mi_light &l) { return l.type == MI_LIGHT_POINT || l.type == MI_LIGHT_DISTANT || l.type == MI_LIGHT_SPOT; }
+// PROJECTION: the caller can meet a projection light (the general k_shade instances, TM_HOLDS_PROJECTION; the probe)
+template <bool PROJECTION = true>
+DEV bool IsDeltaLight(const mi_light &l) {
+    return l.type == MI_LIGHT_POINT || l.type == MI_LIGHT_DISTANT || l.type == MI_LIGHT_SPOT || (PROJECTION && l.type == MI_LIGHT_PROJECTION);
+}
 
 // ---- InfiniteAreaLight (src/lights/infinite.cpp:85-141); IllumRGB / MakeIllumRGB: d_bsdf.h
 DEV float IllumBin(const DScene &s, const IllumRGB &q, int bin) {
@@ -417,6 +421,31 @@ DEV float InfinitePdfLi(const DScene &s, const mi_light &l, const V3 &w) {  // i
     return e.cond_func[(size_t)iv * e.nu + iu] / e.marg_func_int / (2 * kPi * kPi * sinTheta);
 }
 
+// ---- ProjectionLight::Projection(w) (src/lights/projection.cpp:87-98). false: the value is 0 (behind the light, outside the
+// screen bounds). true: *hasMap says whether it is Spectrum(projectionMap->Lookup(st), Illuminant), left in *q, or Spectrum(1).
+// Transform::operator()(Point3f) multiplies by 1 / wp unless wp == 1 (transform.h:222-233, geometry.h:500-504); Inside is
+// inclusive at both ends; the lookup is EnvLookup's (width 0, level 0, Repeat, no flip of t).
+DEV bool Projection(const DScene &s, const mi_light &l, const V3 &w, bool *hasMap, IllumRGB *q) {
+    const V3 wl = Mul3(l.w2l, w);
+    *hasMap = false;
+    if (wl.z < l.hither) return false;   // discard directions behind the projection light
+    const float *m = l.proj;
+    float px = m[0] * wl.x + m[1] * wl.y + m[2] * wl.z + m[3];
+    float py = m[4] * wl.x + m[5] * wl.y + m[6] * wl.z + m[7];
+    const float wp = m[12] * wl.x + m[13] * wl.y + m[14] * wl.z + m[15];
+    if (wp != 1) { const float inv = 1.f / wp; px = inv * px; py = inv * py; }
+    if (!(px >= l.screen[0] && px <= l.screen[2] && py >= l.screen[1] && py <= l.screen[3])) return false;
+    if (l.proj_map < 0) return true;
+    float ox = px - l.screen[0], oy = py - l.screen[1];   // Bounds2::Offset
+    if (l.screen[2] > l.screen[0]) ox /= l.screen[2] - l.screen[0];
+    if (l.screen[3] > l.screen[1]) oy /= l.screen[3] - l.screen[1];
+    float rgb[3];
+    EnvLookup(s.envmaps[l.proj_map], ox, oy, rgb);
+    *q = MakeIllumRGB(rgb);
+    *hasMap = true;
+    return true;
+}
+
 struct LightSample {
     V3 wi;
     float pdf;
@@ -424,7 +453,8 @@ struct LightSample {
     float liScale;   // Li[bin] = L[bin] * liScale (point light: I / d^2 is a true division, flag below)
     bool divide;     // Li[bin] = (L[bin] * liMul) / liScale  (point: liMul = 1; spot: the falloff)
     float liMul;
-    bool isEnv;      // infinite light: Li[bin] = IllumBin(env, bin)
+    bool isEnv;      // infinite light: Li[bin] = IllumBin(env, bin); with `divide` (a projection light with a map):
+                     // Li[bin] = (L[bin] * IllumBin(env, bin)) / liScale
     IllumRGB env;
     Interaction pLight;
 };
@@ -478,6 +508,18 @@ DEV LightSample SampleLi(const DScene &s, const mi_light &l, const Interaction &
         ls.env = MakeIllumRGB(rgb);
         ls.isEnv = true;
         ls.black = false;   // (a black map value shows up bin by bin: the caller tests Li != 0)
+    } else if (TM_HOLDS_PROJECTION(TM) && l.type == MI_LIGHT_PROJECTION) {  // projection.cpp:76-85
+        V3 pLight(l.pos[0], l.pos[1], l.pos[2]);
+        ls.wi = Normalize(pLight - ref.p);
+        ls.pdf = 1.f;
+        ls.pLight.p = pLight;
+        // I * Projection(-wi) / d^2: (I * 1) / d^2 without a map -- the point light's floats --, (I * 0) / d^2 where it is 0
+        bool hasMap;
+        ls.liMul = Projection(s, l, -ls.wi, &hasMap, &ls.env) ? 1.f : 0.f;
+        ls.isEnv = hasMap;   // (with `divide`: the map's spectrum times I, over d^2)
+        ls.divide = true;
+        ls.liScale = DistanceSquared(pLight, ref.p);
+        ls.black = false;   // (a zero projection shows up bin by bin: the caller tests Li != 0)
     } else if (l.type == MI_LIGHT_POINT) {
         V3 pLight(l.pos[0], l.pos[1], l.pos[2]);
         ls.wi = Normalize(pLight - ref.p);
@@ -497,6 +539,7 @@ DEV LightSample SampleLi(const DScene &s, const mi_light &l, const Interaction &
 }
 template <unsigned TM>
 DEV float LiBin(const DScene &s, const mi_light &l, const LightSample &ls, int bin) {
+    if (TM_HOLDS_PROJECTION(TM) && ls.isEnv && ls.divide) return (l.L[bin] * IllumBin(s, ls.env, bin)) / ls.liScale;
     if (TM_LIGHT(TM, MI_LIGHT_INFINITE) && ls.isEnv) return IllumBin(s, ls.env, bin);
     return ls.divide ? (l.L[bin] * ls.liMul) / ls.liScale : l.L[bin];
 }
@@ -504,6 +547,12 @@ DEV float LiBin(const DScene &s, const mi_light &l, const LightSample &ls, int b
 // Quad c (bins 4c..4c+3) of Li; the light's spectrum is one 16-B load (see EvalQuad).
 template <unsigned TM>
 DEV float4 LiQuad(const DScene &s, const mi_light &l, const LightSample &ls, int c) {
+    if (TM_HOLDS_PROJECTION(TM) && ls.isEnv && ls.divide) {
+        const float4 L = LoadSpec4(l.L, c);
+        const int b = 4 * c;
+        return make_float4((L.x * IllumBin(s, ls.env, b)) / ls.liScale, (L.y * IllumBin(s, ls.env, b + 1)) / ls.liScale,
+                           (L.z * IllumBin(s, ls.env, b + 2)) / ls.liScale, (L.w * IllumBin(s, ls.env, min(b + 3, MI_NSPEC - 1))) / ls.liScale);
+    }
     if (TM_LIGHT(TM, MI_LIGHT_INFINITE) && ls.isEnv) {
         const int b = 4 * c;
         return make_float4(IllumBin(s, ls.env, b), IllumBin(s, ls.env, b + 1), IllumBin(s, ls.env, b + 2),

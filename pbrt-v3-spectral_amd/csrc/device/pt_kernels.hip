@@ -2406,7 +2406,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                             auto fQuad = [&](int c) -> float4 { if constexpr (ACCUM) return rdTile(c); else return EvalQuad<NL, TM>(ev, mat->bxdf, c, ltp); };
                             const float absdot = AbsDot(ls.wi, isect.shN);
                             const float scatteringPdf = BSDF_Pdf<TM>(fr, isect.wo, ls.wi, nonSpec);
-                            const bool delta = IsDeltaLight(light);
+                            const bool delta = IsDeltaLight<TM_HOLDS_PROJECTION(TM)>(light);
                             float weight = 1.f;
                             if (!delta) { float pf = 1 * lightPdf, pg = 1 * scatteringPdf; weight = (pf * pf) / (pf * pf + pg * pg); }
                             const Divisor lpDiv = MakeDivisor(lightPdf);
@@ -2489,7 +2489,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
                                 newFlags |= F_SHADOW;
                             }
                         }
-                        if (!IsDeltaLight(light)) {  // BSDF sampling with MIS, integrator.cpp:167-213
+                        if (!IsDeltaLight<TM_HOLDS_PROJECTION(TM)>(light)) {  // BSDF sampling with MIS, integrator.cpp:167-213
                             V3 wi;
                             float sPdf = 0;
                             int sampledType = 0;
@@ -3457,7 +3457,10 @@ constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstanc
 // no class of such a scene fits an instance compiled for a subset, so those are the code they were before disks.
 // `noise`: the scene has noise textures, whose code only the general texture-evaluating instances hold (TM_HOLDS_NOISE): every
 // textured class of such a scene goes there, and the textured matte and plastic instances are the code they were before.
-static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot, bool disks, bool noise) {
+// `projection`: the scene has a projection light, whose code the same instances hold as the disks' (TM_HOLDS_PROJECTION): any
+// class can draw that light, so every class of such a scene goes where a scene with disks sends it.
+static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot, bool disks, bool noise, bool projection) {
+    disks |= projection;
     auto pick = [](int nl, unsigned tm) {
         for (int i = 0; i < N_SHADE_INSTANCES; ++i)
             if (kShadeInstances[i].nl == nl && kShadeInstances[i].tm == tm) return i;
@@ -3705,7 +3708,10 @@ int CheckSceneDesc(const mi_scene_desc *d) {
     }
     for (uint32_t i = 0; i < d->n_envmaps; ++i) {
         const mi_envmap &e = d->envmaps[i];
-        if (e.width < 1 || e.height < 1 || e.nu < 1 || e.nv < 1 || !e.rgb || !e.cond_func || !e.cond_cdf || !e.cond_func_int || !e.marg_func || !e.marg_cdf) {
+        // (a projection light's map is the image alone: nu = nv = 0 and no tables)
+        const bool tables = e.cond_func && e.cond_cdf && e.cond_func_int && e.marg_func && e.marg_cdf;
+        const bool noTables = !e.cond_func && !e.cond_cdf && !e.cond_func_int && !e.marg_func && !e.marg_cdf;
+        if (e.width < 1 || e.height < 1 || !e.rgb || !((e.nu >= 1 && e.nv >= 1 && tables) || (e.nu == 0 && e.nv == 0 && noTables))) {
             g_err = "malformed mi_envmap"; return MI_ERR_INVALID;
         }
     }
@@ -3713,8 +3719,10 @@ int CheckSceneDesc(const mi_scene_desc *d) {
     for (uint32_t i = 0; i < d->n_lights; ++i) {
         const mi_light &l = d->lights[i];
         if (l.type == MI_LIGHT_DIFFUSE_AREA && (l.shape >= 0 ? (uint32_t)l.shape >= d->n_tris : (uint64_t)(uint32_t)(~l.shape) >= (uint64_t)d->n_spheres + d->n_disks)) { g_err = "area light shape index out of range"; return MI_ERR_INVALID; }
+        if (l.type < MI_LIGHT_DIFFUSE_AREA || l.type > MI_LIGHT_PROJECTION) { g_err = "mi_light.type is not a light type"; return MI_ERR_INVALID; }
+        if (l.type == MI_LIGHT_PROJECTION && (l.proj_map < -1 || l.proj_map >= (int)d->n_envmaps)) { g_err = "mi_light.proj_map out of range"; return MI_ERR_INVALID; }
         if (l.type != MI_LIGHT_INFINITE) continue;
-        if ((uint32_t)l.envmap >= d->n_envmaps) { g_err = "infinite light without environment map"; return MI_ERR_INVALID; }
+        if ((uint32_t)l.envmap >= d->n_envmaps || d->envmaps[l.envmap].nu < 1) { g_err = "infinite light without environment map"; return MI_ERR_INVALID; }
         if (++nInfinite > 4) { g_err = "more than 4 infinite lights"; return MI_ERR_INVALID; }
     }
     const mi_lightdistrib &ld = d->light_distrib;
@@ -3976,8 +3984,9 @@ int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, Sh
     int (&classLobes)[MAX_CLASSES] = sc.classLobes;
     unsigned (&classTypes)[MAX_CLASSES] = sc.classTypes;
     std::vector<std::vector<int>> signatures;
-    bool noise = false;
+    bool noise = false, projection = false;
     for (uint32_t i = 0; i < d->n_textures; ++i) noise |= MI_TEX_IS_NOISE(d->textures[i].type);
+    for (uint32_t i = 0; i < d->n_lights; ++i) projection |= d->lights[i].type == MI_LIGHT_PROJECTION;
     for (uint32_t i = 0; i < d->n_materials; ++i) {
         const mi_material &m = d->materials[i];
         std::vector<int> sig;
@@ -3997,7 +4006,7 @@ int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, Sh
     }
     for (int c = 0; c < MAX_CLASSES; ++c) {
         if (!((sc.classMask >> c) & 1u)) continue;
-        const int i = ShadeInstanceOf(classTypes[c], classLobes[c], instanced, hot, d->n_disks > 0, noise);
+        const int i = ShadeInstanceOf(classTypes[c], classLobes[c], instanced, hot, d->n_disks > 0, noise, projection);
         if (i < 0) { g_err = "no k_shade instance for shading class " + std::to_string(c); return MI_ERR_UNSUPPORTED; }
         sc.classInstance[c] = i;
         sc.shadeClasses[i] |= 1u << c;
@@ -4994,7 +5003,7 @@ int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const 
     if (light < 0 || (size_t)light >= pt->lightTypes.size()) { g_err = "mi_pt_light_probe: light index out of range"; return MI_ERR_INVALID; }
     if (mode < 0 || mode > 2) { g_err = "mi_pt_light_probe: mode must be 0, 1 or 2"; return MI_ERR_INVALID; }
     const int type = pt->lightTypes[light];
-    const bool delta = type == MI_LIGHT_POINT || type == MI_LIGHT_DISTANT || type == MI_LIGHT_SPOT;
+    const bool delta = type == MI_LIGHT_POINT || type == MI_LIGHT_DISTANT || type == MI_LIGHT_SPOT || type == MI_LIGHT_PROJECTION;
     if (mode == 2 && delta) { g_err = "mi_pt_light_probe: mode 2 (Le / L) on a delta light"; return MI_ERR_INVALID; }
     if (n > (1u << 24)) { g_err = "mi_pt_light_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;

@@ -765,6 +765,42 @@ struct Api {
             for (int i = 0; i < MI_NSPEC; ++i) l.L[i] = centre.c[i];
             for (int r = 0; r < 3; ++r)
                 for (int c = 0; c < 3; ++c) { l.l2w[3 * r + c] = ctm.m.m[r][c]; l.w2l[3 * r + c] = ctm.mInv.m[r][c]; }
+        } else if (name == "projection") {  // CreateProjectionLight and the constructor, projection.cpp:45-74, 133-142
+            Spectrum I = ps.FindOneSpectrum("I", Spectrum(1.0));
+            Spectrum sc = ps.FindOneSpectrum("scale", Spectrum(1.0));
+            const float fov = ps.FindOneFloat("fov", 45.);
+            std::string texmap = ps.FindOneString("mapname", "");
+            if (!texmap.empty() && texmap[0] != '/') texmap = baseDir + "/" + texmap;   // FindOneFilename
+            const Vec3 p = ctm.Point(Vec3(0, 0, 0));
+            l.type = MI_LIGHT_PROJECTION;
+            Spectrum Is = I * sc;
+            for (int i = 0; i < MI_NSPEC; ++i) l.L[i] = Is.c[i];
+            l.pos[0] = p.x; l.pos[1] = p.y; l.pos[2] = p.z;
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) { l.l2w[3 * r + c] = ctm.m.m[r][c]; l.w2l[3 * r + c] = ctm.mInv.m[r][c]; }
+            // the map: ReadImage reports a file it cannot read and the light goes on without one
+            HostEnvMap map;
+            int rx = 0, ry = 0;
+            Spectrum centre(1.f);
+            std::string ioErr;
+            l.proj_map = -1;
+            if (!texmap.empty()) {
+                if (BuildProjectionMap(texmap, &map, &rx, &ry, &centre, &ioErr)) {
+                    l.proj_map = (int)scene->envStore.size();
+                    scene->envStore.push_back(std::move(map));
+                } else
+                    Err("LightSource \"projection\": " + ioErr + "; the light projects no map (a white frustum)");
+            }
+            for (int i = 0; i < MI_NSPEC; ++i) l.proj_centre[i] = centre.c[i];
+            const float aspect = l.proj_map >= 0 ? (float(rx) / float(ry)) : 1;
+            if (aspect > 1) { l.screen[0] = -aspect; l.screen[1] = -1; l.screen[2] = aspect; l.screen[3] = 1; }
+            else { l.screen[0] = -1; l.screen[1] = -1 / aspect; l.screen[2] = 1; l.screen[3] = 1 / aspect; }
+            l.hither = 1e-3f;
+            const float yon = 1e30f;
+            const Transform lightProjection = Perspective(fov, l.hither, yon);
+            std::memcpy(l.proj, lightProjection.m.m, sizeof(l.proj));
+            const Vec3 wCorner = Normalize(Inverse(lightProjection).Point(Vec3(l.screen[2], l.screen[3], 0)));
+            l.cos_total_width = wCorner.z;
         } else {
             Err("LightSource \"" + name + "\" is outside the hot-path scope (SURVEY 2 row 20); skipped.");
             return;
@@ -1845,6 +1881,8 @@ void HostScene::Finalize() {
         m.nu = e.nu; m.nv = e.nv;
         m.cond_func = e.condFunc.data(); m.cond_cdf = e.condCdf.data(); m.cond_func_int = e.condFuncInt.data();
         m.marg_func = e.margFunc.data(); m.marg_cdf = e.margCdf.data(); m.marg_func_int = e.margFuncInt;
+        if (e.nu == 0 && e.nv == 0)   // a projection light's map: the image alone
+            m.cond_func = m.cond_cdf = m.cond_func_int = m.marg_func = m.marg_cdf = nullptr;
         envmaps.push_back(m);
     }
     d.n_envmaps = (uint32_t)envmaps.size();

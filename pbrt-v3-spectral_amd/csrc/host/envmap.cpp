@@ -81,6 +81,24 @@ bool BuildEnvMap(const Spectrum &L, const std::string &texmap, HostEnvMap *store
     return true;
 }
 
+bool BuildProjectionMap(const std::string &texmap, HostEnvMap *store, int *rx, int *ry, Spectrum *centre, std::string *err) {
+    std::vector<RGB> texels;   // projection.cpp:52-56
+    if (!ReadImage(texmap, rx, ry, &texels, err) || texels.empty()) {
+        if (err->empty()) *err = "Unable to read image \"" + texmap + "\"";
+        return false;
+    }
+    MIPMap mip(*rx, *ry, texels);
+    HostEnvMap &e = *store;
+    e = HostEnvMap();
+    e.width = mip.Width(); e.height = mip.Height();
+    e.rgb.resize((size_t)e.width * e.height * 3);
+    for (size_t i = 0; i < (size_t)e.width * e.height; ++i) for (int k = 0; k < 3; ++k) e.rgb[3 * i + k] = mip.pyramid[0].t[i].c[k];
+    const float half[2] = {.5f, .5f};
+    const RGB c = mip.Lookup(half, .5f);   // projection.cpp:100-106
+    *centre = Spectrum::FromRGB(c.c, SpectrumType::Illuminant);
+    return true;
+}
+
 int ConstantFloatMipMap(HostScene *scene, float value) {
     char keyBuf[64];
     snprintf(keyBuf, sizeof keyBuf, "<constant>|%a", value);

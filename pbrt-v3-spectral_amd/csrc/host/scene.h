@@ -17,7 +17,7 @@ struct SceneStats {
     int nLights = 0, nMaterials = 0;
 };
 
-// LightSource "infinite" (envmap.cpp)
+// LightSource "infinite", and the map of a LightSource "projection" (envmap.cpp)
 struct HostEnvMap {
     int width = 0, height = 0, nu = 0, nv = 0;
     std::vector<float> rgb, condFunc, condCdf, condFuncInt, margFunc, margCdf;
@@ -138,6 +138,10 @@ int BuildTextureMipMap(HostScene *scene, const std::string &filename, bool trili
                        int wrap, float scale, bool gamma, bool isFloat = false);
 int ConstantFloatMipMap(HostScene *scene, float value);   // ConstantTexture<Float> as a 1x1 pyramid
 bool BuildEnvMap(const Spectrum &L, const std::string &texmap, HostEnvMap *store, Spectrum *centre, std::vector<std::string> *errors);
+// LightSource "projection": level 0 of the light's MIPMap<RGBSpectrum> (Repeat, after the power-of-two resampling) as an
+// environment-map record without a distribution (nu = nv = 0), the file's own resolution (the aspect comes from it) and
+// *centre = Spectrum(Lookup((.5, .5), .5f), Illuminant), the map's factor in Power(). false with *err: the file cannot be read.
+bool BuildProjectionMap(const std::string &texmap, HostEnvMap *store, int *rx, int *ry, Spectrum *centre, std::string *err);
 bool WriteRGBImage(const std::string &filename, int w, int h, const float *filmSum, const float *weightSum, float scale,
                    std::string *written, std::string *err);
 bool CompileMixMaterial(const mi_material &m1, const mi_material &m2, const Spectrum &amount, mi_material *out,

@@ -16,7 +16,7 @@
 namespace mipt {
 namespace {
 
-const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '0', '9'};   // 09: mi_texture grew (noise textures) under an unchanged ABI number
+const char kMagic[8] = {'M', 'I', 'P', 'T', 'S', 'C', '1', '0'};   // 10: mi_light grew (projection light) under an unchanged ABI number; 09: mi_texture (noise textures)
 
 struct Out {
     FILE *f;
@@ -178,9 +178,10 @@ HostScene *LoadSceneCache(const std::string &path, std::string *err) {
         consistent = s->primes[i] >= 2 && s->primeSums[i] >= 0 && (size_t)s->primeSums[i] + (size_t)s->primes[i] <= s->perms.size();
     for (size_t i = 0; consistent && i < s->envStore.size(); ++i) {   // mi_envmap
         const HostEnvMap &e = s->envStore[i];
-        consistent = e.width >= 1 && e.height >= 1 && e.nu >= 1 && e.nv >= 1 && e.width <= (1 << 16) && e.height <= (1 << 16) && e.nu <= (1 << 17) && e.nv <= (1 << 17) &&
+        // (nu = nv = 0: a projection light's map, the image without a distribution -- every table empty by the size checks below)
+        consistent = e.width >= 1 && e.height >= 1 && ((e.nu >= 1 && e.nv >= 1) || (e.nu == 0 && e.nv == 0 && e.margCdf.empty())) && e.width <= (1 << 16) && e.height <= (1 << 16) && e.nu <= (1 << 17) && e.nv <= (1 << 17) &&
                      e.rgb.size() == 3ull * e.width * e.height && e.condFunc.size() == (size_t)e.nu * e.nv && e.condCdf.size() == ((size_t)e.nu + 1) * e.nv &&
-                     e.condFuncInt.size() == (size_t)e.nv && e.margFunc.size() == (size_t)e.nv && e.margCdf.size() == (size_t)e.nv + 1;
+                     e.condFuncInt.size() == (size_t)e.nv && e.margFunc.size() == (size_t)e.nv && e.margCdf.size() == (e.nu ? (size_t)e.nv + 1 : 0);
     }
     for (size_t i = 0; consistent && i < s->mipStore.size(); ++i) {   // mi_mipmap: every level inside the texel array
         const HostMipMap &m = s->mipStore[i];
