@@ -330,6 +330,12 @@ def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _check(rc, name):
+    """The return code of the HIP library's entry point `name`: RuntimeError with the library's message unless it is MI_OK."""
+    if rc != 0:
+        raise RuntimeError("%s failed: %s" % (name, hip_lib().mi_pt_last_error().decode()))
+
+
 class Scene:
     """A parsed .pbrt scene flattened to ``mi_scene_desc`` (reference: pbrtParseFile +
     pbrtWorldEnd up to, not including, ``integrator->Render``; src/core/api.cpp:1617-1707)."""
@@ -536,15 +542,13 @@ class PathIntegrator:
     def shade_launch_stats(self):
         """(launches, blocks) of k_shade in the last render, summed over the sub-renderers (mi_pt_shade_launch_stats)."""
         n, b = C.c_uint64(), C.c_uint64()
-        if hip_lib().mi_pt_shade_launch_stats(self._h, C.byref(n), C.byref(b)) != 0:
-            raise RuntimeError("mi_pt_shade_launch_stats failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_shade_launch_stats(self._h, C.byref(n), C.byref(b)), "mi_pt_shade_launch_stats")
         return int(n.value), int(b.value)
 
     def dark_launch_stats(self):
         """(launches, entries, rays, resolve_skipped) of the dark MIS rays in the last render (mi_pt_dark_launch_stats)."""
         v = [C.c_uint64() for _ in range(4)]
-        if hip_lib().mi_pt_dark_launch_stats(self._h, *[C.byref(x) for x in v]) != 0:
-            raise RuntimeError("mi_pt_dark_launch_stats failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_dark_launch_stats(self._h, *[C.byref(x) for x in v]), "mi_pt_dark_launch_stats")
         return tuple(int(x.value) for x in v)
 
     def device_film(self):
@@ -560,9 +564,7 @@ class PathIntegrator:
         n = rays.shape[0]
         hits = np.zeros((n, 4), np.float32)
         fn = hip_lib().mi_pt_trace_timed if rays.shape[1] == 8 else hip_lib().mi_pt_trace
-        rc = fn(self._h, _fptr(rays), n, 1 if any_hit else 0, _fptr(hits))
-        if rc != 0:
-            raise RuntimeError("mi_pt_trace failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(fn(self._h, _fptr(rays), n, 1 if any_hit else 0, _fptr(hits)), "mi_pt_trace")
         return hits
 
     def camera_rays(self, samples):
@@ -570,9 +572,7 @@ class PathIntegrator:
         [n, 8] = o, d, tMax, time."""
         s = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
         out = np.zeros((s.shape[0], 8), np.float32)
-        rc = hip_lib().mi_pt_camera_rays(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], _fptr(out))
-        if rc != 0:
-            raise RuntimeError("mi_pt_camera_rays failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_camera_rays(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], _fptr(out)), "mi_pt_camera_rays")
         return out
 
     def camera_rays_ex(self, samples, band=0):
@@ -581,9 +581,7 @@ class PathIntegrator:
         1 / sqrt(spp)); `band`: the "spectralpath" band whose wavelength the lens is traced at."""
         s = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
         out = np.zeros((s.shape[0], 21), np.float32)
-        rc = hip_lib().mi_pt_camera_rays_ex(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], int(band), _fptr(out))
-        if rc != 0:
-            raise RuntimeError("mi_pt_camera_rays_ex failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_camera_rays_ex(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], int(band), _fptr(out)), "mi_pt_camera_rays_ex")
         return out
 
     def trace_wavefront(self, rays, mode=0):
@@ -596,9 +594,7 @@ class PathIntegrator:
         hits = np.zeros((n, 4), np.float32)
         extra = np.zeros((n, 4), np.float32)
         fn = hip_lib().mi_pt_trace_wavefront_timed if rays.shape[1] == 8 else hip_lib().mi_pt_trace_wavefront   # (rays [n, 8]: a time per ray)
-        rc = fn(self._h, _fptr(rays), n, int(mode), _fptr(hits), _fptr(extra))
-        if rc != 0:
-            raise RuntimeError("mi_pt_trace_wavefront failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(fn(self._h, _fptr(rays), n, int(mode), _fptr(hits), _fptr(extra)), "mi_pt_trace_wavefront")
         return hits, extra.view(np.int32)
 
     def light_distribution(self):
@@ -607,27 +603,21 @@ class PathIntegrator:
         nx, ny, nz = [int(v) for v in d.light_distrib.n_voxels]
         func = np.zeros((nz, ny, nx, d.n_lights), np.float32)
         fint = np.zeros((nz, ny, nx), np.float32)
-        rc = hip_lib().mi_pt_light_distribution(self._h, _fptr(func), _fptr(fint), nx * ny * nz)
-        if rc != 0:
-            raise RuntimeError("mi_pt_light_distribution failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_light_distribution(self._h, _fptr(func), _fptr(fint), nx * ny * nz), "mi_pt_light_distribution")
         return func, fint
 
     def debug_path(self, px, py, sample, max_records=64):
         """Vertex-by-vertex state of one camera sample (records of PATH_RECORD_FLOATS floats, include/mi_pt.h)."""
         rec = np.zeros((max_records, PATH_RECORD_FLOATS), np.float32)
         n = C.c_int32()
-        rc = hip_lib().mi_pt_debug_path(self._h, int(px), int(py), int(sample), max_records, _fptr(rec), C.byref(n))
-        if rc != 0:
-            raise RuntimeError("mi_pt_debug_path failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_debug_path(self._h, int(px), int(py), int(sample), max_records, _fptr(rec), C.byref(n)), "mi_pt_debug_path")
         return rec[: n.value]
 
     def texture_lookup(self, tex, queries):
         """MIPMap::Lookup on the device: queries [n, 6] = (s, t, dsdx, dtdx, dsdy, dtdy) -> rgb [n, 3]."""
         q = np.ascontiguousarray(queries, np.float32)
         out = np.zeros((q.shape[0], 3), np.float32)
-        rc = hip_lib().mi_pt_texture_lookup(self._h, int(tex), q.shape[0], _fptr(q), _fptr(out))
-        if rc != 0:
-            raise RuntimeError("mi_pt_texture_lookup failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_texture_lookup(self._h, int(tex), q.shape[0], _fptr(q), _fptr(out)), "mi_pt_texture_lookup")
         return out
 
     def texture_probe(self, tex, queries):
@@ -635,9 +625,7 @@ class PathIntegrator:
         -> [n], Texture<Float>::Evaluate times post_scale. A texture of another type is an error."""
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, 9)
         out = np.zeros(q.shape[0], np.float32)
-        rc = hip_lib().mi_pt_texture_probe(self._h, int(tex), q.shape[0], _fptr(q), _fptr(out))
-        if rc != 0:
-            raise RuntimeError("mi_pt_texture_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_texture_probe(self._h, int(tex), q.shape[0], _fptr(q), _fptr(out)), "mi_pt_texture_probe")
         return out
 
     def shape_probe(self, quadric, mode, queries):
@@ -647,9 +635,7 @@ class PathIntegrator:
         n_in, n_out = {0: (7, 16), 1: (5, 7), 2: (6, 1)}[int(mode)]
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, n_in)
         out = np.zeros((q.shape[0], n_out), np.float32)
-        rc = hip_lib().mi_pt_shape_probe(self._h, int(quadric), int(mode), q.shape[0], _fptr(q), _fptr(out))
-        if rc != 0:
-            raise RuntimeError("mi_pt_shape_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_shape_probe(self._h, int(quadric), int(mode), q.shape[0], _fptr(q), _fptr(out)), "mi_pt_shape_probe")
         return out[:, 0] if n_out == 1 else out
 
     def light_probe(self, light, mode, queries):
@@ -667,9 +653,7 @@ class PathIntegrator:
         if want is not None and q.shape[1] != want:
             raise ValueError("light_probe mode %d takes %d floats per query for this light" % (mode, want))
         out = np.zeros((q.shape[0], n_out), np.float32)
-        rc = hip_lib().mi_pt_light_probe(self._h, int(light), int(mode), q.shape[0], _fptr(q), _fptr(out))
-        if rc != 0:
-            raise RuntimeError("mi_pt_light_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
+        _check(hip_lib().mi_pt_light_probe(self._h, int(light), int(mode), q.shape[0], _fptr(q), _fptr(out)), "mi_pt_light_probe")
         return out[:, 0] if n_out == 1 else out
 
 
@@ -678,9 +662,7 @@ def math_probe(op, x, y=None, device=0):
     x = np.ascontiguousarray(x, np.float32)
     y = np.ascontiguousarray(x if y is None else y, np.float32)
     out = np.zeros((x.shape[0], 3), np.float32)
-    rc = hip_lib().mi_pt_math_probe(device, int(op), x.shape[0], _fptr(x), _fptr(y), _fptr(out))
-    if rc != 0:
-        raise RuntimeError("mi_pt_math_probe failed: %s" % hip_lib().mi_pt_last_error().decode())
+    _check(hip_lib().mi_pt_math_probe(device, int(op), x.shape[0], _fptr(x), _fptr(y), _fptr(out)), "mi_pt_math_probe")
     return out
 
 
@@ -736,11 +718,9 @@ def shade_instances():
     """[(NL, TM)] of the k_shade instances in launch order (mi_pt_shade_instances; no device)."""
     n = C.c_uint32()
     lib = hip_lib()
-    if lib.mi_pt_shade_instances(None, None, 0, C.byref(n)) != 0:
-        raise RuntimeError("mi_pt_shade_instances failed: %s" % lib.mi_pt_last_error().decode())
+    _check(lib.mi_pt_shade_instances(None, None, 0, C.byref(n)), "mi_pt_shade_instances")
     nl, tm = (C.c_int32 * n.value)(), (C.c_uint32 * n.value)()
-    if lib.mi_pt_shade_instances(nl, tm, n.value, C.byref(n)) != 0:
-        raise RuntimeError("mi_pt_shade_instances failed: %s" % lib.mi_pt_last_error().decode())
+    _check(lib.mi_pt_shade_instances(nl, tm, n.value, C.byref(n)), "mi_pt_shade_instances")
     return [(int(nl[i]), int(tm[i])) for i in range(n.value)]
 
 
@@ -751,8 +731,7 @@ def shade_grid(counts, classes):
     arr = (C.c_uint32 * len(counts))(*counts)
     blocks = C.c_uint32()
     lib = hip_lib()
-    if lib.mi_pt_shade_grid(arr, len(counts), int(classes), C.byref(blocks)) != 0:
-        raise RuntimeError("mi_pt_shade_grid failed: %s" % lib.mi_pt_last_error().decode())
+    _check(lib.mi_pt_shade_grid(arr, len(counts), int(classes), C.byref(blocks)), "mi_pt_shade_grid")
     return int(blocks.value)
 
 

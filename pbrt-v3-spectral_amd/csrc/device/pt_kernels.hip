@@ -3430,9 +3430,9 @@ struct SubRenderer {
 struct ShadeInstance {
     int nl;
     unsigned tm;
-    void (*kernel)(DScene, Pool, DevCounters *, unsigned);
-    void (*kernelLens)(DScene, Pool, DevCounters *, unsigned);   // the LENS twin of an instance that reads image textures, or null
-    void (*kernelMotion)(DScene, Pool, DevCounters *, unsigned), (*kernelMotionLens)(DScene, Pool, DevCounters *, unsigned);   // the MOTION twins of an instance with the instance code, or null
+    // [motion][lens]: [0][1] the LENS twin of an instance that reads image textures, [1][...] the MOTION twins of an instance
+    // with the instance code; null: no such twin
+    void (*kernel[2][2])(DScene, Pool, DevCounters *, unsigned);
 };
 template <int NL, unsigned TM, bool LENS>
 constexpr auto MotionShadeKernel() -> void (*)(DScene, Pool, DevCounters *, unsigned) {
@@ -3444,7 +3444,7 @@ constexpr auto LensShadeKernel() -> void (*)(DScene, Pool, DevCounters *, unsign
     if constexpr ((TM & TM_TEXTURED) != 0) return k_shade<NL, TM, true>;
     else return nullptr;
 }
-#define MIPT_SHADE_ENTRY(P_, NL_, TM_) {NL_, (TM_), k_shade<NL_, (TM_)>, LensShadeKernel<NL_, (TM_)>(), MotionShadeKernel<NL_, (TM_), false>(), MotionShadeKernel<NL_, (TM_), true>()},
+#define MIPT_SHADE_ENTRY(P_, NL_, TM_) {NL_, (TM_), {{k_shade<NL_, (TM_)>, LensShadeKernel<NL_, (TM_)>()}, {MotionShadeKernel<NL_, (TM_), false>(), MotionShadeKernel<NL_, (TM_), true>()}}},
 static const ShadeInstance kShadeInstances[] = {MIPT_SHADE_INSTANCES(MIPT_SHADE_ENTRY)};
 #undef MIPT_SHADE_ENTRY
 constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstances[0]);
@@ -3590,14 +3590,20 @@ void FreePool(Pool &p) {
     p = Pool{};   // n = 0, every pointer null: a later render cannot mistake a half-built pool for a usable one
 }
 
+// The one way a sub-renderer gives its pool back: the memory and every record of it, so that mi_pt_pool_info and the next
+// render's memory budget count nothing that is no longer held.
+void ReleasePool(SubRenderer &sub) {
+    FreePool(sub.pool);
+    sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0;
+    sub.poolBytes = 0;
+}
+
 // Failure-safe: the new pool is built aside and swapped in only when every allocation succeeded; after a failure the
 // sub-renderer holds no pool at all (n == 0), so the next render allocates afresh instead of launching on stale sizes.
 int EnsurePool(SubRenderer &sub, uint32_t n, int nQuadPlanes, int nFloatPlanes) {
     Pool &p = sub.pool;
     if (p.n == n && p.f && sub.poolQuadPlanes == nQuadPlanes && sub.poolFloatPlanes == nFloatPlanes) return MI_OK;
-    FreePool(p);
-    sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0;
-    sub.poolBytes = 0;
+    ReleasePool(sub);
     Pool t{};
     const bool ok = hipMalloc((void **)&t.f, (size_t)nFloatPlanes * n * sizeof(float)) == hipSuccess &&
                     hipMalloc((void **)&t.q, (size_t)nQuadPlanes * n * sizeof(float4)) == hipSuccess &&
@@ -3629,6 +3635,48 @@ struct DevBuf {
     ~DevBuf() { if (p) hipFree(p); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
     template <typename T> T *as() const { return (T *)p; }
+};
+
+// The body of an entry point that asks the device one batch of questions: `in` to the device, `launch(dIn, dOut)` (on the null
+// stream), `out` back. The entry point has checked its arguments.
+template <typename Launch>
+int RunProbe(int device, const void *in, size_t inBytes, void *out, size_t outBytes, Launch launch) {
+    HIPCHK(hipSetDevice(device));
+    DevBuf dIn, dOut;
+    HIPCHK(dIn.alloc(inBytes));
+    HIPCHK(dOut.alloc(outBytes));
+    HIPCHK(hipMemcpy(dIn.p, in, inBytes, hipMemcpyHostToDevice));
+    launch(dIn.p, dOut.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dOut.p, outBytes, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+// The grid of such a launch: a thread per question.
+dim3 ProbeGrid(uint32_t n) { return dim3((n + BLOCK - 1) / BLOCK); }
+
+// The samples (px, py, sample number) of the camera-ray entry point `entry`: the pixel indexes per-pixel tables (Halton offsets, a
+// pixel sampler's tables), so it lies inside the sample bounds, and a pixel sampler's sample number inside its tables.
+int CheckCameraSamples(const mi_pt *pt, const int32_t *samples, uint32_t n, const char *entry) {
+    const DScene &s = pt->scene;
+    for (uint32_t i = 0; i < n; ++i) {
+        const int px = samples[3 * i], py = samples[3 * i + 1];
+        if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3] || samples[3 * i + 2] < 0 ||
+            (s.samplerType >= MI_SAMPLER_ZEROTWO && samples[3 * i + 2] >= pt->spp)) {
+            g_err = std::string(entry) + ": a sample lies outside the sample bounds (or beyond a pixel sampler's tables)";
+            return MI_ERR_INVALID;
+        }
+    }
+    return MI_OK;
+}
+
+// A call that renders through a view of the scene of its own (mi_pt_render_metadata, mi_pt_debug_path) edits pt->scene in
+// place behind one of these: the renderer's DScene and its metaStrategy are back on every return path.
+struct SceneViewGuard {
+    mi_pt *pt;
+    DScene scene = pt->scene;
+    int metaStrategy = pt->metaStrategy;
+    ~SceneViewGuard() { pt->scene = scene; pt->metaStrategy = metaStrategy; }
 };
 
 // -----------------------------------------------------------------------------
@@ -4607,14 +4655,87 @@ int LaunchShade(mi_pt *pt, SubRenderer &sub, dim3 grid) {
         if (!pt->shadeClasses[i]) continue;
         const unsigned long long blocks = pt->shadeGridPool ? (unsigned long long)grid.x + MAX_CLASSES : ShadeGridBlocks(counts, pt->shadeClasses[i]);
         if (blocks == 0) continue;
-        const bool lens = pt->scene.lensDiff && kShadeInstances[i].kernelLens;   // (a realistic camera in front of textures: the twin that loads the stored differentials)
-        const bool motion = pt->scene.motions && kShadeInstances[i].kernelMotion;   // (moving instances: the twin that interpolates)
-        hipLaunchKernelGGL(motion ? (lens ? kShadeInstances[i].kernelMotionLens : kShadeInstances[i].kernelMotion)
-                                  : (lens ? kShadeInstances[i].kernelLens : kShadeInstances[i].kernel), dim3((unsigned)blocks), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, pt->shadeClasses[i]);
+        const ShadeInstance &si = kShadeInstances[i];
+        const bool lens = pt->scene.lensDiff && si.kernel[0][1];   // (a realistic camera in front of textures: the twin that loads the stored differentials)
+        const bool motion = pt->scene.motions && si.kernel[1][0];   // (moving instances: the twin that interpolates)
+        hipLaunchKernelGGL(si.kernel[motion][lens], dim3((unsigned)blocks), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, pt->shadeClasses[i]);
         ++sub.shadeLaunches;
         sub.shadeBlocks += blocks;
     }
     return MI_OK;
+}
+
+// Tiles of 16 samples along one axis of the sample bounds.
+int TilesAlong(const DScene &s, int axis) { return (s.sampleBounds[2 + axis] - s.sampleBounds[axis] + 15) / 16; }
+
+// The work of one pass of one sub-renderer: of the 16 x 16 tiles of the sample bounds every shardCount-th from shardIndex on,
+// `spp` samples from sample number `sampleBegin` in each of their pixels, handed out in runs (MIPT_WORK_RUN caps them).
+// mi_pt_debug_path asks the same way for the one tile of its pixel.
+WorkDesc PlanWork(const DScene &s, int shardIndex, int shardCount, long long spp, long long sampleBegin) {
+    WorkDesc wd{};
+    wd.nTilesX = TilesAlong(s, 0);
+    wd.nTilesY = TilesAlong(s, 1);
+    const int nTiles = wd.nTilesX * wd.nTilesY;
+    wd.shardIndex = shardIndex;
+    wd.shardCount = shardCount;
+    wd.nTilesShard = (wd.shardIndex < nTiles) ? (nTiles - wd.shardIndex + wd.shardCount - 1) / wd.shardCount : 0;
+    wd.spp = spp;
+    wd.sampleBegin = sampleBegin;
+    wd.totalWork = (unsigned long long)wd.nTilesShard * 256ull * (unsigned long long)wd.spp;
+    int runCap = 256;  // (round 3, with the dense film flush: 64 -> 256 takes 5 % off k_generate, killeroo +0.9 %, the 10M-triangle scene
+                       // +0.7 %, cornell-glass the same; 1024 measures as 256. Same-box A/B at the end of round 2: 16 -> 64 took 4 % off k_generate and 1 % off the camera-ray
+                       // traversal, the other kernels unchanged -- 3596 -> 3620 Mray/s; 128 ... 1024 measure the same as 64.
+                       // Earlier in the round longer runs cost the shading kernels 2-5 % and 16 was the optimum.)
+    if (const char *e = getenv("MIPT_WORK_RUN")) runCap = std::max(1, atoi(e));
+    wd.run = 1;
+    while (2 * wd.run <= runCap && wd.spp % (2 * wd.run) == 0) wd.run *= 2;
+    return wd;
+}
+
+// The pool of a render of `wd` on one of `subCount` sub-renderers, its slots of nQuadPlanes and nFloatPlanes: `pathPool` slots
+// in all (mi_render_params.path_pool), or by default what the work, the measurements below and the device's free memory
+// ask for. Allocated (EnsurePool) when this returns MI_OK, `poolN` slots.
+int SizePool(SubRenderer &sub, const WorkDesc &wd, uint32_t pathPool, int subCount, int nQuadPlanes, int nFloatPlanes, uint32_t &poolN) {
+    // Default pool: one slot per sample to render, up to the cap (earlier in round 2, at half: a 1/8 shard took 0.1196 s with the
+    // quarter's 16M slots, 0.1169 s with 32M), at most 96M slots in total (below)
+    // and at least 4M (8M per sub-renderer when several share the GPU): bigger pools mean fewer, better-filled
+    // launches, but the last iterations of a render drain the pool at low occupancy, which a small job (one
+    // shard of a multi-GPU frame) feels. Measured on the 1024-spp killeroo frame and its shards
+    // (tools/shard_tune.py): a 1/8 shard on four sub-renderers takes 0.149 s with 16M slots and 0.143 s with
+    // 32M; 64M slots (47 GB) make the traversal launches 3 % faster and k_shade / k_generate 4-6 % slower
+    // (the path state outgrows the TLB reach), no gain for the full frame.
+    poolN = pathPool;
+    if (poolN == 0) {
+        const unsigned long long quarter = wd.totalWork * (unsigned long long)subCount;   // (all of them: a 1/8 shard of the killeroo frame takes 0.1071 s on 32M slots, 0.1046 s on 64M)
+        const unsigned long long floorN = subCount > 1 ? (8ull << 20) * (unsigned long long)subCount : (1ull << 22);
+        // (`quarter`: half, since round 2.) The cap: 96M slots = 77 GB of path state of the 288 GB. With the kernels of the end
+        // of round 2 bigger pools pay again (fewer, longer launches: the persistent traversal kernels lose less to their
+        // tails, k_shade and k_generate no longer slow down): killeroo 1024 spp 3740 Mray/s at 32M, 3880 at 64M, 3912 at
+        // 96M, 3931 at 128M; the 10M-triangle scene +0.4 %, cornell-glass -0.3 % at 64M.
+        poolN = (uint32_t)std::min<unsigned long long>(3ull << 25, std::max<unsigned long long>(floorN, quarter));
+    }
+    poolN = std::max<uint32_t>(BLOCK, poolN / subCount / BLOCK * BLOCK);
+    if (pathPool == 0) {
+        // the default is a preference: it takes at most 65 % of what the device has free (counting what this sub-renderer's
+        // present pool would give back), so that what comes after the pool -- the film staging of the hand-over, RCCL's
+        // buffers at the first collective, another renderer in the process -- still finds memory
+        size_t freeB = 0, totalB = 0;
+        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+            const size_t budget = (size_t)(0.65 * (double)(freeB + sub.poolBytes)) / (size_t)subCount;
+            const size_t fit = budget / PoolSlotBytes(nQuadPlanes, nFloatPlanes) / BLOCK * BLOCK;
+            if (fit < poolN) poolN = (uint32_t)std::max<size_t>(fit, (size_t)BLOCK);
+        } else (void)hipGetLastError();
+    }
+    if (wd.totalWork < poolN) poolN = (uint32_t)((wd.totalWork + BLOCK - 1) / BLOCK * BLOCK);
+    if (poolN < BLOCK) poolN = BLOCK;
+    int rc = EnsurePool(sub, poolN, nQuadPlanes, nFloatPlanes);
+    // the default size is a preference, not a requirement: on a device that cannot hold it the render goes on with half,
+    // a quarter, ... (an explicit mi_render_params.path_pool is taken at its word and fails)
+    while (rc == MI_ERR_NOMEM && pathPool == 0 && poolN > (1u << 22)) {
+        poolN = poolN / 2 / BLOCK * BLOCK;
+        rc = EnsurePool(sub, poolN, nQuadPlanes, nFloatPlanes);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -4660,23 +4781,7 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
     HIPCHK(hipSetDevice(pt->device));
     hipStream_t st = sub.stream;
     const DScene &s = pt->scene;
-    WorkDesc wd{};
-    wd.nTilesX = (s.sampleBounds[2] - s.sampleBounds[0] + 15) / 16;
-    wd.nTilesY = (s.sampleBounds[3] - s.sampleBounds[1] + 15) / 16;
-    const int nTiles = wd.nTilesX * wd.nTilesY;
-    wd.shardIndex = rp->shard_index + rp->shard_count * subIndex;
-    wd.shardCount = rp->shard_count * subCount;
-    wd.nTilesShard = (wd.shardIndex < nTiles) ? (nTiles - wd.shardIndex + wd.shardCount - 1) / wd.shardCount : 0;
-    wd.spp = PassSpp(pt, rp);
-    wd.sampleBegin = rp->sample_begin;
-    wd.totalWork = (unsigned long long)wd.nTilesShard * 256ull * (unsigned long long)wd.spp;
-    int runCap = 256;  // (round 3, with the dense film flush: 64 -> 256 takes 5 % off k_generate, killeroo +0.9 %, the 10M-triangle scene
-                       // +0.7 %, cornell-glass the same; 1024 measures as 256. Same-box A/B at the end of round 2: 16 -> 64 took 4 % off k_generate and 1 % off the camera-ray
-                       // traversal, the other kernels unchanged -- 3596 -> 3620 Mray/s; 128 ... 1024 measure the same as 64.
-                       // Earlier in the round longer runs cost the shading kernels 2-5 % and 16 was the optimum.)
-    if (const char *e = getenv("MIPT_WORK_RUN")) runCap = std::max(1, atoi(e));
-    wd.run = 1;
-    while (2 * wd.run <= runCap && wd.spp % (2 * wd.run) == 0) wd.run *= 2;
+    const WorkDesc wd = PlanWork(s, rp->shard_index + rp->shard_count * subIndex, rp->shard_count * subCount, PassSpp(pt, rp), rp->sample_begin);
     sub.iterations = 0;
     sub.shadeLaunches = sub.shadeBlocks = 0;
     // (a render that failed half way may have left the dark stream busy: nothing of it may meet this render's clears)
@@ -4686,69 +4791,30 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
     for (double &t : sub.t) t = 0;
     sub.result = DevCounters{};
     if (wd.totalWork == 0) return MI_OK;
-    // Default pool: one slot per sample to render, up to the cap (earlier in round 2, at half: a 1/8 shard took 0.1196 s with the
-    // quarter's 16M slots, 0.1169 s with 32M), at most 96M slots in total (below)
-    // and at least 4M (8M per sub-renderer when several share the GPU): bigger pools mean fewer, better-filled
-    // launches, but the last iterations of a render drain the pool at low occupancy, which a small job (one
-    // shard of a multi-GPU frame) feels. Measured on the 1024-spp killeroo frame and its shards
-    // (tools/shard_tune.py): a 1/8 shard on four sub-renderers takes 0.149 s with 16M slots and 0.143 s with
-    // 32M; 64M slots (47 GB) make the traversal launches 3 % faster and k_shade / k_generate 4-6 % slower
-    // (the path state outgrows the TLB reach), no gain for the full frame.
-    uint32_t poolN = rp->path_pool;
-    if (poolN == 0) {
-        const unsigned long long quarter = wd.totalWork * (unsigned long long)subCount;   // (all of them: a 1/8 shard of the killeroo frame takes 0.1071 s on 32M slots, 0.1046 s on 64M)
-        const unsigned long long floorN = subCount > 1 ? (8ull << 20) * (unsigned long long)subCount : (1ull << 22);
-        // (`quarter`: half, since round 2.) The cap: 96M slots = 77 GB of path state of the 288 GB. With the kernels of the end
-        // of round 2 bigger pools pay again (fewer, longer launches: the persistent traversal kernels lose less to their
-        // tails, k_shade and k_generate no longer slow down): killeroo 1024 spp 3740 Mray/s at 32M, 3880 at 64M, 3912 at
-        // 96M, 3931 at 128M; the 10M-triangle scene +0.4 %, cornell-glass -0.3 % at 64M.
-        poolN = (uint32_t)std::min<unsigned long long>(3ull << 25, std::max<unsigned long long>(floorN, quarter));
-    }
-    poolN = std::max<uint32_t>(BLOCK, poolN / subCount / BLOCK * BLOCK);
-    if (rp->path_pool == 0) {
-        // the default is a preference: it takes at most 65 % of what the device has free (counting what this sub-renderer's
-        // present pool would give back), so that what comes after the pool -- the film staging of the hand-over, RCCL's
-        // buffers at the first collective, another renderer in the process -- still finds memory
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-            const size_t budget = (size_t)(0.65 * (double)(freeB + sub.poolBytes)) / (size_t)subCount;
-            const size_t fit = budget / PoolSlotBytes(QuadPlanes(s), FloatPlanes(s)) / BLOCK * BLOCK;
-            if (fit < poolN) poolN = (uint32_t)std::max<size_t>(fit, (size_t)BLOCK);
-        } else (void)hipGetLastError();
-    }
-    if (wd.totalWork < poolN) poolN = (uint32_t)((wd.totalWork + BLOCK - 1) / BLOCK * BLOCK);
-    if (poolN < BLOCK) poolN = BLOCK;
-    int rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
-    // the default size is a preference, not a requirement: on a device that cannot hold it the render goes on with half,
-    // a quarter, ... (an explicit mi_render_params.path_pool is taken at its word and fails)
-    while (rc == MI_ERR_NOMEM && rp->path_pool == 0 && poolN > (1u << 22)) {
-        poolN = poolN / 2 / BLOCK * BLOCK;
-        rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
-    }
+    uint32_t poolN = 0;
+    int rc = SizePool(sub, wd, rp->path_pool, subCount, QuadPlanes(s), FloatPlanes(s), poolN);
     if (rc != MI_OK) return rc;
     HIPCHK(hipMemsetAsync(sub.pool.i + (size_t)I_FLAGS * poolN, 0, (size_t)poolN * sizeof(int), st));
     HIPCHK(hipMemsetAsync(sub.ctr, 0, sizeof(DevCounters), st));
     const dim3 grid((poolN + BLOCK - 1) / BLOCK), block(BLOCK);
     const dim3 chunkGrid((grid.x + SLOT_CHUNKS - 1) / SLOT_CHUNKS);   // kernels that take SLOT_CHUNKS x 256 slots per block
     const dim3 travGrid(std::min<unsigned>(grid.x, (unsigned)pt->numCUs * TRAV_BLOCKS_PER_CU));
-    unsigned alive = 1;
-    unsigned long long drawn = 0;
     // Per-kernel-class time: HIP events at the kernel boundaries of every iteration,
     // read back after the per-iteration sync that the alive counter needs anyway.
-    auto harvest = [&](int set, bool full) {
+    // (first event, second event, the class in SubRenderer::t that the time between them goes to)
+    static const int kSpans[][3] = {{0, 1, 1}, {1, 2, 2}, {2, 3, 3}, {3, 4, 4}, {4, 5, 5},
+                                    // the closest-hit traversal launch alone: from an event recorded right before it (after the host's
+                                    // per-iteration read of `alive`), so the host round trip is in [2] but not in [6]
+                                    {7, 6, 6}};
+    auto harvest = [&](int set, bool full) {   // (`full`: the iteration went on past k_generate, whose span comes first)
         float ms = 0;
-        hipEventElapsedTime(&ms, sub.evIter[set][0], sub.evIter[set][1]); sub.t[1] += ms * 1e-3;
-        if (!full) return;
-        hipEventElapsedTime(&ms, sub.evIter[set][1], sub.evIter[set][2]); sub.t[2] += ms * 1e-3;
-        hipEventElapsedTime(&ms, sub.evIter[set][2], sub.evIter[set][3]); sub.t[3] += ms * 1e-3;
-        hipEventElapsedTime(&ms, sub.evIter[set][3], sub.evIter[set][4]); sub.t[4] += ms * 1e-3;
-        hipEventElapsedTime(&ms, sub.evIter[set][4], sub.evIter[set][5]); sub.t[5] += ms * 1e-3;
-        // the closest-hit traversal launch alone: from an event recorded right before it (after the host's
-        // per-iteration read of `alive`), so the host round trip is in [2] but not in [6]
-        hipEventElapsedTime(&ms, sub.evIter[set][7], sub.evIter[set][6]); sub.t[6] += ms * 1e-3;
+        for (const int (&sp)[3] : kSpans) {
+            hipEventElapsedTime(&ms, sub.evIter[set][sp[0]], sub.evIter[set][sp[1]]); sub.t[sp[2]] += ms * 1e-3;
+            if (!full) return;
+        }
     };
     int set = 0;
-    bool prevFull = false, havePrev = false;
+    bool havePrev = false;   // the other event set holds a full iteration whose times are not in sub.t yet
     while (true) {
         hipEvent_t *ev = sub.evIter[set];
         HIPCHK(hipMemsetAsync(&sub.ctr->alive, 0, ITER_CLEAR_BYTES, st));
@@ -4756,40 +4822,44 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
         hipLaunchKernelGGL(GenerateKernelOf(s), chunkGrid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
         HIPCHK(hipEventRecord(ev[1], st));
         HIPCHK(hipMemcpyAsync(&sub.reads->alive, &sub.ctr->alive.v, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&sub.reads->drawn, &sub.ctr->nextWork, sizeof(drawn), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&sub.reads->drawn, &sub.ctr->nextWork, sizeof(sub.reads->drawn), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        alive = sub.reads->alive; drawn = sub.reads->drawn;
-        if (havePrev) harvest(set ^ 1, prevFull);
+        const unsigned alive = sub.reads->alive;
+        const unsigned long long drawn = sub.reads->drawn;
+        if (havePrev) harvest(set ^ 1, true);
         // done when no path is alive and every work item has been drawn (an iteration can draw nothing but items outside
         // the pixel bounds and leave the pool empty with work still to hand out)
-        if (alive == 0 && drawn >= wd.totalWork) { harvest(set, false); break; }
-        if (alive == 0) { harvest(set, false); havePrev = false; set ^= 1; if (++sub.iterations > 100000000ull) { g_err = "render loop did not terminate"; return MI_ERR_HIP; } continue; }
-        HIPCHK(hipEventRecord(ev[7], st));
-        LaunchTraversal(pt, sub, 0, travGrid);
-        HIPCHK(hipEventRecord(ev[6], st));
-        LaunchResolve(pt, sub, 0, chunkGrid);
-        HIPCHK(hipEventRecord(ev[2], st));
-        if (pt->metaStrategy >= 0) {   // a metadata pass: the hit is the answer (its commit is timed as the shade class; no shadow or MIS rays)
-            LaunchMetadataCommit(pt, sub, grid);
-            HIPCHK(hipEventRecord(ev[3], st));
-            HIPCHK(hipEventRecord(ev[4], st));
-            HIPCHK(hipEventRecord(ev[5], st));
+        if (alive == 0) {
+            harvest(set, false);
+            if (drawn >= wd.totalWork) break;
         } else {
-            const bool darkBeside = s.misAny && !pt->darkInLine;
-            if ((rc = LaunchShade(pt, sub, grid)) != MI_OK) return rc;
-            HIPCHK(hipEventRecord(ev[3], st));
-            if (darkBeside && !MIPT_DARK_AFTER_SHADOW && (rc = LaunchDarkBeside(pt, sub, grid.x)) != MI_OK) return rc;
-            LaunchTraversal(pt, sub, 1, travGrid);
-            LaunchResolve(pt, sub, 1, grid);
-            HIPCHK(hipEventRecord(ev[4], st));
-            if (darkBeside && MIPT_DARK_AFTER_SHADOW && (rc = LaunchDarkBeside(pt, sub, grid.x)) != MI_OK) return rc;
-            LaunchTraversal(pt, sub, 2, travGrid);
-            LaunchResolve(pt, sub, 2, grid);
-            if (s.misAny && pt->darkInLine && (rc = LaunchDarkInLine(pt, sub, travGrid)) != MI_OK) return rc;
-            HIPCHK(hipEventRecord(ev[5], st));
+            HIPCHK(hipEventRecord(ev[7], st));
+            LaunchTraversal(pt, sub, 0, travGrid);
+            HIPCHK(hipEventRecord(ev[6], st));
+            LaunchResolve(pt, sub, 0, chunkGrid);
+            HIPCHK(hipEventRecord(ev[2], st));
+            if (pt->metaStrategy >= 0) {   // a metadata pass: the hit is the answer (its commit is timed as the shade class; no shadow or MIS rays)
+                LaunchMetadataCommit(pt, sub, grid);
+                HIPCHK(hipEventRecord(ev[3], st));
+                HIPCHK(hipEventRecord(ev[4], st));
+                HIPCHK(hipEventRecord(ev[5], st));
+            } else {
+                const bool darkBeside = s.misAny && !pt->darkInLine;
+                if ((rc = LaunchShade(pt, sub, grid)) != MI_OK) return rc;
+                HIPCHK(hipEventRecord(ev[3], st));
+                if (darkBeside && !MIPT_DARK_AFTER_SHADOW && (rc = LaunchDarkBeside(pt, sub, grid.x)) != MI_OK) return rc;
+                LaunchTraversal(pt, sub, 1, travGrid);
+                LaunchResolve(pt, sub, 1, grid);
+                HIPCHK(hipEventRecord(ev[4], st));
+                if (darkBeside && MIPT_DARK_AFTER_SHADOW && (rc = LaunchDarkBeside(pt, sub, grid.x)) != MI_OK) return rc;
+                LaunchTraversal(pt, sub, 2, travGrid);
+                LaunchResolve(pt, sub, 2, grid);
+                if (s.misAny && pt->darkInLine && (rc = LaunchDarkInLine(pt, sub, travGrid)) != MI_OK) return rc;
+                HIPCHK(hipEventRecord(ev[5], st));
+            }
+            HIPCHK(hipGetLastError());   // a launch of this iteration that was refused (bad configuration) stops the render here
         }
-        HIPCHK(hipGetLastError());   // a launch of this iteration that was refused (bad configuration) stops the render here
-        havePrev = true; prevFull = true;
+        havePrev = alive != 0;
         set ^= 1;
         if (++sub.iterations > 100000000ull) { g_err = "render loop did not terminate"; return MI_ERR_HIP; }
     }
@@ -4914,7 +4984,7 @@ int mi_pt_render_metadata(mi_pt *pt, const mi_render_params *rp, int strategy, f
     }
     // the pass's own view of the scene, as mi_pt_debug_path takes one: no depth limit ends a hit before the commit
     // (EndsUnshaded), one ray per camera sample whatever "spectralpath" asks for
-    struct Restore { mi_pt *pt; DScene s; ~Restore() { pt->scene = s; pt->metaStrategy = -1; } } restore{pt, pt->scene};
+    SceneViewGuard restore{pt};
     pt->scene.maxDepth = 255;
     pt->scene.nBands = 1;
     pt->scene.bandDelta = MI_NSPEC;
@@ -4948,16 +5018,9 @@ int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *querie
     if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
     if (pt->textureTypes[tex] != MI_TEX_IMAGEMAP) { g_err = "mi_pt_texture_lookup: not an image texture"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(pt->device));
-    DevBuf dq, dout;
-    HIPCHK(dq.alloc((size_t)n * 6 * sizeof(float)));
-    HIPCHK(dout.alloc((size_t)n * 3 * sizeof(float)));
-    HIPCHK(hipMemcpy(dq.p, queries, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_texture_lookup, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, tex, dq.as<float>(), n, dout.as<float>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(rgb, dout.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return RunProbe(pt->device, queries, (size_t)n * 6 * sizeof(float), rgb, (size_t)n * 3 * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_texture_lookup, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, tex, (float *)dq, n, (float *)dout);
+    });
 }
 
 int mi_pt_texture_probe(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *out) {
@@ -4966,16 +5029,9 @@ int mi_pt_texture_probe(mi_pt *pt, int32_t tex, uint32_t n, const float *queries
     if (!MI_TEX_IS_NOISE(pt->textureTypes[tex])) { g_err = "mi_pt_texture_probe: not a noise texture"; return MI_ERR_INVALID; }
     if (n > (1u << 24)) { g_err = "mi_pt_texture_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(pt->device));
-    DevBuf dq, dout;
-    HIPCHK(dq.alloc((size_t)n * 9 * sizeof(float)));
-    HIPCHK(dout.alloc((size_t)n * sizeof(float)));
-    HIPCHK(hipMemcpy(dq.p, queries, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_texture_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, (int)tex, dq.as<float>(), n, dout.as<float>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return RunProbe(pt->device, queries, (size_t)n * 9 * sizeof(float), out, (size_t)n * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_texture_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)tex, (float *)dq, n, (float *)dout);
+    });
 }
 
 int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, const float *queries, float *out) {
@@ -4986,16 +5042,9 @@ int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, cons
     if (n == 0) return MI_OK;
     const size_t nIn = mode == 0 ? 7 : (mode == 1 ? 5 : 6);
     const size_t nOut = mode == 0 ? MI_SHAPE_PROBE_HIT_FLOATS : (mode == 1 ? MI_SHAPE_PROBE_SAMPLE_FLOATS : 1);
-    HIPCHK(hipSetDevice(pt->device));
-    DevBuf dq, dout;
-    HIPCHK(dq.alloc((size_t)n * nIn * sizeof(float)));
-    HIPCHK(dout.alloc((size_t)n * nOut * sizeof(float)));
-    HIPCHK(hipMemcpy(dq.p, queries, (size_t)n * nIn * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_shape_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, (int)quadric, (int)mode, dq.as<float>(), n, dout.as<float>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * nOut * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return RunProbe(pt->device, queries, (size_t)n * nIn * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_shape_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)quadric, (int)mode, (float *)dq, n, (float *)dout);
+    });
 }
 
 int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const float *queries, float *out) {
@@ -5009,16 +5058,9 @@ int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const 
     if (n == 0) return MI_OK;
     const size_t nIn = mode == 0 ? 8 : (mode == 1 ? 9 : (type == MI_LIGHT_INFINITE ? 3 : 6));
     const size_t nOut = mode == 0 ? MI_LIGHT_PROBE_SAMPLE_FLOATS : (mode == 1 ? 1 : MI_NSPEC);
-    HIPCHK(hipSetDevice(pt->device));
-    DevBuf dq, dout;
-    HIPCHK(dq.alloc((size_t)n * nIn * sizeof(float)));
-    HIPCHK(dout.alloc((size_t)n * nOut * sizeof(float)));
-    HIPCHK(hipMemcpy(dq.p, queries, (size_t)n * nIn * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_light_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, (int)light, (int)mode, dq.as<float>(), n, dout.as<float>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * nOut * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return RunProbe(pt->device, queries, (size_t)n * nIn * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_light_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)light, (int)mode, (float *)dq, n, (float *)dout);
+    });
 }
 
 int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out) {
@@ -5033,25 +5075,10 @@ int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out)
         for (uint32_t i = 0; i < n; ++i) memcpy(out + 8 * (size_t)i, ex.data() + (size_t)i * MI_CAMERA_RAY_EX_FLOATS, 8 * sizeof(float));
         return MI_OK;
     }
-    for (uint32_t i = 0; i < n; ++i) {   // the pixel indexes per-pixel tables (Halton offsets, a pixel sampler's tables): inside the sample bounds
-        const int px = samples[3 * i], py = samples[3 * i + 1];
-        if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3] || samples[3 * i + 2] < 0 ||
-            (s.samplerType >= MI_SAMPLER_ZEROTWO && samples[3 * i + 2] >= pt->spp)) {
-            g_err = "mi_pt_camera_rays: a sample lies outside the sample bounds (or beyond a pixel sampler's tables)";
-            return MI_ERR_INVALID;
-        }
-    }
-    HIPCHK(hipSetDevice(pt->device));
-    DevBuf ds, dout;
-    HIPCHK(ds.alloc((size_t)n * 3 * sizeof(int32_t)));
-    HIPCHK(dout.alloc((size_t)n * 8 * sizeof(float)));
-    HIPCHK(hipMemcpy(ds.p, samples, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL((s.camera.animated ? k_camera_rays<true> : k_camera_rays<false>), dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, s,
-                       ds.as<int32_t>(), n, dout.as<float>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    if (const int rc = CheckCameraSamples(pt, samples, n, "mi_pt_camera_rays")) return rc;
+    return RunProbe(pt->device, samples, (size_t)n * 3 * sizeof(int32_t), out, (size_t)n * 8 * sizeof(float), [&](void *ds, void *dout) {
+        hipLaunchKernelGGL((s.camera.animated ? k_camera_rays<true> : k_camera_rays<false>), ProbeGrid(n), dim3(BLOCK), 0, 0, s, (int32_t *)ds, n, (float *)dout);
+    });
 }
 
 int mi_pt_camera_rays_ex(mi_pt *pt, const int32_t *samples, uint32_t n, int32_t band, float *out) {
@@ -5060,27 +5087,13 @@ int mi_pt_camera_rays_ex(mi_pt *pt, const int32_t *samples, uint32_t n, int32_t 
     const DScene &s = pt->scene;
     if (band < 0 || band >= std::max(1, s.nBands)) { g_err = "mi_pt_camera_rays_ex: no such band"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
-    for (uint32_t i = 0; i < n; ++i) {
-        const int px = samples[3 * i], py = samples[3 * i + 1];
-        if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3] || samples[3 * i + 2] < 0 ||
-            (s.samplerType >= MI_SAMPLER_ZEROTWO && samples[3 * i + 2] >= pt->spp)) {
-            g_err = "mi_pt_camera_rays_ex: a sample lies outside the sample bounds (or beyond a pixel sampler's tables)";
-            return MI_ERR_INVALID;
-        }
-    }
-    HIPCHK(hipSetDevice(pt->device));
-    DevBuf ds, dout;
-    HIPCHK(ds.alloc((size_t)n * 3 * sizeof(int32_t)));
-    HIPCHK(dout.alloc((size_t)n * MI_CAMERA_RAY_EX_FLOATS * sizeof(float)));
-    HIPCHK(hipMemcpy(ds.p, samples, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (const int rc = CheckCameraSamples(pt, samples, n, "mi_pt_camera_rays_ex")) return rc;
     const bool real = s.cameraType == MI_CAMERA_REALISTIC, moving = s.camera.animated != 0;
     auto kernel = real ? (moving ? k_camera_rays_ex<true, true> : k_camera_rays_ex<false, true>)
                        : (moving ? k_camera_rays_ex<true, false> : k_camera_rays_ex<false, false>);
-    hipLaunchKernelGGL(kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, s, ds.as<int32_t>(), n, (int)band, dout.as<float>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * MI_CAMERA_RAY_EX_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return RunProbe(pt->device, samples, (size_t)n * 3 * sizeof(int32_t), out, (size_t)n * MI_CAMERA_RAY_EX_FLOATS * sizeof(float), [&](void *ds, void *dout) {
+        hipLaunchKernelGGL(kernel, ProbeGrid(n), dim3(BLOCK), 0, 0, s, (int32_t *)ds, n, (int)band, (float *)dout);
+    });
 }
 
 // Parity tools for the shading plan (include/mi_pt.h): host code only.
@@ -5184,24 +5197,16 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
     *n_records = 0;
     HIPCHK(hipSetDevice(pt->device));
     ReadQueueBlocksCap(pt);
-    const DScene saved = pt->scene;
-    struct Restore { mi_pt *pt; DScene s; ~Restore() { pt->scene = s; } } restore{pt, saved};
+    SceneViewGuard restore{pt};
     DScene &s = pt->scene;
     if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3]) { g_err = "pixel outside the sample bounds"; return MI_ERR_INVALID; }
     s.pixelBounds[0] = px; s.pixelBounds[1] = py; s.pixelBounds[2] = px + 1; s.pixelBounds[3] = py + 1;
     s.index32 = 0; s.storePixelSample = 1;
     SubRenderer &sub = pt->subs[0];
     hipStream_t st = sub.stream;
-    WorkDesc wd{};
-    wd.nTilesX = (s.sampleBounds[2] - s.sampleBounds[0] + 15) / 16;
-    wd.nTilesY = (s.sampleBounds[3] - s.sampleBounds[1] + 15) / 16;
-    wd.shardIndex = ((py - s.sampleBounds[1]) / 16) * wd.nTilesX + (px - s.sampleBounds[0]) / 16;   // the pixel's tile alone
-    wd.shardCount = wd.nTilesX * wd.nTilesY;
-    wd.nTilesShard = 1;
-    wd.spp = 1;
-    wd.run = 1;
-    wd.sampleBegin = sample;
-    wd.totalWork = 256;
+    // the pixel's tile alone: a shard of its own among as many shards as there are tiles, one sample per pixel (256 work items)
+    const int tile = ((py - s.sampleBounds[1]) / 16) * TilesAlong(s, 0) + (px - s.sampleBounds[0]) / 16;
+    const WorkDesc wd = PlanWork(s, tile, TilesAlong(s, 0) * TilesAlong(s, 1), 1, sample);
     const uint32_t poolN = BLOCK;
     int rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
     if (rc != MI_OK) return rc;
@@ -5264,8 +5269,7 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
         if (!(fl & F_L_ZERO)) HIPCHK(Spec((fl & F_L_IN_B) ? Q_LB : Q_L, slot, r + 51));
         ++*n_records;
     }
-    FreePool(sub.pool);   // the next render sizes its own
-    sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0;
+    ReleasePool(sub);   // the next render sizes its own
     HIPCHK(hipMemset(pt->film, 0, pt->nPix * 32 * sizeof(float)));
     return MI_OK;
 }
@@ -5273,16 +5277,9 @@ int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t 
 static int TraceRays(mi_pt *pt, const float *rays, int stride, uint32_t n, int any_hit, float *hits) {
     if (!pt || !rays || !hits) { g_err = "null argument"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
-    HIPCHK(hipSetDevice(pt->device));
-    DevBuf dr, dh;
-    HIPCHK(dr.alloc((size_t)n * stride * sizeof(float)));
-    HIPCHK(dh.alloc((size_t)n * 4 * sizeof(float)));
-    HIPCHK(hipMemcpy(dr.p, rays, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_trace, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, pt->scene, dr.as<float>(), n, any_hit, dh.as<float>(), stride);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(hits, dh.p, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
+    return RunProbe(pt->device, rays, (size_t)n * stride * sizeof(float), hits, (size_t)n * 4 * sizeof(float), [&](void *dr, void *dh) {
+        hipLaunchKernelGGL(k_trace, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (float *)dr, n, any_hit, (float *)dh, stride);
+    });
 }
 
 int mi_pt_trace(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits) { return TraceRays(pt, rays, 7, n, any_hit, hits); }
@@ -5294,7 +5291,7 @@ int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, con
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || device_ordinal < 0 || device_ordinal >= nDev) { g_err = "no HIP device available (this path has no CPU fallback)"; return MI_ERR_NO_DEVICE; }
     HIPCHK(hipSetDevice(device_ordinal));
-    DevBuf dx, dy, dout;
+    DevBuf dx, dy, dout;   // (two inputs: not RunProbe's shape)
     HIPCHK(dx.alloc((size_t)n * 2 * sizeof(float)));
     HIPCHK(dy.alloc((size_t)n * 2 * sizeof(float)));
     HIPCHK(dout.alloc((size_t)n * 3 * sizeof(float)));
@@ -5332,7 +5329,7 @@ static int TraceWavefront(mi_pt *pt, const float *rays, int stride, uint32_t n, 
     const uint32_t poolN = (n + SLOT_CHUNKS * BLOCK - 1) / (SLOT_CHUNKS * BLOCK) * (SLOT_CHUNKS * BLOCK);
     int rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
     if (rc != MI_OK) return rc;
-    struct PoolGuard { SubRenderer &sub; ~PoolGuard() { FreePool(sub.pool); sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0; } } guard{sub};   // the next render sizes its own
+    struct PoolGuard { SubRenderer &sub; ~PoolGuard() { ReleasePool(sub); } } guard{sub};   // the next render sizes its own
     DevBuf dr, dh, dx;
     HIPCHK(dr.alloc((size_t)n * stride * sizeof(float)));
     HIPCHK(dh.alloc((size_t)n * 4 * sizeof(float)));
@@ -5364,7 +5361,7 @@ void mi_pt_destroy(mi_pt *pt) {
     if (pt->stageSum) hipFree(pt->stageSum);
     if (pt->stageW) hipFree(pt->stageW);
     for (SubRenderer &sub : pt->subs) {
-        FreePool(sub.pool);
+        ReleasePool(sub);
         for (int a = 0; a < 2; ++a) for (int b = 0; b < N_EV; ++b) if (sub.evIter[a][b]) hipEventDestroy(sub.evIter[a][b]);
         if (sub.stream) hipStreamDestroy(sub.stream);
         // (the hipDeviceSynchronize above has joined the dark stream, after a failed create or render as well)
