@@ -1,6 +1,6 @@
 // scene.h -- the host front end's flat scene: owning storage behind the POD
 // mi_scene_desc that crosses the C ABI (include/mi_pt.h). Produced by the .pbrt
-// front end (api.cpp) the way pbrtWorldEnd() produces Scene + Integrator in the
+// front end (parser.cpp, api.cpp, world_end.cpp) the way pbrtWorldEnd() produces Scene + Integrator in the
 // reference (src/core/api.cpp:1617-1737), but as flat arrays because the
 // reference's Scene/BVHAccel internals are private.
 #pragma once
@@ -121,9 +121,6 @@ bool BuildRealisticLens(std::vector<float> lensData, float apertureDiameter, flo
 // Light-selection distributions, src/core/lightdistrib.cpp:48-300.
 void BuildLightDistribution(HostScene *scene, const std::string &strategy);
 
-// Material compilation (constant textures -> fixed BxDF list),
-// src/materials/{matte,plastic,glass,uber,disney,mirror}.cpp.
-// Returns false (and appends to errs) for materials this path does not cover.
 // Shape "plymesh" (plymesh.cpp)
 struct PLYMeshData {
     std::vector<int> indices;
@@ -144,6 +141,9 @@ bool BuildEnvMap(const Spectrum &L, const std::string &texmap, HostEnvMap *store
 bool BuildProjectionMap(const std::string &texmap, HostEnvMap *store, int *rx, int *ry, Spectrum *centre, std::string *err);
 bool WriteRGBImage(const std::string &filename, int w, int h, const float *filmSum, const float *weightSum, float scale,
                    std::string *written, std::string *err);
+// Material compilation (constant textures -> fixed BxDF list),
+// src/materials/{matte,plastic,glass,uber,disney,mirror}.cpp.
+// Returns false (and appends to errs) for materials this path does not cover.
 bool CompileMixMaterial(const mi_material &m1, const mi_material &m2, const Spectrum &amount, mi_material *out,
                         std::vector<std::string> *errs);
 bool CompileMaterial(const std::string &type, const TextureParams &mp, mi_material *out,
