@@ -841,6 +841,54 @@ DEV float4 SimpleEvalQuad(const SimpleLobes<NL> &sl, const mi_bxdf *bx, int c, D
 // `acc |= bits(|x|)`: acc != 0 afterwards iff some x was != 0 (a NaN counts, as in `x != 0.f`)
 DEV void OrNonZero(unsigned &acc, float x) { acc |= __float_as_uint(x) & 0x7fffffffu; }
 
+// The divisors of an estimate: the sampling pdf, then the light-choice pdf unless it is 1 (x / 1 == x: the division is skipped).
+struct PdfChain {
+    Divisor pdf, sel;
+    bool selIsOne, allSelOne, fast;   // allSelOne: for every lane of the wave that is here; fast: the lane's divisors are all in DivBy's fast range
+};
+DEV PdfChain MakePdfChain(const Divisor &pdf, const Divisor &sel, bool selIsOne) { return PdfChain{pdf, sel, selIsOne, (bool)__all(selIsOne), pdf.fast && (selIsOne || sel.fast)}; }
+DEV PdfChain MakePdfChain(const Divisor &pdf) { return PdfChain{pdf, pdf, true, true, pdf.fast}; }   // (no light was chosen: the continuation)
+DEV float DivChainExact(float x, const PdfChain &ch) {
+    float q = DivBy(x, ch.pdf);
+    if (!ch.selIsOne) q = DivBy(q, ch.sel);
+    return q;
+}
+template <bool EXACT>
+DEV float DivChain(float x, const PdfChain &ch, DivTrack &trk) {
+    if constexpr (EXACT) return DivChainExact(x, ch);
+    float q = DivFast(x, ch.pdf.d, ch.pdf.r, trk);
+    if (!ch.allSelOne) { const float q2 = DivFast(q, ch.sel.d, ch.sel.r, trk); q = ch.selIsOne ? q : q2; }
+    return q;
+}
+// The straight-line form of a pass (SimpleLobes, above): a quad is formed with DivFast first and, if a quotient of some
+// lane left DivBy's fast range, redone with DivBy. Each pass writes the three-line retry loop out itself: its generic quad
+// lambda handed to a function template compiled the four TM_DIFFUSE instances to 288-368 B of private segment for 256 / 288
+// and 105-191 scratch instructions for 69-100 (compile-time figures; not measured on the GPU).
+template <int NL>
+struct StraightPass {
+    SimpleLobes<NL> sl;
+    const mi_bxdf *bx;
+    bool divFast;   // the lobes' divisors and the chain's are all in the fast range
+};
+template <int NL, unsigned TM>
+DEV StraightPass<NL> MakeStraightPass(const BSDFEvalT<NL> &ev, const mi_bxdf *bx, const PdfChain &ch) {
+    StraightPass<NL> sp = {MakeSimpleLobes<NL, TM>(ev), bx, false};
+    sp.divFast = sp.sl.divisorsFast && ch.fast;
+    return sp;
+}
+// A quad's prologue: the tracker reset, f of the quad, bin 31 (which does not exist: the last quad's fourth word) zeroed.
+// withChain: the pass divides f by its pdf chain (the dark MIS pass only asks whether f is black).
+template <int NL, unsigned TM, bool EXACT>
+DEV float4 StraightQuadF(const StraightPass<NL> &sp, bool withChain, int c, bool lastQuad, DivTrack &trk) {
+    trk.Reset(withChain ? sp.divFast : sp.sl.divisorsFast);
+    float4 fq = SimpleEvalQuad<NL, TM, EXACT>(sp.sl, sp.bx, c, trk);
+    if (lastQuad) fq.w = 0.f;
+    return fq;
+}
+// A quad's epilogue: the fast form holds if no lane of the wave left the fast range (the exact form always does).
+template <bool EXACT>
+DEV bool QuadHolds(const DivTrack &trk) { return EXACT || !__any(trk.Bad()); }
+
 // BSDF::f(woW, wiW, flags) (reflection.cpp:670-683) summed lobe by lobe into the caller's spectrum (rd(c) / wr(c, quad): quad c of
 // the lane's column of the LDS tile), for the instances with more than two lobes: ONE lobe description alive at a time and
 // one copy of LobeF's switch, where the list form keeps NL descriptions (73 registers at NL = 8, indexed at run time: the

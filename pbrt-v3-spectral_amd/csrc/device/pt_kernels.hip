@@ -2023,6 +2023,51 @@ DEV void HitInteraction(const DScene &s, int prim, const V3 &ro, const V3 &rd, f
     else { float t; QuadricInteraction<DISKS>(s, ~p.shape, ro, rd, kInfinity, si, &t); }
 }
 
+// The hit vertex in world space. A hit inside an object instance: the interaction is built with the ray in the instance's
+// space and taken to the world by InstanceToWorld (TransformedPrimitive::Intersect, primitive.cpp:78-92). The only place that
+// chooses between the matrices of a moving instance (both of Interpolate(ray.time), held as values) and the record of a static one.
+// (The interactions and the moving instance's matrices are objects of their own, neither members nor pointed to by one: they
+// are indexed at run time, which keeps them in private memory, and as members they took the whole vertex there: +176 B of
+// private segment per instance; a stored pointer to the matrices still cost 16 B.)
+// MOTION (TM_INSTANCES instances only): the scene has moving instances -- a hit inside one is carried by the two matrices of
+// Interpolate(ray time), held as values. The MOTION = false instances read the instance's record in place.
+template <bool MOTION>
+struct MovingMatrices { float w2i[MOTION ? 16 : 1], i2w[MOTION ? 16 : 1]; };
+template <bool INST, bool MOTION>
+struct HitVertex {
+    V3 ro, rd;
+    int inst;
+    V3 roS, rdS;   // the ray in the space the hit shape was intersected in
+    DEV const float *W2I(const DScene &s, const MovingMatrices<MOTION> &mm) const { if constexpr (MOTION) return mm.w2i; else return s.instances[inst].w2i; }
+    DEV const float *I2W(const DScene &s, const MovingMatrices<MOTION> &mm) const { if constexpr (MOTION) return mm.i2w; else return s.instances[inst].i2w; }
+};
+// isectObj (may be null): the interaction in the instance's space, set for inst >= 0.
+template <bool DISKS, bool INST, bool MOTION>
+DEV void BuildHitVertex(const DScene &s, const Pool &pool, uint32_t slot, int prim, const float4 &ray0, const float4 &ray1, bool needIsect,
+                        MovingMatrices<MOTION> &mm, HitVertex<INST, MOTION> &hv, SurfaceInteraction *isect, SurfaceInteraction *isectObj) {
+    hv.ro = V3(ray0.x, ray0.y, ray0.z); hv.rd = V3(ray1.x, ray1.y, ray1.z);
+    hv.inst = -1;
+    hv.roS = hv.ro; hv.rdS = hv.rd;
+    if constexpr (INST) {
+        if (needIsect) hv.inst = pool.I(I_HITINST, slot);
+        if (hv.inst >= 0) {
+            if constexpr (MOTION) {
+                const float time = PathTime(s, pool, slot);
+                InstanceW2I(s, hv.inst, time, mm.w2i);
+                InstanceI2W(s, hv.inst, time, mm.i2w);
+            }
+            const Ray ir = XfRay(hv.W2I(s, mm), Ray(hv.ro, hv.rd, kInfinity)); hv.roS = ir.o; hv.rdS = ir.d;
+        }
+    }
+    if (needIsect) { const float4 hr = pool.R(R_HIT, slot); HitInteraction<DISKS>(s, prim, hv.roS, hv.rdS, hr.y, hr.z, hr.w, isect); }
+    if constexpr (INST) {
+        if (hv.inst >= 0) {
+            if (isectObj) *isectObj = *isect;
+            InteractionToWorld(hv.I2W(s, mm), hv.W2I(s, mm), isect);
+        }
+    }
+}
+
 // (the shading kernel's dimensions start after the camera sample's, so dim >= 5 here)
 
 // ------------------------------------------------------------------ shade
@@ -2089,132 +2134,740 @@ DEV void StoreSpectrumLines(SpectrumTile &t, const Pool &pool, int spectrum, uin
 // k_shade's own note beside the flags it is forming: the vertex has a dark MIS ray, which goes to the MIS queue but not into
 // the state word (StateWord keeps FLAG_BITS bits).
 constexpr int SHADE_DARK_RAY = 1 << FLAG_BITS;
-// MOTION (TM_INSTANCES instances only): the scene has moving instances -- a hit inside one is carried by the two matrices of
-// Interpolate(ray time), held as values. The MOTION = false instances read the instance's record in place, as before.
-template <int NL, unsigned TM, bool LENS = false, bool MOTION = false>
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT_SHADE_WAVES_PER_EU, 8))) k_shade(DScene s, Pool pool, DevCounters *ctr, unsigned classes) {
-    // the grid covers the queues of `classes` back to back, each padded to whole blocks
-    unsigned blk = blockIdx.x, count = 0;
-    int cls = -1;
+
+// ---- the stages of a vertex, in k_shade's order. Every routine is inlined and templated on the axes it reads.
+// Queue entry: the grid covers the queues of `classes` back to back, each padded to whole blocks.
+struct ShadeEntry { int cls; unsigned count; uint32_t qi; };   // the class (-1: past the last queue), its queue's length, the lane's index in it
+DEV ShadeEntry ShadeQueueEntry(const DevCounters *ctr, unsigned classes) {
+    ShadeEntry e = {-1, 0u, 0u};
+    unsigned blk = blockIdx.x;
     for (int c = 0; c < MAX_CLASSES; ++c) {
         if (!((classes >> c) & 1)) continue;
         const unsigned n = ctr->shadeCount[c].v, nb = (n + BLOCK - 1) / BLOCK;
-        if (blk < nb) { cls = c; count = n; break; }
+        if (blk < nb) { e.cls = c; e.count = n; break; }
         blk -= nb;
     }
-    const uint32_t qi = blk * BLOCK + threadIdx.x;
-    constexpr bool HALTON_ONLY = (TM & TM_SAMPLERS) == 0;
-    constexpr bool DISKS = TM_HOLDS_DISKS(TM);   // (a scene with disks is shaded by the general instances alone: ShadeInstanceOf)
-    constexpr bool NOISE = TM_HOLDS_NOISE(TM);   // (likewise the textured classes of a scene with noise textures)
-    constexpr bool SIMPLE_SPECTRA = NL <= 2 && TM_SIMPLE_KINDS(TM);   // the straight-line spectral passes (d_bsdf.h, SimpleLobes)
-    // more than two lobes: f is summed lobe by lobe into the lane's column of the spectrum tile (AccumulateF, d_bsdf.h)
-    constexpr bool ACCUM = NL > 2 || (TM & TM_TEXTURED) != 0;   // (image-textured lobes too: their spectra quad by quad, TexturedQuad)
-    __shared__ SpectrumTile tile;
-    auto rdTile = [&](int c) -> float4 { return tile.q[c][threadIdx.x]; };
-    auto wrTile = [&](int c, const float4 &v) { tile.q[c][threadIdx.x] = v; };
-    unsigned totalPaths = 0, pathLen = 0, zeroNow = 0;
-    bool wantShadow = false, wantMis = false, wantDark = false;
-    uint32_t slot = 0;
-    if (cls >= 0 && qi < count) {
-        slot = pool.shadeQ[(size_t)cls * pool.n + qi];
-        const int word = pool.I(I_FLAGS, slot);   // flags | bounces | sampler dimension (StateWord)
-        const int flags = word & FLAG_MASK;
-        bool lZero = (flags & F_L_ZERO) != 0, betaWritten = false;
-        const int lPlane = LPlane(flags);   // the line that holds the path's L
-        const bool betaOne = (flags & F_BETA_ONE) != 0;
-        const int bounces = StateBounces(word);
-        int dimNow = StateDim(word);
-        const int prim = pool.I(I_HITPRIM, slot);
-        const bool found = prim >= 0;
-        auto loadBeta = [&](int c) -> float4 { return LoadBeta(pool, c, slot, betaOne); };
-        // the ray and the interaction are needed by vertices that will be shaded or may show emitted light; an escaped
-        // ray without environment lights and a path at its last vertex need neither (k_resolve_extend ends those itself and
-        // does not queue them, EndsUnshaded: what this kernel writes for one, below, is FinishedWord)
-        const bool emitCheck = bounces == 0 || (flags & F_SPECULAR);
-        const bool needIsect = found && (bounces < s.maxDepth || emitCheck);
-        const bool needRay = needIsect || (!found && emitCheck && TM_LIGHT(TM, MI_LIGHT_INFINITE) && s.nInfiniteLights > 0);
-        float4 ray0 = make_float4(0.f, 0.f, 0.f, 0.f), ray1 = make_float4(0.f, 0.f, 1.f, 1.f);
-        if (needRay) { ray0 = pool.R(R_RAY0, slot); ray1 = pool.R(R_RAY1, slot); }
-        V3 ro(ray0.x, ray0.y, ray0.z), rd(ray1.x, ray1.y, ray1.z);
-        SurfaceInteraction isect;
-        bool finished = false, passThrough = false;
-        // a hit inside an object instance: the interaction is built with the ray in the instance's space and taken to the
-        // world by InstanceToWorld (TransformedPrimitive::Intersect, primitive.cpp:78-92)
-        int inst = -1;
-        V3 roS = ro, rdS = rd;   // the ray in the space the hit shape was intersected in
-        float instW2I[MOTION ? 16 : 1], instI2W[MOTION ? 16 : 1];
-        if constexpr ((TM & TM_INSTANCES) != 0) {
-            if (needIsect) inst = pool.I(I_HITINST, slot);
-            if constexpr (MOTION) {
-                if (inst >= 0) {   // (both matrices of Interpolate(ray.time), kept for the shading frame below)
-                    const float time = PathTime(s, pool, slot);
-                    InstanceW2I(s, inst, time, instW2I);
-                    InstanceI2W(s, inst, time, instI2W);
-                    const Ray ir = XfRay(instW2I, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d;
-                }
-            } else if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
-        }
-        if (needIsect) { const float4 hr = pool.R(R_HIT, slot); HitInteraction<DISKS>(s, prim, roS, rdS, hr.y, hr.z, hr.w, &isect); }
-        SurfaceInteraction isectObj;
-        if constexpr ((TM & TM_INSTANCES) != 0) {
-            if (inst >= 0) {
-                isectObj = isect;
-                if constexpr (MOTION) InteractionToWorld(instI2W, instW2I, &isect);
-                else InteractionToWorld(s.instances[inst], &isect);
-            }
-        }
-        // emitted light at the vertex, path.cpp:91-101
-        if ((bounces == 0 || (flags & F_SPECULAR)) && found) {
-            const int li = s.prims[prim].area_light;
-            if (li >= 0) {
-                const mi_light &l = s.lights[li];
-                if (l.two_sided || Dot(isect.n, -rd) > 0)
-{
+    e.qi = blk * BLOCK + threadIdx.x;
+    return e;
+}
+// Path head: the state word (flags | bounces | sampler dimension, StateWord) unpacked once, and the hit primitive.
+struct PathHead {
+    int word, flags, bounces, dim, prim, lPlane;   // lPlane: the line that holds the path's L
+    bool lZero, betaOne, found, emitCheck;         // emitCheck: the vertex may show emitted light, path.cpp:91
+};
+DEV PathHead LoadPathHead(const Pool &pool, uint32_t slot) {
+    PathHead h;
+    h.word = pool.I(I_FLAGS, slot);
+    h.flags = h.word & FLAG_MASK; h.bounces = StateBounces(h.word); h.dim = StateDim(h.word);
+    h.lZero = (h.flags & F_L_ZERO) != 0; h.betaOne = (h.flags & F_BETA_ONE) != 0; h.lPlane = LPlane(h.flags);
+    h.prim = pool.I(I_HITPRIM, slot);
+    h.found = h.prim >= 0;
+    h.emitCheck = h.bounces == 0 || (h.flags & F_SPECULAR);
+    return h;
+}
+
+// L += beta * Le over the path's eight quads; `leQuad(c)` is the emitter's Le, quad c.
+template <typename LeQuad>
+DEV void AddEmitted(const Pool &pool, uint32_t slot, int lPlane, bool betaOne, bool lZero, LeQuad leQuad) {
 #pragma unroll 1
-                    for (int c = 0; c < NQ; ++c) {
-                        const float4 bt = loadBeta(c);
-                        float4 L4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (!lZero) L4 = pool.Q(lPlane + c, slot);
-                        const float4 Le = LoadSpec4(l.L, c);
+    for (int c = 0; c < NQ; ++c) {
+        const float4 bt = LoadBeta(pool, c, slot, betaOne);
+        float4 L4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!lZero) L4 = pool.Q(lPlane + c, slot);
+        const float4 Le = leQuad(c);
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int b = 4 * c + k;
-                            if (b < MI_NSPEC) Set4(L4, k, Get4(L4, k) + Get4(bt, k) * Get4(Le, k));
-                        }
-                        pool.Q(lPlane + c, slot) = L4;
-                    }
-                    lZero = false;
-                }
-            }
+        for (int k = 0; k < 4; ++k) {
+            const int b = 4 * c + k;
+            if (b < MI_NSPEC) Set4(L4, k, Get4(L4, k) + Get4(bt, k) * Get4(Le, k));
         }
-        if ((bounces == 0 || (flags & F_SPECULAR)) && !found) {  // escaped: scene.infiniteLights, path.cpp:96-99
-            for (int il = 0; TM_LIGHT(TM, MI_LIGHT_INFINITE) && il < s.nInfiniteLights; ++il) {
-                const IllumRGB le = InfiniteLe(s, s.lights[s.infiniteLights[il]], rd);
-#pragma unroll 1
-                for (int c = 0; c < NQ; ++c) {
-                    const float4 bt = loadBeta(c);
-                    float4 L4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (!lZero) L4 = pool.Q(lPlane + c, slot);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int b = 4 * c + k;
-                        if (b < MI_NSPEC) Set4(L4, k, Get4(L4, k) + Get4(bt, k) * IllumBin(s, le, b));
-                    }
-                    pool.Q(lPlane + c, slot) = L4;
-                }
+        pool.Q(lPlane + c, slot) = L4;
+    }
+}
+// Emitted light at the vertex, path.cpp:91-101: the hit emitter's, or scene.infiniteLights' for an escaped ray. Returns lZero.
+template <unsigned TM>
+DEV bool EmittedLight(const DScene &s, const Pool &pool, uint32_t slot, const PathHead &h, const V3 &n, const V3 &rd) {
+    bool lZero = h.lZero;
+    if (h.emitCheck && h.found) {
+        const int li = s.prims[h.prim].area_light;
+        if (li >= 0) {
+            const mi_light &l = s.lights[li];
+            if (l.two_sided || Dot(n, -rd) > 0) {
+                AddEmitted(pool, slot, h.lPlane, h.betaOne, lZero, [&](int c) -> float4 { return LoadSpec4(l.L, c); });
                 lZero = false;
             }
         }
-        if (!found || bounces >= s.maxDepth) finished = true;
-        int newFlags = 0;
-        if (!finished && s.prims[prim].material < 0) {  // interface without BSDF: continue through it, path.cpp:108-113
-            Ray r = SpawnRay(isect, rd);
-            pool.R(R_RAY0, slot) = make_float4(r.o.x, r.o.y, r.o.z, r.tMax);
-            passThrough = true;  // flags and bounce count stay as they are (but the spawned ray has no differentials)
-            if (flags & F_DIFF) pool.I(I_FLAGS, slot) = word & ~F_DIFF;
+    }
+    if (h.emitCheck && !h.found) {
+        for (int il = 0; TM_LIGHT(TM, MI_LIGHT_INFINITE) && il < s.nInfiniteLights; ++il) {
+            const IllumRGB le = InfiniteLe(s, s.lights[s.infiniteLights[il]], rd);
+            AddEmitted(pool, slot, h.lPlane, h.betaOne, lZero, [&](int c) -> float4 {
+                float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (4 * c + k < MI_NSPEC) Set4(q, k, IllumBin(s, le, 4 * c + k));
+                return q;
+            });
+            lZero = false;
         }
+    }
+    return lZero;
+}
+
+// An interface without BSDF: the path continues through it, path.cpp:108-113. Flags and bounce count stay as they are, but
+// the spawned ray has no differentials.
+DEV void PassThroughInterface(const Pool &pool, uint32_t slot, const PathHead &h, const SurfaceInteraction &isect, const V3 &rd) {
+    Ray r = SpawnRay(isect, rd);
+    pool.R(R_RAY0, slot) = make_float4(r.o.x, r.o.y, r.o.z, r.tMax);
+    if (h.flags & F_DIFF) pool.I(I_FLAGS, slot) = h.word & ~F_DIFF;
+}
+
+// SurfaceInteraction::ComputeDifferentials, interaction.cpp:99-143, for a camera ray. LENS: the lens camera's offset rays,
+// which k_generate stored; otherwise the perspective camera's, static or animated.
+template <bool LENS>
+DEV TexDifferentials VertexDifferentials(const DScene &s, const Pool &pool, uint32_t slot, const V3 &ro, const V3 &rd, const SurfaceInteraction &isect, const V3 &dpdv) {
+    if constexpr (LENS) {
+        CamDifferentials cd;
+        cd.rxOrigin = V3(pool.F(P_LENSDIFF + 0, slot), pool.F(P_LENSDIFF + 1, slot), pool.F(P_LENSDIFF + 2, slot));
+        cd.ryOrigin = V3(pool.F(P_LENSDIFF + 3, slot), pool.F(P_LENSDIFF + 4, slot), pool.F(P_LENSDIFF + 5, slot));
+        cd.rxDirection = V3(pool.F(P_LENSDIFF + 6, slot), pool.F(P_LENSDIFF + 7, slot), pool.F(P_LENSDIFF + 8, slot));
+        cd.ryDirection = V3(pool.F(P_LENSDIFF + 9, slot), pool.F(P_LENSDIFF + 10, slot), pool.F(P_LENSDIFF + 11, slot));
+        return ComputeDifferentials(isect.p, isect.n, isect.dpdu, dpdv, cd);
+    } else {
+        float lu = 0.f, lv = 0.f;
+        // CameraToWorld for the offset rays: one call of CameraDifferentials on one local array
+        float c2w[16];
+        if (s.camera.animated) {   // (uniform) the camera sample's time and lens position again, and the transform at that time
+            const int pixw = pool.I(I_PIXEL, slot);
+            float cu0, cu1, tu;
+            CameraSampleDims<true>(s, (int)(short)(pixw & 0xffff), pixw >> 16, (long long)pool.I(I_SAMPLE, slot), &cu0, &cu1, &lu, &lv, nullptr, &tu);
+            MovingCameraToWorld(s.cameraMotion, lerpf(tu, s.camera.shutter_open, s.camera.shutter_close), c2w);
+        } else {
+            if (s.camera.lens_radius > 0) {   // the camera sample's lens position again
+                const int pixw = pool.I(I_PIXEL, slot);
+                float cu0, cu1;
+                CameraSampleDims(s, (int)(short)(pixw & 0xffff), pixw >> 16, (long long)pool.I(I_SAMPLE, slot), &cu0, &cu1, &lu, &lv);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) c2w[i] = s.camera.camera_to_world[i];
+        }
+        const CamDifferentials cd = CameraDifferentials(s, c2w, pool.F(P_FILMX, slot), pool.F(P_FILMY, slot), lu, lv, ro, rd, s.invSqrtSpp);
+        return ComputeDifferentials(isect.p, isect.n, isect.dpdu, dpdv, cd);
+    }
+}
+
+// The textured roughness and sigma of the material at the hit, into the frame's overrides:
+// `rough = roughness->Evaluate(*si); if (remapRoughness) rough = RoughnessToAlpha(rough)` (plastic.cpp:57-62 ...).
+// Returns whether the raw roughnesses (MI_ROUGH_GLASS: the values before the remap) are both 0.
+template <bool NOISE>
+DEV bool RoughnessOverrides(const DScene &s, const mi_material *mat, float u, float v, const V3 &p, const TexDifferentials &td, BSDFFrame &fr) {
+    float rawU = mat->bxdf[0].p[6], rawV = mat->bxdf[0].p[7];
+    if (mat->rough_flags & MI_ROUGH_DISNEY) {   // `Float rough = roughness->Evaluate(*si)`, disney.cpp:491
+        fr.ov.disney = true;
+        fr.ov.rough = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[0], u, v, p, td);
+    } else
+    if (mat->rough_tex[0] >= 0) {
+        const float rv = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[0], u, v, p, td);
+        fr.ov.u = (mat->rough_flags & MI_ROUGH_REMAP) ? RoughnessToAlpha(rv) : rv;
+        fr.ov.onU = true;
+        rawU = rv;
+    }
+    if (mat->rough_tex[1] >= 0) {
+        if (mat->rough_tex[1] == mat->rough_tex[0]) { fr.ov.v = fr.ov.u; rawV = rawU; }
+        else {
+            const float rv = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[1], u, v, p, td);
+            fr.ov.v = (mat->rough_flags & MI_ROUGH_REMAP) ? RoughnessToAlpha(rv) : rv;
+            rawV = rv;
+        }
+        fr.ov.onV = true;
+    }
+    if (mat->sigma_tex >= 0) {   // `Float sig = Clamp(sigma->Evaluate(*si), 0, 90)`, matte.cpp:57; OrenNayar's constructor
+        const float sig = clampf(EvalFloatImageTexture<NOISE>(s, mat->sigma_tex, u, v, p, td), 0.f, 90.f);
+        if (sig == 0) fr.ov.sigMode = 2;
+        else {
+            const float sigma = (kPi / 180) * sig, sigma2 = sigma * sigma;
+            fr.ov.sigMode = 1;
+            fr.ov.sigA = 1.f - (sigma2 / (2.f * (sigma2 + 0.33f)));
+            fr.ov.sigB = 0.45f * sigma2 / (sigma2 + 0.09f);
+        }
+    }
+    return rawU == 0 && rawV == 0;
+}
+
+// Which lobes the material adds at this hit: its lobe textures evaluated into `lt`, a lobe kept when the spectrum its rule
+// tests is not black (matte.cpp:55-63, plastic.cpp:52-68, uber.cpp:60-100, ...).
+template <int NL, bool NOISE>
+DEV unsigned LobePresenceMask(const DScene &s, const mi_material *mat, float u, float v, const V3 &p, const TexDifferentials &td, LobeTexT<NL> &lt) {
+    unsigned mask = 0u;
+    for (int i = 0; i < mat->n_bxdfs; ++i) {
+        const mi_lobe_tex ltx = mat->tex[i];
+        if (ltx.tex_R < 0 && ltx.tex_S < 0) { mask |= 1u << i; continue; }
+        if (i >= NL) continue;
+        if (ltx.tex_R >= 0) {
+            lt.r[i] = EvalImageTexture<NOISE>(s, ltx.tex_R, u, v, p, td);
+            if (ltx.rule == MI_LOBE_METAL) lt.hasK |= 1u << i;   // (k's texture: the lobe's R stays the constant)
+            else lt.hasR |= 1u << i;
+            if (ltx.flags & MI_LOBE_TEX_MUL_R) lt.mulR |= 1u << i;
+        }
+        if (ltx.tex_S >= 0) {
+            lt.s[i] = EvalImageTexture<NOISE>(s, ltx.tex_S, u, v, p, td);
+            lt.hasS |= 1u << i;
+            if (ltx.flags & MI_LOBE_TEX_MUL_S) lt.mulS |= 1u << i;
+        }
+        lt.rules |= (unsigned)(ltx.rule & 15) << (4 * i);
+        if (ltx.rule >= MI_LOBE_ALWAYS) {   // "disney": lobes are added whatever the colour is
+            if (ltx.rule >= MI_LOBE_DISNEY_SHEEN && ltx.rule <= MI_LOBE_DISNEY_STRANS && lt.lum == 0.f) {   // lum = c.y(), once per vertex (every lobe has the same colour)
+                float yy = 0.f;
+                for (int b = 0; b < MI_NSPEC; ++b) yy += SpecYBinAccum(s, b, TexBin(lt.basis, lt.textures, lt.r[i], b));
+                lt.lum = YScale(yy);
+            }
+            mask |= 1u << i;
+            continue;
+        }
+        // (the spectrum the material tests with IsBlack(), a quad of bins at a time; only what the lobe's rule reads)
+        unsigned rNZ = 0u, sNZ = 0u, texNZ = 0u;
+        auto orQuad = [](unsigned &acc, const float4 &q, int c) {
+            OrNonZero(acc, q.x); OrNonZero(acc, q.y); OrNonZero(acc, q.z);
+            if (c != NQ - 1) OrNonZero(acc, q.w);   // bin 31 does not exist
+        };
+#pragma unroll 1
+        for (int c = 0; c < NQ; ++c) {
+            if (ltx.rule != MI_LOBE_IF_TEX) orQuad(rNZ, TexturedQuad(lt, mat->bxdf[i], i, 0, c), c);
+            if (ltx.rule == MI_LOBE_IF_R_OR_S) orQuad(sNZ, TexturedQuad(lt, mat->bxdf[i], i, 1, c), c);
+            if (ltx.rule == MI_LOBE_IF_TEX) {
+                if (ltx.tex_R >= 0) orQuad(texNZ, TexQuad(lt.basis, lt.textures, lt.r[i], c), c);
+                if (ltx.tex_S >= 0) orQuad(texNZ, TexQuad(lt.basis, lt.textures, lt.s[i], c), c);
+            }
+        }
+        const bool rNonBlack = rNZ != 0u, sNonBlack = sNZ != 0u, texNonBlack = texNZ != 0u;
+        const bool present = ltx.rule == MI_LOBE_IF_R_OR_S ? (rNonBlack || sNonBlack) : (ltx.rule == MI_LOBE_IF_TEX ? texNonBlack : rNonBlack);
+        if (present) mask |= 1u << i;
+    }
+    return mask;
+}
+
+// Material::ComputeScatteringFunctions with image textures: evaluate them at the hit (which Bump() may move), fill the
+// frame's overrides and lobe mask and the lobe textures.
+template <int NL, unsigned TM, bool LENS, bool MOTION>
+DEV void TexturedScattering(const DScene &s, const Pool &pool, uint32_t slot, const PathHead &h,
+                            const HitVertex<(TM & TM_INSTANCES) != 0, MOTION> &hv, const MovingMatrices<MOTION> &mm, SurfaceInteraction &isect, const SurfaceInteraction &isectObj,
+                            const mi_material *mat, BSDFFrame &fr, LobeTexT<NL> &lt) {
+    constexpr bool DISKS = TM_HOLDS_DISKS(TM), NOISE = TM_HOLDS_NOISE(TM);
+    lt.hasR = lt.hasS = lt.mulR = lt.mulS = 0u;
+    lt.rules = 0u; lt.lum = 0.f; lt.hasK = 0u;
+    lt.basis = s.rgbIllum; lt.textures = s.textures;
+    float u = 0.f, v = 0.f;
+    TriShading tsh;
+    bool haveUV = false;
+    if (mat->textured) {
+        const int shape = s.prims[h.prim].shape;
+        if (shape >= 0) {
+            const float4 hr = pool.R(R_HIT, slot);
+            TriTexCoords(s, shape, hr.y, hr.z, hr.w, hv.inst >= 0 ? isectObj : isect, &u, &v, &tsh);
+            haveUV = true;
+        } else if (DISKS && IsDisk(s, ~shape))
+            haveUV = DiskTexCoords(s.disks[~shape - s.nSpheres], hv.roS, hv.rdS, &u, &v, &tsh);
+        else
+            haveUV = SphereTexCoords(s.spheres[~shape], hv.roS, hv.rdS, &u, &v, &tsh);
+        if constexpr ((TM & TM_INSTANCES) != 0) {
+            if (hv.inst >= 0) ShadingToWorld(hv.I2W(s, mm), hv.W2I(s, mm), &tsh);
+        }
+    }
+    if (haveUV) {
+        TexDifferentials td;
+        td.dudx = td.dvdx = td.dudy = td.dvdy = 0;
+        td.dpdx = td.dpdy = V3(0, 0, 0);
+        if (h.flags & F_DIFF) td = VertexDifferentials<LENS>(s, pool, slot, hv.ro, hv.rd, isect, tsh.dpdv);
+        if (mat->bump_tex >= 0) Bump<NOISE>(s, mat->bump_tex, u, v, td, tsh, &isect);   // `if (bumpMap) Bump(bumpMap, si)`
+        const bool rawSmooth = RoughnessOverrides<NOISE>(s, mat, u, v, isect.p, td, fr);
+        unsigned mask = LobePresenceMask<NL, NOISE>(s, mat, u, v, isect.p, td, lt);
+        if (mat->rough_flags & MI_ROUGH_GLASS) mask &= rawSmooth ? 1u : ~1u;   // glass.cpp:66: `isSpecular = urough == 0 && vrough == 0` at this hit; lobe 0 is the FresnelSpecular one
+        fr.mask = mask;
+    }
+}
+
+// ---- the pieces of a spectral pass (the divisor chain and the straight-line quad's pieces: d_bsdf.h, PdfChain and StraightPass)
+// f of the evaluated direction, quad c: summed into the lane's tile column (ACCUM), or formed from the lobe list.
+template <int NL, unsigned TM, bool ACCUM>
+DEV float4 FQuad(const SpectrumTile &tile, const BSDFEvalT<NL> &ev, const mi_bxdf *bx, int c, const LobeTexT<NL> *ltp) {
+    if constexpr (ACCUM) return tile.q[c][threadIdx.x];
+    else return EvalQuad<NL, TM>(ev, bx, c, ltp);
+}
+
+// Commit: the vertex's final flags and state word, and which ray queues the slot joins. Returns 1 for a direct-lighting
+// estimate that is already known to be black.
+DEV unsigned CommitVertex(const DScene &s, const Pool &pool, uint32_t slot, const PathHead &h, int newFlags, bool finished, bool lZero, bool betaWritten,
+                          int dimNow, bool *wantShadow, bool *wantMis, bool *wantDark) {
+    unsigned zeroNow = 0;
+    if (finished) newFlags = (newFlags & (F_NEE | F_SHADOW | F_MIS | F_CAND | F_NEE_NZ | SHADE_DARK_RAY)) | F_FINISHED;
+    else newFlags |= F_ALIVE;
+    if (lZero) newFlags |= F_L_ZERO;
+    newFlags |= h.flags & F_L_IN_B;
+    if (h.betaOne && !betaWritten) newFlags |= F_BETA_ONE;
+    *wantShadow = (newFlags & F_SHADOW) != 0;
+    // (a dark ray has a queue of its own where k_trav<3> serves the live ones; with k_trav<2> both share misQ)
+    *wantDark = s.misAny && (newFlags & SHADE_DARK_RAY) != 0;
+    *wantMis = (newFlags & F_MIS) != 0 || (!s.misAny && (newFlags & SHADE_DARK_RAY) != 0);
+    // a direct-lighting estimate with neither ray pending (a dark MIS ray is none) is already known to be black
+    if ((newFlags & F_NEE) && !*wantShadow && !(newFlags & F_MIS)) { ++zeroNow; newFlags &= ~F_NEE; }
+    pool.I(I_FLAGS, slot) = StateWord(newFlags, finished ? h.bounces : h.bounces + 1, dimNow);
+    return zeroNow;
+}
+
+// What an instance compiles its spectral passes as.
+template <int NL, unsigned TM> constexpr bool ShadeSimpleSpectra = NL <= 2 && TM_SIMPLE_KINDS(TM);   // the straight-line passes (d_bsdf.h, SimpleLobes)
+// more than two lobes: f is summed lobe by lobe into the lane's column of the spectrum tile (AccumulateF, d_bsdf.h)
+template <int NL, unsigned TM> constexpr bool ShadeAccum = NL > 2 || (TM & TM_TEXTURED) != 0;   // (image-textured lobes too: their spectra quad by quad, TexturedQuad)
+// The lane's column of the spectrum tile, as AccumulateF reads and writes it.
+struct TileColumnRead { const SpectrumTile &t; DEV float4 operator()(int c) const { return t.q[c][threadIdx.x]; } };
+struct TileColumnWrite { SpectrumTile &t; DEV void operator()(int c, const float4 &v) const { t.q[c][threadIdx.x] = v; } };
+// Direct lighting, the light-sample term (EstimateDirect, integrator.cpp:107-165): f * Li * weight / pdf into the candidate
+// line, the shadow ray. Returns the flags it sets.
+template <int NL, unsigned TM>
+DEV int LightSampleTerm(const DScene &s, const Pool &pool, SpectrumTile &tile, uint32_t slot, const PathHead &h, const SurfaceInteraction &isect,
+                        const BSDFFrame &fr, const mi_material *mat, const LobeTexT<NL> *ltp, bool lZero, const mi_light &light, float uL0, float uL1,
+                        const Divisor &selDiv, bool selIsOne) {
+    constexpr bool SIMPLE_SPECTRA = ShadeSimpleSpectra<NL, TM>, ACCUM = ShadeAccum<NL, TM>;
+    const TileColumnRead rdTile{tile};
+    const TileColumnWrite wrTile{tile};
+    auto loadBeta = [&](int c) -> float4 { return LoadBeta(pool, c, slot, h.betaOne); };
+    const int nonSpec = MI_BSDF_ALL & ~MI_BSDF_SPECULAR;
+    int flags = 0;
+    const LightSample ls = SampleLi<TM>(s, light, isect, uL0, uL1);
+    const float lightPdf = ls.pdf;
+    if (lightPdf > 0 && !ls.black) {
+        BSDFEvalT<NL> ev;
+        if constexpr (ACCUM) AccumulateF<NL, TM>(fr, isect.wo, ls.wi, nonSpec, ltp, rdTile, wrTile);
+        else BSDF_f<NL, TM>(fr, isect.wo, ls.wi, nonSpec, &ev);
+        const float absdot = AbsDot(ls.wi, isect.shN);
+        const float scatteringPdf = BSDF_Pdf<TM>(fr, isect.wo, ls.wi, nonSpec);
+        const bool delta = IsDeltaLight<TM_HOLDS_PROJECTION(TM)>(light);
+        float weight = 1.f;
+        if (!delta) { float pf = 1 * lightPdf, pg = 1 * scatteringPdf; weight = (pf * pf) / (pf * pf + pg * pg); }
+        const PdfChain div = MakePdfChain(MakeDivisor(lightPdf), selDiv, selIsOne);
+        bool fNonBlack = false, liNonBlack = false, nzAny = false;
+        // the path's L so far, quad c: the candidate is L + contribution (F_CAND)
+        auto lBase = [&](int c) -> float4 { return lZero ? make_float4(0.f, 0.f, 0.f, 0.f) : pool.Q(h.lPlane + c, slot); };
+        auto neeQuad = [&](int c, const float4 &fq, const float4 &Lq) {
+            const float4 bt = loadBeta(c), l4 = lBase(c);
+            float4 out = l4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int b = 4 * c + k;
+                if (b < MI_NSPEC) {
+                    const float f = Get4(fq, k) * absdot;
+                    const float Li = Get4(Lq, k);
+                    fNonBlack |= (f != 0.f);
+                    liNonBlack |= (Li != 0.f);
+                    const float Ld = DivChainExact(delta ? f * Li : (f * Li) * weight, div);
+                    const float contrib = Get4(bt, k) * Ld;
+                    nzAny |= (contrib != 0.f);
+                    Set4(out, k, Get4(l4, k) + contrib);
+                }
+            }
+            tile.q[c][threadIdx.x] = out;
+        };
+        if constexpr (SIMPLE_SPECTRA) {
+            // straight-line form (d_bsdf.h, SimpleLobes); a quad in which a quotient leaves DivBy's fast range is redone with DivBy
+            const StraightPass<NL> sp = MakeStraightPass<NL, TM>(ev, mat->bxdf, div);
+            unsigned accF = 0u, accLi = 0u, accNz = 0u;
+            auto quad = [&](int c, auto exactTag) {
+                constexpr bool EXACT = decltype(exactTag)::value;
+                DivTrack trk;
+                const float4 bt = loadBeta(c), l4 = lBase(c);   // (the loads first: f's evaluation covers them)
+                const float4 fq = StraightQuadF<NL, TM, EXACT>(sp, true, c, c == NQ - 1, trk);
+                float4 Lq = LiQuad<TM>(s, light, ls, c);
+                if (c == NQ - 1) Lq.w = 0.f;   // bin 31 does not exist
+                unsigned aF = 0u, aLi = 0u, aNz = 0u;
+                float o[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float f = Get4(fq, k) * absdot;
+                    const float Li = Get4(Lq, k);
+                    OrNonZero(aF, f); OrNonZero(aLi, Li);
+                    const float x = (f * Li) * weight;   // (weight == 1 for a delta light: x * 1 == x)
+                    o[k] = Get4(bt, k) * DivChain<EXACT>(x, div, trk);
+                    OrNonZero(aNz, o[k]);
+                }
+                if (!QuadHolds<EXACT>(trk)) return false;
+                tile.q[c][threadIdx.x] = make_float4(l4.x + o[0], l4.y + o[1], l4.z + o[2], l4.w + o[3]);
+                accF |= aF; accLi |= aLi; accNz |= aNz;
+                return true;
+            };
+#pragma unroll 1
+            for (int c = 0; c < NQ; ++c)
+                if (!quad(c, std::false_type{})) quad(c, std::true_type{});
+            fNonBlack |= accF != 0u; liNonBlack |= accLi != 0u; nzAny |= accNz != 0u;
+        } else {
+#pragma unroll 1
+            for (int c = 0; c < NQ; ++c) neeQuad(c, FQuad<NL, TM, ACCUM>(tile, ev, mat->bxdf, c, ltp), LiQuad<TM>(s, light, ls, c));
+        }
+        // the tile holds L + contribution, the candidate (F_CAND): only one whose shadow ray will be traced
+        // is ever read
+        const bool traced = fNonBlack && liNonBlack;
+        StoreSpectrumLines(tile, pool, LOtherPlane(h.flags), slot, traced);
+        if (traced) flags |= F_CAND | (nzAny ? F_NEE_NZ : 0);
+        if (traced) {  // the shadow ray is traced iff f != 0 (integrator.cpp:138-150)
+            Ray sr = SpawnRayTo(isect, ls.pLight);
+            pool.R(R_SH0, slot) = make_float4(sr.o.x, sr.o.y, sr.o.z, sr.d.x);
+            pool.R(R_SH1, slot) = make_float4(sr.d.y, sr.d.z, 0.f, 0.f);
+            flags |= F_SHADOW;
+        }
+    }
+    return flags;
+}
+// Direct lighting, the BSDF-sample term with MIS (integrator.cpp:167-213): the span of the sampled light along the ray, the
+// dark rays, the contribution line, the MIS ray. Returns the flags it sets.
+template <int NL, unsigned TM>
+DEV int BsdfSampleTerm(const DScene &s, const Pool &pool, SpectrumTile &tile, uint32_t slot, const PathHead &h, const SurfaceInteraction &isect,
+                       const BSDFFrame &fr, const mi_material *mat, const LobeTexT<NL> *ltp, const mi_light &light, int lightNum, float uS0, float uS1,
+                       const Divisor &selDiv, bool selIsOne) {
+    constexpr bool SIMPLE_SPECTRA = ShadeSimpleSpectra<NL, TM>, ACCUM = ShadeAccum<NL, TM>;
+    constexpr bool DISKS = TM_HOLDS_DISKS(TM);
+    const TileColumnRead rdTile{tile};
+    const TileColumnWrite wrTile{tile};
+    auto loadBeta = [&](int c) -> float4 { return LoadBeta(pool, c, slot, h.betaOne); };
+    const int nonSpec = MI_BSDF_ALL & ~MI_BSDF_SPECULAR;
+    int flags = 0;
+    if (!IsDeltaLight<TM_HOLDS_PROJECTION(TM)>(light)) {  // BSDF sampling with MIS, integrator.cpp:167-213
+        V3 wi;
+        float sPdf = 0;
+        int sampledType = 0;
+        BSDFEvalT<NL> ev;
+        V3 wiLocal;
+        const bool ok = BSDF_Sample_f<NL, TM, !ACCUM>(fr, isect.wo, &wi, uS0, uS1, &sPdf, nonSpec, &sampledType, &ev, &wiLocal);
+        if (ok && sPdf > 0) {
+            const float absdot = AbsDot(wi, isect.shN);
+            // Pdf_Li has no side effect: evaluate it before knowing whether f is black
+            float weight = 1;
+            bool go = true;
+            float tShape = -1.f;   // a triangle light: where wi meets it
+            if (!(sampledType & MI_BSDF_SPECULAR)) {
+                const float lp = (TM_LIGHT(TM, MI_LIGHT_INFINITE) && light.type == MI_LIGHT_INFINITE) ? InfinitePdfLi(s, light, wi)
+                                                                   : ShapePdf<DISKS>(s, light.shape, light.area, isect, wi, &tShape);
+                if (lp == 0) go = false;
+                else { float pf = 1 * sPdf, pg = 1 * lp; weight = (pf * pf) / (pf * pf + pg * pg); }
+            }
+            const bool isEnvLight = TM_LIGHT(TM, MI_LIGHT_INFINITE) && light.type == MI_LIGHT_INFINITE;
+            IllumRGB envLe;
+            envLe.i1 = envLe.i2 = 0; envLe.w0 = envLe.w1 = envLe.w2 = 0;
+            if (isEnvLight && go) envLe = InfiniteLe(s, light, wi);   // light.Le(ray) when the ray escapes
+            const PdfChain div = MakePdfChain(MakeDivisor(sPdf), selDiv, selIsOne);
+            bool fNonBlack = false;
+            // a ray that cannot reach the sampled area light is traced all the same (the reference
+            // traces it), but its contribution is never read: a dark ray (MIS_EXCL_DARK)
+            const Ray mr = SpawnRay(isect, wi);
+            float spanLo = 0.f, spanHi = kInfinity;
+            const bool dark = go && !isEnvLight && !RaySpanInBox(mr.o, mr.d, s.lightBounds[2 * lightNum], s.lightBounds[2 * lightNum + 1], &spanLo, &spanHi);
+            float misTHi = kInfinity, misWord = __uint_as_float(MIS_EXCL_NONE | (31u << MIS_EXCL_BITS));   // (environment light, dark ray: any hit ends it)
+            if (s.misAny && go && !dark && !isEnvLight) {
+                // a triangle: Shape::Pdf has intersected it (the same test the traversal runs); a sphere: its span in the
+                // dilated bounds. Either way widened by what the float arithmetic of the triangle and box tests can disagree
+                // by about where things are along the ray: those work on coordinates relative to the ray's origin, so their
+                // absolute error in t grows with the distance of the farthest vertex, a few ulps of it (a ray that starts
+                // 1e-3 above a 2000-unit ground plane meets it at a t that is 10 % noise, and the plane's box later than that:
+                // tests/test_gpu_parity.py::test_mis_visibility_kernel_verdicts_on_recorded_rays). 64 ulps of the distance to
+                // the far corner of the world bound: inside the span the reference's visiting order decides, outside it cannot.
+                const float far = maxf(absf(mr.o.x - s.wbMin[0]), absf(s.wbMax[0] - mr.o.x)) + maxf(absf(mr.o.y - s.wbMin[1]), absf(s.wbMax[1] - mr.o.y)) +
+                                  maxf(absf(mr.o.z - s.wbMin[2]), absf(s.wbMax[2] - mr.o.z));
+#ifdef MIPT_EXP_NO_SPAN_SLACK   // (experiment build; no test scene so far tells it from the default)
+                const float slack = 0.f * far;
+#else
+                const float slack = far * 0x1p-18f;
+#endif
+                if (tShape > 0.f) MisSpanWords(tShape * (1.f - 1e-5f) - slack, tShape * (1.f + 1e-5f) + slack, (unsigned)s.lightPrim[lightNum], &misTHi, &misWord);
+                else MisSpanWords(spanLo * 0.9999f - slack, spanHi + slack, (unsigned)s.lightPrim[lightNum], &misTHi, &misWord);
+            }
+            if constexpr (ACCUM) {   // f of the sampled direction into the tile (only if something will read it)
+                if (go) {
+                    if (ev.n > 0) AccumulateSpecular<NL, TM>(ev.lobes[0], mat->bxdf, ltp, rdTile, wrTile);
+                    else AccumulateFLocal<NL, TM>(fr, fr.WorldToLocal(isect.wo), wiLocal, Dot(wi, fr.ng) * Dot(isect.wo, fr.ng) > 0, nonSpec, ltp, rdTile, wrTile);
+                }
+            }
+            auto darkQuad = [&](int c, const float4 &fq) {   // (only: is f black? -- that decides whether the ray exists)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (4 * c + k < MI_NSPEC) fNonBlack |= (Get4(fq, k) * absdot != 0.f);
+            };
+            // (when the light's pdf for wi is 0 the estimate ends here, integrator.cpp:186-187:
+            // nothing reads the spectrum then, so it is not formed)
+            auto misQuad = [&](int c, const float4 &fq, const float4 &Lq) {
+                const float4 bt = loadBeta(c);
+                float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int b = 4 * c + k;
+                    if (b < MI_NSPEC) {
+                        const float f = Get4(fq, k) * absdot;
+                        fNonBlack |= (f != 0.f);
+                        const float LiB = isEnvLight ? IllumBin(s, envLe, b) : Get4(Lq, k);   // Le of the light if the ray reaches it
+                        const float Ld = DivChainExact((f * LiB) * weight, div);  // f * Li * Tr(=1) * weight / scatteringPdf / the light's choice
+                        Set4(out, k, Get4(bt, k) * Ld);
+                    }
+                }
+                tile.q[c][threadIdx.x] = out;
+            };
+            const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (SIMPLE_SPECTRA) {
+                const StraightPass<NL> sp = MakeStraightPass<NL, TM>(ev, mat->bxdf, div);
+                unsigned accF = 0u;
+                if (dark) {
+                    auto quad = [&](int c, auto exactTag) {
+                        constexpr bool EXACT = decltype(exactTag)::value;
+                        DivTrack trk;
+                        const float4 fq = StraightQuadF<NL, TM, EXACT>(sp, false, c, c == NQ - 1, trk);   // (f alone: no pdf divides it)
+                        unsigned aF = 0u;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) OrNonZero(aF, Get4(fq, k) * absdot);
+                        if (!QuadHolds<EXACT>(trk)) return false;
+                        accF |= aF;
+                        return true;
+                    };
+#pragma unroll 1
+                    for (int c = 0; c < NQ; ++c)
+                        if (!quad(c, std::false_type{})) quad(c, std::true_type{});
+                }
+                if (go && !dark) {
+                    auto quad = [&](int c, auto exactTag) {
+                        constexpr bool EXACT = decltype(exactTag)::value;
+                        DivTrack trk;
+                        const float4 bt = loadBeta(c);
+                        const float4 fq = StraightQuadF<NL, TM, EXACT>(sp, true, c, c == NQ - 1, trk);
+                        float4 Lq = isEnvLight ? zero4 : LoadSpec4(light.L, c);
+                        if (c == NQ - 1) Lq.w = 0.f;
+                        unsigned aF = 0u;
+                        float o[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const float f = Get4(fq, k) * absdot;
+                            OrNonZero(aF, f);
+                            const float LiB = isEnvLight ? ((4 * c + k < MI_NSPEC) ? IllumBin(s, envLe, min(4 * c + k, MI_NSPEC - 1)) : 0.f) : Get4(Lq, k);
+                            o[k] = Get4(bt, k) * DivChain<EXACT>((f * LiB) * weight, div, trk);
+                        }
+                        if (!QuadHolds<EXACT>(trk)) return false;
+                        tile.q[c][threadIdx.x] = make_float4(o[0], o[1], o[2], o[3]);
+                        accF |= aF;
+                        return true;
+                    };
+#pragma unroll 1
+                    for (int c = 0; c < NQ; ++c)
+                        if (!quad(c, std::false_type{})) quad(c, std::true_type{});
+                }
+                fNonBlack |= accF != 0u;
+            } else if (go) {   // (dark implies go; one loop, so that f's code is inlined once: two sites had left it an out-of-line call)
+#pragma unroll 1
+                for (int c = 0; c < NQ; ++c) {
+                    const float4 fq = FQuad<NL, TM, ACCUM>(tile, ev, mat->bxdf, c, ltp);
+                    if (dark) darkQuad(c, fq);
+                    else misQuad(c, fq, isEnvLight ? zero4 : LoadSpec4(light.L, c));
+                }
+            }
+            StoreSpectrumLines(tile, pool, Q_LMIS, slot, go && !dark);   // whole 128-B lines, as for the light sample
+            if (fNonBlack && go) {
+                // (a dark ray is queued and traced, but the estimate does not wait for it: no F_MIS)
+                if (dark) misWord = __uint_as_float(MIS_EXCL_DARK | (31u << MIS_EXCL_BITS));
+                pool.R(R_MI0, slot) = make_float4(mr.o.x, mr.o.y, mr.o.z, mr.d.x);
+                pool.R(R_MI1, slot) = make_float4(mr.d.y, mr.d.z, misTHi, misWord);
+                if (s.nLights > 1 && !dark) pool.I(I_MISLIGHT, slot) = lightNum;   // (one light: k_resolve_mis knows which)
+                flags |= dark ? SHADE_DARK_RAY : F_MIS;
+            }
+        }
+    }
+    return flags;
+}
+// Direct lighting: UniformSampleOneLight + EstimateDirect, integrator.cpp:85-215 -- the light choice and the five dimensions of
+// the estimate, then its two terms. Returns the flags it sets (F_NEE: the vertex has non-specular lobes and counts as a path).
+template <int NL, unsigned TM>
+DEV int DirectLighting(const DScene &s, const Pool &pool, SpectrumTile &tile, uint32_t slot, const PathHead &h, const SurfaceInteraction &isect,
+                       const BSDFFrame &fr, const mi_material *mat, const LobeTexT<NL> *ltp, bool lZero, PathSampler &ps,
+                       const int *__restrict__ pixelPlane, const int *__restrict__ samplePlane) {
+    constexpr bool HALTON_ONLY = (TM & TM_SAMPLERS) == 0;
+    const int nonSpec = MI_BSDF_ALL & ~MI_BSDF_SPECULAR;
+    int flags = 0;
+    if (NumComponents(fr, nonSpec) > 0) {
+        flags |= F_NEE;
+        if (s.nLights > 0) {
+            const uint32_t di = LightDistribIndex(s, isect.p);
+            float selPdf;
+            // the five dimensions of the estimate (light choice, light sample, BSDF sample)
+            float u5[5];
+            u5[0] = Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot);
+            const int lightNum = SampleDiscrete(s.ldFunc + (size_t)di * s.nLights, s.ldCdf + (size_t)di * (s.nLights + 1),
+                                                s.ldFuncInt[di], (int)s.nLights, u5[0], &selPdf);
+            if (selPdf != 0) {
+                // uLight = Get2D(), uScattering = Get2D() (integrator.cpp:100-101)
+                Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[1], &u5[2]);
+                Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[3], &u5[4]);
+                const float uL0 = u5[1], uL1 = u5[2], uS0 = u5[3], uS1 = u5[4];
+                const mi_light &light = s.lights[lightNum];
+                const bool selIsOne = (selPdf == 1.f);  // x / 1 == x: skip the division
+                const Divisor selDiv = MakeDivisor(selPdf);
+                flags |= LightSampleTerm<NL, TM>(s, pool, tile, slot, h, isect, fr, mat, ltp, lZero, light, uL0, uL1, selDiv, selIsOne);
+                flags |= BsdfSampleTerm<NL, TM>(s, pool, tile, slot, h, isect, fr, mat, ltp, light, lightNum, uS0, uS1, selDiv, selIsOne);
+            }
+        }
+    }
+    return flags;
+}
+// Continuation, path.cpp:131-184: the BSDF sample for the next direction, the new throughput, Russian roulette, the next ray.
+// etaScaleIn: the ray's (R_RAY1.w). Returns the flags it sets; *finished: the path ends here.
+template <int NL, unsigned TM>
+DEV int Continuation(const DScene &s, const Pool &pool, SpectrumTile &tile, uint32_t slot, const PathHead &h, const SurfaceInteraction &isect,
+                     const BSDFFrame &fr, const mi_material *mat, const LobeTexT<NL> *ltp, const V3 &rd, float etaScaleIn, PathSampler &ps,
+                     const int *__restrict__ pixelPlane, const int *__restrict__ samplePlane, bool *finished, bool *betaWritten) {
+    constexpr bool SIMPLE_SPECTRA = ShadeSimpleSpectra<NL, TM>, ACCUM = ShadeAccum<NL, TM>;
+    constexpr bool HALTON_ONLY = (TM & TM_SAMPLERS) == 0;
+    const TileColumnRead rdTile{tile};
+    const TileColumnWrite wrTile{tile};
+    auto loadBeta = [&](int c) -> float4 { return LoadBeta(pool, c, slot, h.betaOne); };
+    int flags = 0;
+    V3 wo = -rd, wi;
+    float pdf = 0;
+    int sflags = 0;
+    float u2[2];
+    Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u2[0], &u2[1]);
+    const float u0 = u2[0], u1 = u2[1];
+    BSDFEvalT<NL> ev;
+    V3 wiLocal;
+    const bool ok = BSDF_Sample_f<NL, TM, !ACCUM>(fr, wo, &wi, u0, u1, &pdf, MI_BSDF_ALL, &sflags, &ev, &wiLocal);
+    if constexpr (ACCUM) {
+        if (ok && pdf != 0.f) {
+            if (ev.n > 0) AccumulateSpecular<NL, TM>(ev.lobes[0], mat->bxdf, ltp, rdTile, wrTile);
+            else AccumulateFLocal<NL, TM>(fr, fr.WorldToLocal(wo), wiLocal, Dot(wi, fr.ng) * Dot(wo, fr.ng) > 0, MI_BSDF_ALL, ltp, rdTile, wrTile);
+        }
+    }
+    bool fNonBlack = false;
+    if (ok && pdf != 0.f) {
+        const float absdot = AbsDot(wi, isect.shN);
+        float etaScale = etaScaleIn;
+        if ((sflags & MI_BSDF_SPECULAR) && (sflags & MI_BSDF_TRANSMISSION)) {
+            float eta = mat->eta;
+            etaScale *= (Dot(wo, isect.n) > 0) ? (eta * eta) : 1 / (eta * eta);
+        }
+        const PdfChain div = MakePdfChain(MakeDivisor(pdf));
+        float maxRR = 0;
+        auto contQuad = [&](int c, const float4 &fq) {  // beta *= f * |wi.ns| / pdf (only meaningful when f is not black)
+            float4 bt = loadBeta(c);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int b = 4 * c + k;
+                if (b < MI_NSPEC) {
+                    const float f = Get4(fq, k);
+                    fNonBlack |= (f != 0.f);
+                    const float nb = Get4(bt, k) * DivChainExact(f * absdot, div);
+                    Set4(bt, k, nb);
+                    const float rr = nb * etaScale;
+                    maxRR = (b == 0) ? rr : maxf(maxRR, rr);
+                }
+            }
+            tile.q[c][threadIdx.x] = bt;
+        };
+        if constexpr (SIMPLE_SPECTRA) {
+            const StraightPass<NL> sp = MakeStraightPass<NL, TM>(ev, mat->bxdf, div);
+            unsigned accF = 0u;
+            auto quad = [&](int c, auto exactTag) {
+                constexpr bool EXACT = decltype(exactTag)::value;
+                DivTrack trk;
+                const float4 bt = loadBeta(c);
+                const float4 fq = StraightQuadF<NL, TM, EXACT>(sp, true, c, c == NQ - 1, trk);
+                unsigned aF = 0u;
+                float o[4], mr = maxRR;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float f = Get4(fq, k);
+                    OrNonZero(aF, f);
+                    o[k] = Get4(bt, k) * DivChain<EXACT>(f * absdot, div, trk);
+                    const float rr = o[k] * etaScale;
+                    if (k == 0) mr = (c == 0) ? rr : maxf(mr, rr);
+                    else if (k < 3) mr = maxf(mr, rr);
+                    else mr = (c == NQ - 1) ? mr : maxf(mr, rr);
+                }
+                if (c == NQ - 1) o[3] = bt.w;   // (the pad word keeps what it held)
+                if (!QuadHolds<EXACT>(trk)) return false;
+                tile.q[c][threadIdx.x] = make_float4(o[0], o[1], o[2], o[3]);
+                accF |= aF;
+                maxRR = mr;
+                return true;
+            };
+#pragma unroll 1
+            for (int c = 0; c < NQ; ++c)
+                if (!quad(c, std::false_type{})) quad(c, std::true_type{});
+            fNonBlack |= accF != 0u;
+        } else {
+#pragma unroll 1
+            for (int c = 0; c < NQ; ++c) contQuad(c, FQuad<NL, TM, ACCUM>(tile, ev, mat->bxdf, c, ltp));
+        }
+        // (the new throughput is stored below, once it is known that a later vertex will read it)
+        bool killed = false;
+        if (fNonBlack) {
+            // Russian roulette, path.cpp:176-184
+            if (maxRR < s.rrThreshold && h.bounces > 3) {
+                float q = maxf(.05f, 1 - maxRR);
+                if (Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot) < q) killed = true;
+                else {
+                    const Divisor inv = MakeDivisor(1 - q);
+#pragma unroll 1
+                    for (int c = 0; c < NQ; ++c) {
+                        float4 bt = tile.q[c][threadIdx.x];   // (the new beta, parked in the tile)
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (4 * c + k < MI_NSPEC) Set4(bt, k, DivBy(Get4(bt, k), inv));
+                        tile.q[c][threadIdx.x] = bt;
+                    }
+                }
+            }
+        }
+        // the next vertex reads the throughput if it is shaded (bounces + 1 < maxDepth) or may show emitted
+        // light (after a specular bounce, path.cpp:91-101); a path that ends here, or whose last ray only
+        // has to be traced, leaves none behind
+        const bool needBeta = fNonBlack && !killed && (h.bounces + 1 < s.maxDepth || (sflags & MI_BSDF_SPECULAR));
+        StoreSpectrumLines(tile, pool, Q_BETA, slot, needBeta);
+        if (needBeta) *betaWritten = true;
+        if (fNonBlack) {
+            if (killed) *finished = true;
+            else {
+                const Ray nr = SpawnRay(isect, wi);
+                pool.R(R_RAY0, slot) = make_float4(nr.o.x, nr.o.y, nr.o.z, nr.tMax);
+                pool.R(R_RAY1, slot) = make_float4(nr.d.x, nr.d.y, nr.d.z, etaScale);
+                if (sflags & MI_BSDF_SPECULAR) flags |= F_SPECULAR;
+            }
+        }
+    }
+    if (!(ok && pdf != 0.f && fNonBlack)) *finished = true;
+    return flags;
+}
+template <int NL, unsigned TM, bool LENS = false, bool MOTION = false>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT_SHADE_WAVES_PER_EU, 8))) k_shade(DScene s, Pool pool, DevCounters *ctr, unsigned classes) {
+    const ShadeEntry entry = ShadeQueueEntry(ctr, classes);
+    constexpr bool HALTON_ONLY = (TM & TM_SAMPLERS) == 0;
+    constexpr bool DISKS = TM_HOLDS_DISKS(TM);   // (a scene with disks is shaded by the general instances alone: ShadeInstanceOf)
+    __shared__ SpectrumTile tile;
+    unsigned totalPaths = 0, pathLen = 0, zeroNow = 0;
+    bool wantShadow = false, wantMis = false, wantDark = false;
+    uint32_t slot = 0;
+    if (entry.cls >= 0 && entry.qi < entry.count) {
+        slot = pool.shadeQ[(size_t)entry.cls * pool.n + entry.qi];
+        const PathHead h = LoadPathHead(pool, slot);
+        bool betaWritten = false;
+        int dimNow = h.dim;
+        // the ray and the interaction are needed by vertices that will be shaded or may show emitted light; an escaped
+        // ray without environment lights and a path at its last vertex need neither (k_resolve_extend ends those itself and
+        // does not queue them, EndsUnshaded: what this kernel writes for one, below, is FinishedWord)
+        const bool needIsect = h.found && (h.bounces < s.maxDepth || h.emitCheck);
+        const bool needRay = needIsect || (!h.found && h.emitCheck && TM_LIGHT(TM, MI_LIGHT_INFINITE) && s.nInfiniteLights > 0);
+        float4 ray0 = make_float4(0.f, 0.f, 0.f, 0.f), ray1 = make_float4(0.f, 0.f, 1.f, 1.f);
+        if (needRay) { ray0 = pool.R(R_RAY0, slot); ray1 = pool.R(R_RAY1, slot); }
+        MovingMatrices<MOTION> mm;
+        HitVertex<(TM & TM_INSTANCES) != 0, MOTION> hv;
+        SurfaceInteraction isect, isectObj;
+        BuildHitVertex<DISKS>(s, pool, slot, h.prim, ray0, ray1, needIsect, mm, hv, &isect, &isectObj);
+        const V3 &rd = hv.rd;
+        bool lZero = EmittedLight<TM>(s, pool, slot, h, isect.n, rd);
+        bool finished = !h.found || h.bounces >= s.maxDepth;
+        const bool passThrough = !finished && s.prims[h.prim].material < 0;
+        if (passThrough) PassThroughInterface(pool, slot, h, isect, rd);
+        int newFlags = 0;
         if (!finished && !passThrough) {
-            const mi_material *mat = &s.materials[s.prims[prim].material];
+            const mi_material *mat = &s.materials[s.prims[h.prim].material];
             BSDFFrame fr;
             fr.m = mat;
             fr.mask = 0xffu;
@@ -2224,149 +2877,8 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             LobeTexT<NL> lt;
             const LobeTexT<NL> *ltp = nullptr;
             if constexpr ((TM & TM_TEXTURED) != 0) {
-                // Material::ComputeScatteringFunctions with image textures: evaluate them at the hit, keep the lobes
-                // whose tested spectrum is not black (matte.cpp:55-63, plastic.cpp:52-68, uber.cpp:60-100, ...)
-                lt.hasR = lt.hasS = lt.mulR = lt.mulS = 0u;
-                lt.rules = 0u; lt.lum = 0.f; lt.hasK = 0u;
-                lt.basis = s.rgbIllum; lt.textures = s.textures;
+                TexturedScattering<NL, TM, LENS, MOTION>(s, pool, slot, h, hv, mm, isect, isectObj, mat, fr, lt);
                 ltp = &lt;
-                float u = 0.f, v = 0.f;
-                TriShading tsh;
-                bool haveUV = false;
-                if (mat->textured) {
-                    const int shape = s.prims[prim].shape;
-                    if (shape >= 0) {
-                        const float4 hr = pool.R(R_HIT, slot);
-                        TriTexCoords(s, shape, hr.y, hr.z, hr.w, inst >= 0 ? isectObj : isect, &u, &v, &tsh);
-                        haveUV = true;
-                    } else if (DISKS && IsDisk(s, ~shape))
-                        haveUV = DiskTexCoords(s.disks[~shape - s.nSpheres], roS, rdS, &u, &v, &tsh);
-                    else
-                        haveUV = SphereTexCoords(s.spheres[~shape], roS, rdS, &u, &v, &tsh);
-                    if constexpr ((TM & TM_INSTANCES) != 0) {
-                        if (inst >= 0) {
-                            if constexpr (MOTION) ShadingToWorld(instI2W, instW2I, &tsh);
-                            else ShadingToWorld(s.instances[inst].i2w, s.instances[inst].w2i, &tsh);
-                        }
-                    }
-                }
-                if (haveUV) {
-                    TexDifferentials td;
-                    td.dudx = td.dvdx = td.dudy = td.dvdy = 0;
-                    td.dpdx = td.dpdy = V3(0, 0, 0);
-                    if (flags & F_DIFF) {   // SurfaceInteraction::ComputeDifferentials, interaction.cpp:99-143
-                        if constexpr (LENS) {   // the lens camera's, from its offset rays: k_generate stored them
-                            CamDifferentials cd;
-                            cd.rxOrigin = V3(pool.F(P_LENSDIFF + 0, slot), pool.F(P_LENSDIFF + 1, slot), pool.F(P_LENSDIFF + 2, slot));
-                            cd.ryOrigin = V3(pool.F(P_LENSDIFF + 3, slot), pool.F(P_LENSDIFF + 4, slot), pool.F(P_LENSDIFF + 5, slot));
-                            cd.rxDirection = V3(pool.F(P_LENSDIFF + 6, slot), pool.F(P_LENSDIFF + 7, slot), pool.F(P_LENSDIFF + 8, slot));
-                            cd.ryDirection = V3(pool.F(P_LENSDIFF + 9, slot), pool.F(P_LENSDIFF + 10, slot), pool.F(P_LENSDIFF + 11, slot));
-                            td = ComputeDifferentials(isect.p, isect.n, isect.dpdu, tsh.dpdv, cd);
-                        } else {
-                        float lu = 0.f, lv = 0.f;
-                        // CameraToWorld for the offset rays: one call of CameraDifferentials on one local array
-                        float c2w[16];
-                        if (s.camera.animated) {   // (uniform) the camera sample's time and lens position again, and the transform at that time
-                            const int pixw = pool.I(I_PIXEL, slot);
-                            float cu0, cu1, tu;
-                            CameraSampleDims<true>(s, (int)(short)(pixw & 0xffff), pixw >> 16, (long long)pool.I(I_SAMPLE, slot), &cu0, &cu1, &lu, &lv, nullptr, &tu);
-                            MovingCameraToWorld(s.cameraMotion, lerpf(tu, s.camera.shutter_open, s.camera.shutter_close), c2w);
-                        } else {
-                            if (s.camera.lens_radius > 0) {   // the camera sample's lens position again
-                                const int pixw = pool.I(I_PIXEL, slot);
-                                float cu0, cu1;
-                                CameraSampleDims(s, (int)(short)(pixw & 0xffff), pixw >> 16, (long long)pool.I(I_SAMPLE, slot), &cu0, &cu1, &lu, &lv);
-                            }
-#pragma unroll
-                            for (int i = 0; i < 16; ++i) c2w[i] = s.camera.camera_to_world[i];
-                        }
-                        const CamDifferentials cd = CameraDifferentials(s, c2w, pool.F(P_FILMX, slot), pool.F(P_FILMY, slot), lu, lv, ro, rd, s.invSqrtSpp);
-                        td = ComputeDifferentials(isect.p, isect.n, isect.dpdu, tsh.dpdv, cd);
-                        }
-                    }
-                    if (mat->bump_tex >= 0) Bump<NOISE>(s, mat->bump_tex, u, v, td, tsh, &isect);   // `if (bumpMap) Bump(bumpMap, si)`
-                    // `rough = roughness->Evaluate(*si); if (remapRoughness) rough = RoughnessToAlpha(rough)` (plastic.cpp:57-62 ...)
-                    float rawU = mat->bxdf[0].p[6], rawV = mat->bxdf[0].p[7];   // (MI_ROUGH_GLASS: the values before the remap)
-                    if (mat->rough_flags & MI_ROUGH_DISNEY) {   // `Float rough = roughness->Evaluate(*si)`, disney.cpp:491
-                        fr.ov.disney = true;
-                        fr.ov.rough = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[0], u, v, isect.p, td);
-                    } else
-                    if (mat->rough_tex[0] >= 0) {
-                        const float rv = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[0], u, v, isect.p, td);
-                        fr.ov.u = (mat->rough_flags & MI_ROUGH_REMAP) ? RoughnessToAlpha(rv) : rv;
-                        fr.ov.onU = true;
-                        rawU = rv;
-                    }
-                    if (mat->rough_tex[1] >= 0) {
-                        if (mat->rough_tex[1] == mat->rough_tex[0]) { fr.ov.v = fr.ov.u; rawV = rawU; }
-                        else {
-                            const float rv = EvalFloatImageTexture<NOISE>(s, mat->rough_tex[1], u, v, isect.p, td);
-                            fr.ov.v = (mat->rough_flags & MI_ROUGH_REMAP) ? RoughnessToAlpha(rv) : rv;
-                            rawV = rv;
-                        }
-                        fr.ov.onV = true;
-                    }
-                    if (mat->sigma_tex >= 0) {   // `Float sig = Clamp(sigma->Evaluate(*si), 0, 90)`, matte.cpp:57; OrenNayar's constructor
-                        const float sig = clampf(EvalFloatImageTexture<NOISE>(s, mat->sigma_tex, u, v, isect.p, td), 0.f, 90.f);
-                        if (sig == 0) fr.ov.sigMode = 2;
-                        else {
-                            const float sigma = (kPi / 180) * sig, sigma2 = sigma * sigma;
-                            fr.ov.sigMode = 1;
-                            fr.ov.sigA = 1.f - (sigma2 / (2.f * (sigma2 + 0.33f)));
-                            fr.ov.sigB = 0.45f * sigma2 / (sigma2 + 0.09f);
-                        }
-                    }
-                    unsigned mask = 0u;
-                    for (int i = 0; i < mat->n_bxdfs; ++i) {
-                        const mi_lobe_tex ltx = mat->tex[i];
-                        if (ltx.tex_R < 0 && ltx.tex_S < 0) { mask |= 1u << i; continue; }
-                        if (i >= NL) continue;
-                        if (ltx.tex_R >= 0) {
-                            lt.r[i] = EvalImageTexture<NOISE>(s, ltx.tex_R, u, v, isect.p, td);
-                            if (ltx.rule == MI_LOBE_METAL) lt.hasK |= 1u << i;   // (k's texture: the lobe's R stays the constant)
-                            else lt.hasR |= 1u << i;
-                            if (ltx.flags & MI_LOBE_TEX_MUL_R) lt.mulR |= 1u << i;
-                        }
-                        if (ltx.tex_S >= 0) {
-                            lt.s[i] = EvalImageTexture<NOISE>(s, ltx.tex_S, u, v, isect.p, td);
-                            lt.hasS |= 1u << i;
-                            if (ltx.flags & MI_LOBE_TEX_MUL_S) lt.mulS |= 1u << i;
-                        }
-                        lt.rules |= (unsigned)(ltx.rule & 15) << (4 * i);
-                        if (ltx.rule >= MI_LOBE_ALWAYS) {   // "disney": lobes are added whatever the colour is
-                            if (ltx.rule >= MI_LOBE_DISNEY_SHEEN && ltx.rule <= MI_LOBE_DISNEY_STRANS && lt.lum == 0.f) {   // lum = c.y(), once per vertex (every lobe has the same colour)
-                                float yy = 0.f;
-                                for (int b = 0; b < MI_NSPEC; ++b) yy += SpecYBinAccum(s, b, TexBin(lt.basis, lt.textures, lt.r[i], b));
-                                lt.lum = YScale(yy);
-                            }
-                            mask |= 1u << i;
-                            continue;
-                        }
-                        // (the spectrum the material tests with IsBlack(), a quad of bins at a time; only what the lobe's rule reads)
-                        unsigned rNZ = 0u, sNZ = 0u, texNZ = 0u;
-                        auto orQuad = [](unsigned &acc, const float4 &q, int c) {
-                            OrNonZero(acc, q.x); OrNonZero(acc, q.y); OrNonZero(acc, q.z);
-                            if (c != NQ - 1) OrNonZero(acc, q.w);   // bin 31 does not exist
-                        };
-#pragma unroll 1
-                        for (int c = 0; c < NQ; ++c) {
-                            if (ltx.rule != MI_LOBE_IF_TEX) orQuad(rNZ, TexturedQuad(lt, mat->bxdf[i], i, 0, c), c);
-                            if (ltx.rule == MI_LOBE_IF_R_OR_S) orQuad(sNZ, TexturedQuad(lt, mat->bxdf[i], i, 1, c), c);
-                            if (ltx.rule == MI_LOBE_IF_TEX) {
-                                if (ltx.tex_R >= 0) orQuad(texNZ, TexQuad(lt.basis, lt.textures, lt.r[i], c), c);
-                                if (ltx.tex_S >= 0) orQuad(texNZ, TexQuad(lt.basis, lt.textures, lt.s[i], c), c);
-                            }
-                        }
-                        const bool rNonBlack = rNZ != 0u, sNonBlack = sNZ != 0u, texNonBlack = texNZ != 0u;
-                        const bool present = ltx.rule == MI_LOBE_IF_R_OR_S ? (rNonBlack || sNonBlack) : (ltx.rule == MI_LOBE_IF_TEX ? texNonBlack : rNonBlack);
-                        if (present) mask |= 1u << i;
-                    }
-                    if (mat->rough_flags & MI_ROUGH_GLASS) {   // glass.cpp:66: `isSpecular = urough == 0 && vrough == 0` at this hit
-                        const bool spec = rawU == 0 && rawV == 0;
-                        mask &= spec ? 1u : ~1u;   // lobe 0 is the FresnelSpecular one
-                    }
-                    fr.mask = mask;
-                }
             }
             // BSDF ctor, reflection.h:170-176 (after Bump(): it reads the shading geometry)
             fr.ns = isect.shN; fr.ng = isect.n; fr.ss = Normalize(isect.shDpdu); fr.ts = Cross(fr.ns, fr.ss);
@@ -2376,404 +2888,9 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             ps.dim = dimNow;
             if constexpr (!HALTON_ONLY) { if (IsPixelSampler(s)) ps.dim = pool.I(I_DIM, slot); }
             const int *__restrict__ pixelPlane = pool.i + (size_t)I_PIXEL * pool.n, *__restrict__ samplePlane = pool.i + (size_t)I_SAMPLE * pool.n;
-            const int nonSpec = MI_BSDF_ALL & ~MI_BSDF_SPECULAR;
-            // ---- direct lighting: UniformSampleOneLight + EstimateDirect, integrator.cpp:85-215
-            if (NumComponents(fr, nonSpec) > 0) {
-                ++totalPaths;
-                newFlags |= F_NEE;
-                if (s.nLights > 0) {
-                    const uint32_t di = LightDistribIndex(s, isect.p);
-                    float selPdf;
-                    // the five dimensions of the estimate (light choice, light sample, BSDF sample)
-                    float u5[5];
-                    u5[0] = Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot);
-                    const int lightNum = SampleDiscrete(s.ldFunc + (size_t)di * s.nLights, s.ldCdf + (size_t)di * (s.nLights + 1),
-                                                        s.ldFuncInt[di], (int)s.nLights, u5[0], &selPdf);
-                    if (selPdf != 0) {
-                        // uLight = Get2D(), uScattering = Get2D() (integrator.cpp:100-101)
-                        Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[1], &u5[2]);
-                        Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[3], &u5[4]);
-                        const float uL0 = u5[1], uL1 = u5[2], uS0 = u5[3], uS1 = u5[4];
-                        const mi_light &light = s.lights[lightNum];
-                        const bool selIsOne = (selPdf == 1.f);  // x / 1 == x: skip the division
-                        const Divisor selDiv = MakeDivisor(selPdf);
-                        const LightSample ls = SampleLi<TM>(s, light, isect, uL0, uL1);
-                        const float lightPdf = ls.pdf;
-                        if (lightPdf > 0 && !ls.black) {
-                            BSDFEvalT<NL> ev;
-                            if constexpr (ACCUM) AccumulateF<NL, TM>(fr, isect.wo, ls.wi, nonSpec, ltp, rdTile, wrTile);
-                            else BSDF_f<NL, TM>(fr, isect.wo, ls.wi, nonSpec, &ev);
-                            auto fQuad = [&](int c) -> float4 { if constexpr (ACCUM) return rdTile(c); else return EvalQuad<NL, TM>(ev, mat->bxdf, c, ltp); };
-                            const float absdot = AbsDot(ls.wi, isect.shN);
-                            const float scatteringPdf = BSDF_Pdf<TM>(fr, isect.wo, ls.wi, nonSpec);
-                            const bool delta = IsDeltaLight<TM_HOLDS_PROJECTION(TM)>(light);
-                            float weight = 1.f;
-                            if (!delta) { float pf = 1 * lightPdf, pg = 1 * scatteringPdf; weight = (pf * pf) / (pf * pf + pg * pg); }
-                            const Divisor lpDiv = MakeDivisor(lightPdf);
-                            bool fNonBlack = false, liNonBlack = false, nzAny = false;
-                            // the path's L so far, quad c: the candidate is L + contribution (F_CAND)
-                            auto lBase = [&](int c) -> float4 { return lZero ? make_float4(0.f, 0.f, 0.f, 0.f) : pool.Q(lPlane + c, slot); };
-                            auto neeQuad = [&](int c, const float4 &fq, const float4 &Lq) {
-                                const float4 bt = loadBeta(c), l4 = lBase(c);
-                                float4 out = l4;
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) {
-                                    const int b = 4 * c + k;
-                                    if (b < MI_NSPEC) {
-                                        const float f = Get4(fq, k) * absdot;
-                                        const float Li = Get4(Lq, k);
-                                        fNonBlack |= (f != 0.f);
-                                        liNonBlack |= (Li != 0.f);
-                                        float Ld = delta ? DivBy(f * Li, lpDiv) : DivBy((f * Li) * weight, lpDiv);
-                                        if (!selIsOne) Ld = DivBy(Ld, selDiv);
-                                        const float contrib = Get4(bt, k) * Ld;
-                                        nzAny |= (contrib != 0.f);
-                                        Set4(out, k, Get4(l4, k) + contrib);
-                                    }
-                                }
-                                tile.q[c][threadIdx.x] = out;
-                            };
-                            if constexpr (SIMPLE_SPECTRA) {
-                                // straight-line form (d_bsdf.h, SimpleLobes); a quad in which a quotient leaves DivBy's fast range is redone with DivBy
-                                const SimpleLobes<NL> sl = MakeSimpleLobes<NL, TM>(ev);
-                                const mi_bxdf *bx = mat->bxdf;
-                                const bool allSelOne = __all(selIsOne);
-                                const bool divFast = sl.divisorsFast && lpDiv.fast && (selIsOne || selDiv.fast);
-                                unsigned accF = 0u, accLi = 0u, accNz = 0u;
-                                auto quad = [&](int c, auto exactTag) {
-                                    constexpr bool EXACT = decltype(exactTag)::value;
-                                    DivTrack trk;
-                                    trk.Reset(divFast);
-                                    const float4 bt = loadBeta(c), l4 = lBase(c);
-                                    float4 fq = SimpleEvalQuad<NL, TM, EXACT>(sl, bx, c, trk), Lq = LiQuad<TM>(s, light, ls, c);
-                                    if (c == NQ - 1) { fq.w = 0.f; Lq.w = 0.f; }   // bin 31 does not exist
-                                    unsigned aF = 0u, aLi = 0u, aNz = 0u;
-                                    float o[4];
-#pragma unroll
-                                    for (int k = 0; k < 4; ++k) {
-                                        const float f = Get4(fq, k) * absdot;
-                                        const float Li = Get4(Lq, k);
-                                        OrNonZero(aF, f); OrNonZero(aLi, Li);
-                                        const float x = (f * Li) * weight;   // (weight == 1 for a delta light: x * 1 == x)
-                                        float Ld;
-                                        if constexpr (EXACT) { Ld = DivBy(x, lpDiv); if (!selIsOne) Ld = DivBy(Ld, selDiv); }
-                                        else {
-                                            Ld = DivFast(x, lpDiv.d, lpDiv.r, trk);
-                                            if (!allSelOne) { const float Ld2 = DivFast(Ld, selDiv.d, selDiv.r, trk); Ld = selIsOne ? Ld : Ld2; }
-                                        }
-                                        o[k] = Get4(bt, k) * Ld;
-                                        OrNonZero(aNz, o[k]);
-                                    }
-                                    if (!EXACT && __any(trk.Bad())) return false;
-                                    tile.q[c][threadIdx.x] = make_float4(l4.x + o[0], l4.y + o[1], l4.z + o[2], l4.w + o[3]);
-                                    accF |= aF; accLi |= aLi; accNz |= aNz;
-                                    return true;
-                                };
-#pragma unroll 1
-                                for (int c = 0; c < NQ; ++c)
-                                    if (!quad(c, std::false_type{})) quad(c, std::true_type{});
-                                fNonBlack |= accF != 0u; liNonBlack |= accLi != 0u; nzAny |= accNz != 0u;
-                            } else {
-#pragma unroll 1
-                                for (int c = 0; c < NQ; ++c) neeQuad(c, fQuad(c), LiQuad<TM>(s, light, ls, c));
-                            }
-                            // the tile holds L + contribution, the candidate (F_CAND): only one whose shadow ray will be traced
-                            // is ever read
-                            const bool traced = fNonBlack && liNonBlack;
-                            StoreSpectrumLines(tile, pool, LOtherPlane(flags), slot, traced);
-                            if (traced) newFlags |= F_CAND | (nzAny ? F_NEE_NZ : 0);
-                            if (traced) {  // the shadow ray is traced iff f != 0 (integrator.cpp:138-150)
-                                Ray sr = SpawnRayTo(isect, ls.pLight);
-                                pool.R(R_SH0, slot) = make_float4(sr.o.x, sr.o.y, sr.o.z, sr.d.x);
-                                pool.R(R_SH1, slot) = make_float4(sr.d.y, sr.d.z, 0.f, 0.f);
-                                newFlags |= F_SHADOW;
-                            }
-                        }
-                        if (!IsDeltaLight<TM_HOLDS_PROJECTION(TM)>(light)) {  // BSDF sampling with MIS, integrator.cpp:167-213
-                            V3 wi;
-                            float sPdf = 0;
-                            int sampledType = 0;
-                            BSDFEvalT<NL> ev;
-                            V3 wiLocal;
-                            const bool ok = BSDF_Sample_f<NL, TM, !ACCUM>(fr, isect.wo, &wi, uS0, uS1, &sPdf, nonSpec, &sampledType, &ev, &wiLocal);
-                            auto fQuad = [&](int c) -> float4 { if constexpr (ACCUM) return rdTile(c); else return EvalQuad<NL, TM>(ev, mat->bxdf, c, ltp); };
-                            if (ok && sPdf > 0) {
-                                const float absdot = AbsDot(wi, isect.shN);
-                                // Pdf_Li has no side effect: evaluate it before knowing whether f is black
-                                float weight = 1;
-                                bool go = true;
-                                float tShape = -1.f;   // a triangle light: where wi meets it
-                                if (!(sampledType & MI_BSDF_SPECULAR)) {
-                                    const float lp = (TM_LIGHT(TM, MI_LIGHT_INFINITE) && light.type == MI_LIGHT_INFINITE) ? InfinitePdfLi(s, light, wi)
-                                                                                       : ShapePdf<DISKS>(s, light.shape, light.area, isect, wi, &tShape);
-                                    if (lp == 0) go = false;
-                                    else { float pf = 1 * sPdf, pg = 1 * lp; weight = (pf * pf) / (pf * pf + pg * pg); }
-                                }
-                                const bool isEnvLight = TM_LIGHT(TM, MI_LIGHT_INFINITE) && light.type == MI_LIGHT_INFINITE;
-                                IllumRGB envLe;
-                                envLe.i1 = envLe.i2 = 0; envLe.w0 = envLe.w1 = envLe.w2 = 0;
-                                if (isEnvLight && go) envLe = InfiniteLe(s, light, wi);   // light.Le(ray) when the ray escapes
-                                const Divisor spDiv = MakeDivisor(sPdf);
-                                bool fNonBlack = false;
-                                // a ray that cannot reach the sampled area light is traced all the same (the reference
-                                // traces it), but its contribution is never read: a dark ray (MIS_EXCL_DARK)
-                                const Ray mr = SpawnRay(isect, wi);
-                                float spanLo = 0.f, spanHi = kInfinity;
-                                const bool dark = go && !isEnvLight && !RaySpanInBox(mr.o, mr.d, s.lightBounds[2 * lightNum], s.lightBounds[2 * lightNum + 1], &spanLo, &spanHi);
-                                float misTHi = kInfinity, misWord = __uint_as_float(MIS_EXCL_NONE | (31u << MIS_EXCL_BITS));   // (environment light, dark ray: any hit ends it)
-                                if (s.misAny && go && !dark && !isEnvLight) {
-                                    // a triangle: Shape::Pdf has intersected it (the same test the traversal runs); a sphere: its span in the
-                                    // dilated bounds. Either way widened by what the float arithmetic of the triangle and box tests can disagree
-                                    // by about where things are along the ray: those work on coordinates relative to the ray's origin, so their
-                                    // absolute error in t grows with the distance of the farthest vertex, a few ulps of it (a ray that starts
-                                    // 1e-3 above a 2000-unit ground plane meets it at a t that is 10 % noise, and the plane's box later than that:
-                                    // tests/test_gpu_parity.py::test_mis_visibility_kernel_verdicts_on_recorded_rays). 64 ulps of the distance to
-                                    // the far corner of the world bound: inside the span the reference's visiting order decides, outside it cannot.
-                                    const float far = maxf(absf(mr.o.x - s.wbMin[0]), absf(s.wbMax[0] - mr.o.x)) + maxf(absf(mr.o.y - s.wbMin[1]), absf(s.wbMax[1] - mr.o.y)) +
-                                                      maxf(absf(mr.o.z - s.wbMin[2]), absf(s.wbMax[2] - mr.o.z));
-#ifdef MIPT_EXP_NO_SPAN_SLACK   // (experiment build; no test scene so far tells it from the default)
-                                    const float slack = 0.f * far;
-#else
-                                    const float slack = far * 0x1p-18f;
-#endif
-                                    if (tShape > 0.f) MisSpanWords(tShape * (1.f - 1e-5f) - slack, tShape * (1.f + 1e-5f) + slack, (unsigned)s.lightPrim[lightNum], &misTHi, &misWord);
-                                    else MisSpanWords(spanLo * 0.9999f - slack, spanHi + slack, (unsigned)s.lightPrim[lightNum], &misTHi, &misWord);
-                                }
-                                if constexpr (ACCUM) {   // f of the sampled direction into the tile (only if something will read it)
-                                    if (go) {
-                                        if (ev.n > 0) AccumulateSpecular<NL, TM>(ev.lobes[0], mat->bxdf, ltp, rdTile, wrTile);
-                                        else AccumulateFLocal<NL, TM>(fr, fr.WorldToLocal(isect.wo), wiLocal, Dot(wi, fr.ng) * Dot(isect.wo, fr.ng) > 0, nonSpec, ltp, rdTile, wrTile);
-                                    }
-                                }
-                                auto darkQuad = [&](int c, const float4 &fq) {   // (only: is f black? -- that decides whether the ray exists)
-#pragma unroll
-                                    for (int k = 0; k < 4; ++k)
-                                        if (4 * c + k < MI_NSPEC) fNonBlack |= (Get4(fq, k) * absdot != 0.f);
-                                };
-                                // (when the light's pdf for wi is 0 the estimate ends here, integrator.cpp:186-187:
-                                // nothing reads the spectrum then, so it is not formed)
-                                auto misQuad = [&](int c, const float4 &fq, const float4 &Lq) {
-                                    const float4 bt = loadBeta(c);
-                                    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                                    for (int k = 0; k < 4; ++k) {
-                                        const int b = 4 * c + k;
-                                        if (b < MI_NSPEC) {
-                                            const float f = Get4(fq, k) * absdot;
-                                            fNonBlack |= (f != 0.f);
-                                            const float LiB = isEnvLight ? IllumBin(s, envLe, b) : Get4(Lq, k);   // Le of the light if the ray reaches it
-                                            float Ld = DivBy((f * LiB) * weight, spDiv);  // f * Li * Tr(=1) * weight / scatteringPdf
-                                            if (!selIsOne) Ld = DivBy(Ld, selDiv);
-                                            Set4(out, k, Get4(bt, k) * Ld);
-                                        }
-                                    }
-                                    tile.q[c][threadIdx.x] = out;
-                                };
-                                const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                                if constexpr (SIMPLE_SPECTRA) {
-                                    const SimpleLobes<NL> sl = MakeSimpleLobes<NL, TM>(ev);
-                                    const mi_bxdf *bx = mat->bxdf;
-                                    const bool allSelOne = __all(selIsOne);
-                                    const bool divFast = sl.divisorsFast && spDiv.fast && (selIsOne || selDiv.fast);
-                                    unsigned accF = 0u;
-                                    if (dark) {
-                                        auto quad = [&](int c, auto exactTag) {
-                                            constexpr bool EXACT = decltype(exactTag)::value;
-                                            DivTrack trk;
-                                            trk.Reset(sl.divisorsFast);
-                                            float4 fq = SimpleEvalQuad<NL, TM, EXACT>(sl, bx, c, trk);
-                                            if (c == NQ - 1) fq.w = 0.f;
-                                            unsigned aF = 0u;
-#pragma unroll
-                                            for (int k = 0; k < 4; ++k) OrNonZero(aF, Get4(fq, k) * absdot);
-                                            if (!EXACT && __any(trk.Bad())) return false;
-                                            accF |= aF;
-                                            return true;
-                                        };
-#pragma unroll 1
-                                        for (int c = 0; c < NQ; ++c)
-                                            if (!quad(c, std::false_type{})) quad(c, std::true_type{});
-                                    }
-                                    if (go && !dark) {
-                                        auto quad = [&](int c, auto exactTag) {
-                                            constexpr bool EXACT = decltype(exactTag)::value;
-                                            DivTrack trk;
-                                            trk.Reset(divFast);
-                                            const float4 bt = loadBeta(c);
-                                            float4 fq = SimpleEvalQuad<NL, TM, EXACT>(sl, bx, c, trk), Lq = isEnvLight ? zero4 : LoadSpec4(light.L, c);
-                                            if (c == NQ - 1) { fq.w = 0.f; Lq.w = 0.f; }
-                                            unsigned aF = 0u;
-                                            float o[4];
-#pragma unroll
-                                            for (int k = 0; k < 4; ++k) {
-                                                const float f = Get4(fq, k) * absdot;
-                                                OrNonZero(aF, f);
-                                                const float LiB = isEnvLight ? ((4 * c + k < MI_NSPEC) ? IllumBin(s, envLe, min(4 * c + k, MI_NSPEC - 1)) : 0.f) : Get4(Lq, k);
-                                                const float x = (f * LiB) * weight;
-                                                float Ld;
-                                                if constexpr (EXACT) { Ld = DivBy(x, spDiv); if (!selIsOne) Ld = DivBy(Ld, selDiv); }
-                                                else {
-                                                    Ld = DivFast(x, spDiv.d, spDiv.r, trk);
-                                                    if (!allSelOne) { const float Ld2 = DivFast(Ld, selDiv.d, selDiv.r, trk); Ld = selIsOne ? Ld : Ld2; }
-                                                }
-                                                o[k] = Get4(bt, k) * Ld;
-                                            }
-                                            if (!EXACT && __any(trk.Bad())) return false;
-                                            tile.q[c][threadIdx.x] = make_float4(o[0], o[1], o[2], o[3]);
-                                            accF |= aF;
-                                            return true;
-                                        };
-#pragma unroll 1
-                                        for (int c = 0; c < NQ; ++c)
-                                            if (!quad(c, std::false_type{})) quad(c, std::true_type{});
-                                    }
-                                    fNonBlack |= accF != 0u;
-                                } else {
-                                    if (dark) {
-#pragma unroll 1
-                                        for (int c = 0; c < NQ; ++c) darkQuad(c, fQuad(c));
-                                    }
-                                    if (go && !dark) {
-#pragma unroll 1
-                                        for (int c = 0; c < NQ; ++c) misQuad(c, fQuad(c), isEnvLight ? zero4 : LoadSpec4(light.L, c));
-                                    }
-                                }
-                                StoreSpectrumLines(tile, pool, Q_LMIS, slot, go && !dark);   // whole 128-B lines, as for the light sample
-                                if (fNonBlack && go) {
-                                    // (a dark ray is queued and traced, but the estimate does not wait for it: no F_MIS)
-                                    if (dark) misWord = __uint_as_float(MIS_EXCL_DARK | (31u << MIS_EXCL_BITS));
-                                    pool.R(R_MI0, slot) = make_float4(mr.o.x, mr.o.y, mr.o.z, mr.d.x);
-                                    pool.R(R_MI1, slot) = make_float4(mr.d.y, mr.d.z, misTHi, misWord);
-                                    if (s.nLights > 1 && !dark) pool.I(I_MISLIGHT, slot) = lightNum;   // (one light: k_resolve_mis knows which)
-                                    newFlags |= dark ? SHADE_DARK_RAY : F_MIS;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            // ---- sample the BSDF for the next direction, path.cpp:131-150
-            {
-                V3 wo = -rd, wi;
-                float pdf = 0;
-                int sflags = 0;
-                float u2[2];
-                Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u2[0], &u2[1]);
-                const float u0 = u2[0], u1 = u2[1];
-                BSDFEvalT<NL> ev;
-                V3 wiLocal;
-                const bool ok = BSDF_Sample_f<NL, TM, !ACCUM>(fr, wo, &wi, u0, u1, &pdf, MI_BSDF_ALL, &sflags, &ev, &wiLocal);
-                if constexpr (ACCUM) {
-                    if (ok && pdf != 0.f) {
-                        if (ev.n > 0) AccumulateSpecular<NL, TM>(ev.lobes[0], mat->bxdf, ltp, rdTile, wrTile);
-                        else AccumulateFLocal<NL, TM>(fr, fr.WorldToLocal(wo), wiLocal, Dot(wi, fr.ng) * Dot(wo, fr.ng) > 0, MI_BSDF_ALL, ltp, rdTile, wrTile);
-                    }
-                }
-                auto fQuad = [&](int c) -> float4 { if constexpr (ACCUM) return rdTile(c); else return EvalQuad<NL, TM>(ev, mat->bxdf, c, ltp); };
-                bool fNonBlack = false;
-                if (ok && pdf != 0.f) {
-                    const float absdot = AbsDot(wi, isect.shN);
-                    float etaScale = ray1.w;
-                    if ((sflags & MI_BSDF_SPECULAR) && (sflags & MI_BSDF_TRANSMISSION)) {
-                        float eta = mat->eta;
-                        etaScale *= (Dot(wo, isect.n) > 0) ? (eta * eta) : 1 / (eta * eta);
-                    }
-                    const Divisor pdfDiv = MakeDivisor(pdf);
-                    float maxRR = 0;
-                    auto contQuad = [&](int c, const float4 &fq) {  // beta *= f * |wi.ns| / pdf (only meaningful when f is not black)
-                        float4 bt = loadBeta(c);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int b = 4 * c + k;
-                            if (b < MI_NSPEC) {
-                                const float f = Get4(fq, k);
-                                fNonBlack |= (f != 0.f);
-                                const float nb = Get4(bt, k) * DivBy(f * absdot, pdfDiv);
-                                Set4(bt, k, nb);
-                                const float rr = nb * etaScale;
-                                maxRR = (b == 0) ? rr : maxf(maxRR, rr);
-                            }
-                        }
-                        tile.q[c][threadIdx.x] = bt;
-                    };
-                    if constexpr (SIMPLE_SPECTRA) {
-                        const SimpleLobes<NL> sl = MakeSimpleLobes<NL, TM>(ev);
-                        const mi_bxdf *bx = mat->bxdf;
-                        const bool divFast = sl.divisorsFast && pdfDiv.fast;
-                        unsigned accF = 0u;
-                        auto quad = [&](int c, auto exactTag) {
-                            constexpr bool EXACT = decltype(exactTag)::value;
-                            DivTrack trk;
-                            trk.Reset(divFast);
-                            const float4 bt = loadBeta(c);
-                            float4 fq = SimpleEvalQuad<NL, TM, EXACT>(sl, bx, c, trk);
-                            if (c == NQ - 1) fq.w = 0.f;
-                            unsigned aF = 0u;
-                            float o[4], mr = maxRR;
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const float f = Get4(fq, k);
-                                OrNonZero(aF, f);
-                                const float x = f * absdot;
-                                o[k] = Get4(bt, k) * (EXACT ? DivBy(x, pdfDiv) : DivFast(x, pdfDiv.d, pdfDiv.r, trk));
-                                const float rr = o[k] * etaScale;
-                                if (k == 0) mr = (c == 0) ? rr : maxf(mr, rr);
-                                else if (k < 3) mr = maxf(mr, rr);
-                                else mr = (c == NQ - 1) ? mr : maxf(mr, rr);
-                            }
-                            if (c == NQ - 1) o[3] = bt.w;   // (the pad word keeps what it held)
-                            if (!EXACT && __any(trk.Bad())) return false;
-                            tile.q[c][threadIdx.x] = make_float4(o[0], o[1], o[2], o[3]);
-                            accF |= aF;
-                            maxRR = mr;
-                            return true;
-                        };
-#pragma unroll 1
-                        for (int c = 0; c < NQ; ++c)
-                            if (!quad(c, std::false_type{})) quad(c, std::true_type{});
-                        fNonBlack |= accF != 0u;
-                    } else {
-#pragma unroll 1
-                        for (int c = 0; c < NQ; ++c) contQuad(c, fQuad(c));
-                    }
-                    // (the new throughput is stored below, once it is known that a later vertex will read it)
-                    bool killed = false;
-                    if (fNonBlack) {
-                        // Russian roulette, path.cpp:176-184
-                        if (maxRR < s.rrThreshold && bounces > 3) {
-                            float q = maxf(.05f, 1 - maxRR);
-                            if (Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot) < q) killed = true;
-                            else {
-                                const Divisor inv = MakeDivisor(1 - q);
-#pragma unroll 1
-                                for (int c = 0; c < NQ; ++c) {
-                                    float4 bt = tile.q[c][threadIdx.x];   // (the new beta, parked in the tile)
-#pragma unroll
-                                    for (int k = 0; k < 4; ++k)
-                                        if (4 * c + k < MI_NSPEC) Set4(bt, k, DivBy(Get4(bt, k), inv));
-                                    tile.q[c][threadIdx.x] = bt;
-                                }
-                            }
-                        }
-                    }
-                    // the next vertex reads the throughput if it is shaded (bounces + 1 < maxDepth) or may show emitted
-                    // light (after a specular bounce, path.cpp:91-101); a path that ends here, or whose last ray only
-                    // has to be traced, leaves none behind
-                    const bool needBeta = fNonBlack && !killed && (bounces + 1 < s.maxDepth || (sflags & MI_BSDF_SPECULAR));
-                    StoreSpectrumLines(tile, pool, Q_BETA, slot, needBeta);
-                    if (needBeta) betaWritten = true;
-                    if (fNonBlack) {
-                        if (killed) finished = true;
-                        else {
-                            const Ray nr = SpawnRay(isect, wi);
-                            pool.R(R_RAY0, slot) = make_float4(nr.o.x, nr.o.y, nr.o.z, nr.tMax);
-                            pool.R(R_RAY1, slot) = make_float4(nr.d.x, nr.d.y, nr.d.z, etaScale);
-                            if (sflags & MI_BSDF_SPECULAR) newFlags |= F_SPECULAR;
-                        }
-                    }
-                }
-                if (!(ok && pdf != 0.f && fNonBlack)) finished = true;
-            }
+            newFlags |= DirectLighting<NL, TM>(s, pool, tile, slot, h, isect, fr, mat, ltp, lZero, ps, pixelPlane, samplePlane);
+            if (newFlags & F_NEE) ++totalPaths;
+            newFlags |= Continuation<NL, TM>(s, pool, tile, slot, h, isect, fr, mat, ltp, rd, ray1.w, ps, pixelPlane, samplePlane, &finished, &betaWritten);
             dimNow = ps.dim;
             if constexpr (!HALTON_ONLY) { if (IsPixelSampler(s)) { pool.I(I_DIM, slot) = ps.dim; dimNow = 0; } }
             if (!HALTON_ONLY && s.samplerType >= MI_SAMPLER_RANDOM) {   // the stream moves on with the path
@@ -2782,23 +2899,8 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(MIPT
             }
         }
         if (!passThrough) {
-            if (finished) {
-                // ReportValue(pathLength, bounces): `bounces` at the break of path.cpp's loop
-                pathLen = (unsigned)bounces;
-                newFlags = (newFlags & (F_NEE | F_SHADOW | F_MIS | F_CAND | F_NEE_NZ | SHADE_DARK_RAY)) | F_FINISHED;
-            } else {
-                newFlags |= F_ALIVE;
-            }
-            if (lZero) newFlags |= F_L_ZERO;
-            newFlags |= flags & F_L_IN_B;
-            if (betaOne && !betaWritten) newFlags |= F_BETA_ONE;
-            wantShadow = (newFlags & F_SHADOW) != 0;
-            // (a dark ray has a queue of its own where k_trav<3> serves the live ones; with k_trav<2> both share misQ)
-            wantDark = s.misAny && (newFlags & SHADE_DARK_RAY) != 0;
-            wantMis = (newFlags & F_MIS) != 0 || (!s.misAny && (newFlags & SHADE_DARK_RAY) != 0);
-            // a direct-lighting estimate with neither ray pending (a dark MIS ray is none) is already known to be black
-            if ((newFlags & F_NEE) && !wantShadow && !(newFlags & F_MIS)) { ++zeroNow; newFlags &= ~F_NEE; }
-            pool.I(I_FLAGS, slot) = StateWord(newFlags, finished ? bounces : bounces + 1, dimNow);
+            if (finished) pathLen = (unsigned)h.bounces;   // ReportValue(pathLength, bounces): `bounces` at the break of path.cpp's loop
+            zeroNow = CommitVertex(s, pool, slot, h, newFlags, finished, lZero, betaWritten, dimNow, &wantShadow, &wantMis, &wantDark);
         }
     }
     __shared__ unsigned sAppend[15];
@@ -3239,8 +3341,8 @@ __global__ void k_film_split(const float *film32, float *filmSum, float *weightS
 // here: a hit gets its value by `strategy` (mi_metadata_strategy) in the line that holds the path's L, a miss keeps L = 0
 // (F_L_ZERO), and the state word is FinishedWord's, so the next k_generate flushes the slot through the guards of
 // SamplerIntegrator::Render and the filter like any radiance (integrator.cpp:277-323; the ray weight of the perspective
-// camera is 1). isect.p is rebuilt by the routines k_shade uses -- HitInteraction with the ray of the space the hit lies in,
-// InteractionToWorld for a hit inside an instance -- so it is the point shading sees, bit for bit. `primMeta`: the ids of
+// camera is 1). isect.p is rebuilt by the routine k_shade uses -- BuildHitVertex: HitInteraction with the ray of the space the hit
+// lies in, InteractionToWorld for a hit inside an instance -- so it is the point shading sees, bit for bit. `primMeta`: the ids of
 // every primitive, parallel to DScene::prims (mi_prim_meta); the instance id of a hit reached through a
 // TransformedPrimitive is that instance's number + 1 (primitive.cpp:89).
 //
@@ -3271,30 +3373,12 @@ __global__ void __launch_bounds__(BLOCK) k_commit_metadata(DScene s, Pool pool, 
                 const float v = (float)id;   // L = Spectrum(isect.materialId) / Spectrum(isect.instanceId), metadata.cpp:71-75
                 val = make_float4(v, v, v, v);
             } else {
-                const float4 ray0 = pool.R(R_RAY0, slot), ray1 = pool.R(R_RAY1, slot), hr = pool.R(R_HIT, slot);
-                const V3 ro(ray0.x, ray0.y, ray0.z), rd(ray1.x, ray1.y, ray1.z);
-                int inst = -1;
-                V3 roS = ro, rdS = rd;   // the ray in the space the hit shape was intersected in (as in k_shade)
-                float instW2I[MOTION ? 16 : 1], instI2W[MOTION ? 16 : 1];
-                if (INST) {
-                    inst = pool.I(I_HITINST, slot);
-                    if constexpr (MOTION) {
-                        if (inst >= 0) {
-                            const float time = PathTime(s, pool, slot);
-                            InstanceW2I(s, inst, time, instW2I);
-                            InstanceI2W(s, inst, time, instI2W);
-                            const Ray ir = XfRay(instW2I, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d;
-                        }
-                    } else if (inst >= 0) { const Ray ir = XfRay(s.instances[inst].w2i, Ray(ro, rd, kInfinity)); roS = ir.o; rdS = ir.d; }
-                }
+                MovingMatrices<MOTION> mm;
+                HitVertex<INST, MOTION> hv;
                 SurfaceInteraction isect;
-                HitInteraction(s, prim, roS, rdS, hr.y, hr.z, hr.w, &isect);
-                if (INST) {
-                    if constexpr (MOTION) { if (inst >= 0) InteractionToWorld(instI2W, instW2I, &isect); }
-                    else if (inst >= 0) InteractionToWorld(s.instances[inst], &isect);
-                }
+                BuildHitVertex<true>(s, pool, slot, prim, pool.R(R_RAY0, slot), pool.R(R_RAY1, slot), true, mm, hv, &isect, nullptr);
                 if (strategy == MI_METADATA_DEPTH) {
-                    const V3 toIntersect = isect.p - ro;   // metadata.cpp:68-69
+                    const V3 toIntersect = isect.p - hv.ro;   // metadata.cpp:68-69
                     const float v = toIntersect.Length();
                     val = make_float4(v, v, v, v);
                 } else
