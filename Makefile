@@ -17,10 +17,10 @@ cli: $(PKG)/pbrt_amd
 $(PKG)/libmipt_host.so: $(HOSTSRC) $(wildcard $(PKG)/csrc/host/*.h) $(wildcard $(PKG)/csrc/host/*.inc) include/mi_pt.h include/mi_scene.h
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOSTSRC) -ldl -lz
 
-# pt_kernels.hip is compiled four times side by side (MIPT_PART: the other kernels + host code, and the k_shade instances in
-# three groups), hlbvh.hip once; `make -j` runs them together.
+# pt_kernels.hip is compiled five times side by side (MIPT_PART: the other kernels + host code, the k_shade instances in
+# three groups, and the BSDF probe), hlbvh.hip once; `make -j` runs them together.
 DEVDEPS  := $(wildcard $(PKG)/csrc/device/*.hip) $(wildcard $(PKG)/csrc/device/*.h) include/mi_pt.h
-DEVOBJ   := build/pt_part0.o build/pt_part1.o build/pt_part2.o build/pt_part3.o build/hlbvh.o
+DEVOBJ   := build/pt_part0.o build/pt_part1.o build/pt_part2.o build/pt_part3.o build/pt_part4.o build/hlbvh.o
 build/pt_part%.o: $(DEVDEPS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -DMIPT_PART=$* -c -o $@ $(PKG)/csrc/device/pt_kernels.hip

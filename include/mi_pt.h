@@ -663,6 +663,8 @@ int mi_pt_camera_rays_ex(mi_pt *pt, const int32_t *samples, uint32_t n, int32_t 
  *            -> value, lower bound, upper bound
  *   op 5: FindInterval over the array 0, 1, ..., 9 with the predicate a[i] <= x0, as Distribution1D::SampleDiscrete runs it
  *         (pbrt.h:405-418, sampling.h:91-98; tests/find_interval.cpp:8) -> the interval
+ *   op 6: x0 / y0 the two ways the spectral passes divide: DivBy(x0, MakeDivisor(y0)), DivFast(x0, y0, 1 / y0, tracker) with
+ *         a tracker reset for this divisor alone, and 1 where that tracker reports a quotient outside the fast range
  * Host pointers; needs no scene. */
 int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, const float *y, float *out);
 
@@ -705,6 +707,33 @@ int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, cons
  *           light -- queries: 6 floats (n[3], w[3]); out: MI_NSPEC floats. MI_ERR_INVALID for the delta lights. */
 #define MI_LIGHT_PROBE_SAMPLE_FLOATS (10 + MI_NSPEC)
 int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const float *queries, float *out);
+
+/* Parity tool for the BSDF code: material `material` of the scene through the BSDF routines of shading-kernel instance `instance`
+ * (an index into the table mi_pt_shade_instances reports), one query at a time. Host pointers. The frame is the canonical one
+ * (ns = ng = +z, ss = +x, ts = +y), every lobe of the material is on and nothing is overridden: what the kernel has at a
+ * material without image textures. queries: 8 floats each -- wo[3], wi[3], u[2] (world = local directions).
+ *   mode 0: BSDF::f(wo, wi, flags) and BSDF::Pdf(wo, wi, flags); u is not read.
+ *   mode 1: BSDF::Sample_f(wo, u, flags); the query's wi is not read.
+ * out: MI_BSDF_PROBE_FLOATS floats per query -- f[MI_NSPEC], pdf, wi[3] (mode 0: the query's), the sampled type (mode 0: 0); all
+ * zero where Sample_f returns a black value. `form` is the code path that forms the 31 bins:
+ *   0: the lobe list (BSDF_f / BSDF_Sample_f) summed bin by bin (EvalBin) -- the definition;
+ *   1: the same list four bins at a time (EvalQuad);
+ *   2: the straight-line form of the instances with at most two lobes of the simple kinds, with its retry where a quotient leaves
+ *      the fast range. out has MI_BSDF_PROBE_STRAIGHT_FLOATS floats per query for this form: the record, then 1 if some quad of
+ *      the query's wave (the 64 queries 64 w .. 64 w + 63) took the retry, then 1 if a quotient of this query left the range;
+ *   3: summed lobe by lobe (AccumulateF; mode 1: AccumulateSpecular / AccumulateFLocal) -- the instances with more than two
+ *      lobes or image textures.
+ * MI_ERR_INVALID for a form the instance does not compile (mi_pt_bsdf_probe_forms), a material that reads an image texture (a
+ * lobe's spectrum, the roughness, sigma or a bump map) or has more lobes than the instance holds, and an index out of range. A
+ * lobe or Fresnel kind outside the instance's mask evaluates to nothing, as in the kernel: the caller picks instances that
+ * hold the material's kinds. */
+#define MI_BSDF_PROBE_FLOATS (5 + MI_NSPEC)
+#define MI_BSDF_PROBE_STRAIGHT_FLOATS (MI_BSDF_PROBE_FLOATS + 2)
+int mi_pt_bsdf_probe(mi_pt *pt, int32_t material, int32_t instance, int32_t mode, int32_t form, int32_t flags, uint32_t n,
+                     const float *queries, float *out);
+/* The forms of mi_pt_bsdf_probe that instance `instance` compiles (bit f: form f). The probe is compiled once per lobe count and
+ * set of BSDF bits of the instances' masks; MI_ERR_INVALID for an instance that none of those covers. Touches no device. */
+int mi_pt_bsdf_probe_forms(int32_t instance, uint32_t *forms);
 
 /* Parity tool for the spatial light-selection strategy: the per-voxel Distribution1D tables mi_pt_create estimated on
  * the device (SpatialLightDistribution::ComputeDistribution, src/core/lightdistrib.cpp:232-300; the reference fills its

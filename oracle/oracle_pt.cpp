@@ -1385,6 +1385,13 @@ void oracle_bsdf(const mi_scene_desc *desc, int mat, int mode, const float *wo3,
         out[31] = pdf; out[32] = wi.x; out[33] = wi.y; out[34] = wi.z; out[35] = (float)st;
     }
 }
+// oracle_bsdf for n queries in one call: queries8[n][8] = wo, wi, u (mode 0 reads wo and wi, mode 1 wo and u) -> out36[n][36].
+void oracle_bsdf_n(const mi_scene_desc *desc, int mat, int mode, int flags, uint32_t n, const float *queries8, float *out36) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *q = queries8 + 8 * (size_t)i;
+        oracle_bsdf(desc, mat, mode, q, q + 3, q + 6, flags, out36 + 36 * (size_t)i);
+    }
+}
 // Spatial light distribution of the voxel containing p: pmf[n_lights].
 void oracle_light_pmf(const mi_scene_desc *desc, const float *p3, float *pmf) {
     LightDistribution ld(*desc);

@@ -310,6 +310,9 @@ def hip_lib():
         lib.mi_pt_shape_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_texture_probe.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_light_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        if hasattr(lib, "mi_pt_bsdf_probe"):   # (as below: a parent's library behind MIPT_HIP_LIB has none)
+            lib.mi_pt_bsdf_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+            lib.mi_pt_bsdf_probe_forms.argtypes = [C.c_int32, C.POINTER(C.c_uint32)]
         lib.mi_pt_light_distribution.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]
         lib.mi_pt_debug_path.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         lib.mi_pt_shade_instances.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -655,6 +658,31 @@ class PathIntegrator:
         out = np.zeros((q.shape[0], n_out), np.float32)
         _check(hip_lib().mi_pt_light_probe(self._h, int(light), int(mode), q.shape[0], _fptr(q), _fptr(out)), "mi_pt_light_probe")
         return out[:, 0] if n_out == 1 else out
+
+    def bsdf_probe(self, material, instance, mode, form, queries, flags=31):
+        """One material of the scene through the BSDF routines of one k_shade instance (mi_pt_bsdf_probe; `instance` indexes
+        shade_instances()). queries: [n, 8] float32 wo, wi, u. mode 0: BSDF::f and Pdf for (wo, wi); mode 1: Sample_f(wo, u).
+        form: how the 31 bins are formed -- 0 the lobe list bin by bin, 1 four bins at a time, 2 the straight-line form, 3 lobe
+        by lobe (bsdf_probe_forms(instance) says which an instance compiles). Returns [n, 36]: f[31], pdf, wi[3], the sampled
+        type; for form 2 [n, 38]: then 1 where the query's wave of 64 redid a quad, and 1 where a quotient of the query left
+        the fast range. What the library refuses is a RuntimeError with its message."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, 8)
+        out = np.zeros((q.shape[0], BSDF_PROBE_FLOATS + (2 if int(form) == 2 else 0)), np.float32)
+        _check(hip_lib().mi_pt_bsdf_probe(self._h, int(material), int(instance), int(mode), int(form), int(flags), q.shape[0], _fptr(q), _fptr(out)),
+               "mi_pt_bsdf_probe")
+        return out
+
+
+BSDF_PROBE_FLOATS = 36   # MI_BSDF_PROBE_FLOATS
+
+
+def bsdf_probe_forms(instance):
+    """The forms of PathIntegrator.bsdf_probe that k_shade instance `instance` compiles, as a tuple (mi_pt_bsdf_probe_forms; no
+    device). ValueError for an instance the probe has no instantiation for."""
+    m = C.c_uint32()
+    if hip_lib().mi_pt_bsdf_probe_forms(int(instance), C.byref(m)) != 0:
+        raise ValueError(hip_lib().mi_pt_last_error().decode())
+    return tuple(f for f in range(4) if (m.value >> f) & 1)
 
 
 def math_probe(op, x, y=None, device=0):

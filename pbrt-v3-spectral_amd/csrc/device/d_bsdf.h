@@ -743,23 +743,29 @@ DEV float4 EvalQuad(const BSDFEvalT<NL> &ev, const mi_bxdf *bx, int c, const Lob
 //  * DivBy's quotient candidate is formed for every operand without testing it; instead the largest and smallest magnitude
 //    seen in the quad are tracked as integers (two instructions per quotient) and ONE wave-uniform test per quad decides
 //    whether any lane left DivBy's fast range -- then the quad is redone by the branching code (EvalQuad / DivBy), which
-//    is the definition of the result. (An exact zero stays on the fast path: 0 * r is the quotient 0 / d.)
+//    is the definition of the result. (An exact zero stays on the fast path: 0 * r is the quotient 0 / d, and the result takes
+//    the sign of that product -- the correction step alone turns -0 / d into +0 for d > 0.)
 #define TM_SIMPLE_KINDS(tm) (!TM_FRESNEL(tm, MI_FRESNEL_CONDUCTOR) && !TM_FRESNEL(tm, MI_FRESNEL_DISNEY) && !TM_HAS(tm, MI_BXDF_FRESNEL_BLEND) && \
                              !TM_HAS(tm, MI_BXDF_DISNEY_CLEARCOAT) && !TM_HAS(tm, MI_BXDF_DISNEY_DIFFUSE) && !TM_HAS(tm, MI_BXDF_DISNEY_RETRO) && (((tm) & (TM_TEXTURED | TM_SCALED)) == 0u))
 struct DivTrack {
-    unsigned mx, mn;   // over the quotient candidates q1 != 0 formed so far: max of bits(|q1|), min of bits(|q1|) - 1
+    unsigned mx, mn;   // over the quotient candidates q1 != 0 formed so far: max of bits(|q1|), min of min(bits(|q1|), bits(2 |x|)) - 1
     DEV void Reset(bool allDivisorsFast) { mx = allDivisorsFast ? 0u : 0xffffffffu; mn = 0xffffffffu; }
-    // DivBy's `aq > 1e-30f && aq < 1e30f` for all of them (bits of 1e-30f: 0x0da24260, of 1e30f: 0x7149f2ca)
+    // DivBy's `aq > 1e-30f && aq < 1e30f && 2.f * absf(x) > 1e-30f` for all of them (bits of 1e-30f: 0x0da24260, of 1e30f: 0x7149f2ca)
     DEV bool Bad() const { return mx >= 0x7149f2cau || mn < 0x0da24260u; }
 };
+// CHECK_X = false: x is itself a quotient that went through this tracker (the second divisor of a chain) -- in range, or already reported
+template <bool CHECK_X = true>
 DEV float DivFast(float x, float d, float r, DivTrack &t) {
     const float q = x * r;
     const float rem = __builtin_fmaf(-q, d, x);
     const float q1 = __builtin_fmaf(rem, r, q);
     const unsigned u = __float_as_uint(q1) & 0x7fffffffu;
     t.mx = max(t.mx, u);
-    t.mn = min(t.mn, u - 1u);   // (u == 0: wraps to the top, leaves the minimum alone)
-    return q1;
+    if constexpr (CHECK_X) {
+        const unsigned ux = __float_as_uint(2.f * absf(x));   // (a numerator whose remainder would be subnormal: DivBy divides plainly)
+        t.mn = min(t.mn, min(u, ux) - 1u);   // (u == 0: wraps to the top, leaves the minimum alone)
+    } else t.mn = min(t.mn, u - 1u);
+    return __builtin_copysignf(q1, q);   // (q1 != 0 has q's sign; a zero takes it: -0 / d is -0 for d > 0, and q1 is +0)
 }
 // The lobe list of one evaluation in canonical form, per lane: f[bin] = sum over slots of ((R*A)*B)*C / d. A slot the lane does
 // not use has A = 0 (its term is +0: f + 0 == f), a slot without division d = r = 1 (DivBy(v, 1) == v). TM says at compile
@@ -857,7 +863,7 @@ template <bool EXACT>
 DEV float DivChain(float x, const PdfChain &ch, DivTrack &trk) {
     if constexpr (EXACT) return DivChainExact(x, ch);
     float q = DivFast(x, ch.pdf.d, ch.pdf.r, trk);
-    if (!ch.allSelOne) { const float q2 = DivFast(q, ch.sel.d, ch.sel.r, trk); q = ch.selIsOne ? q : q2; }
+    if (!ch.allSelOne) { const float q2 = DivFast<false>(q, ch.sel.d, ch.sel.r, trk); q = ch.selIsOne ? q : q2; }
     return q;
 }
 // The straight-line form of a pass (SimpleLobes, above): a quad is formed with DivFast first and, if a quotient of some

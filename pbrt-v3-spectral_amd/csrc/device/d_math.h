@@ -52,6 +52,9 @@ DEV float Log2F(float x) { const float invLog2 = 1.44269504088896338700465094007
 // rounded reciprocal this is the correctly rounded quotient except when x/d lies within
 // ~2^-23 ulp of a rounding boundary (about 2^-22 of operands, then off by one ulp);
 // operands whose reciprocal or quotient leave the normal range use the plain division.
+// That bound needs an exact remainder: it is about 2^-24 |x|, so for |x| below 2^-101 it is a
+// subnormal float (and the quotient then one ulp off as far as 3e-3 ulp from a boundary).
+// Such numerators -- 2 |x| <= 1e-30f -- use the plain division as well.
 struct Divisor {
     float d, r;
     bool fast;
@@ -70,7 +73,7 @@ DEV float DivBy(float x, const Divisor &v) {
         const float rem = __builtin_fmaf(-q, v.d, x);
         const float q1 = __builtin_fmaf(rem, v.r, q);
         const float aq = absf(q1);
-        if (aq > 1e-30f && aq < 1e30f) return q1;
+        if (aq > 1e-30f && aq < 1e30f && 2.f * absf(x) > 1e-30f) return q1;
     }
     return x / v.d;
 }

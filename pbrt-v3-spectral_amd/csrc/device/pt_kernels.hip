@@ -38,9 +38,10 @@
 
 using namespace dpt;
 
-// The library is built from this file four times in parallel (Makefile): MIPT_PART 0 holds everything but the shading
+// The library is built from this file five times in parallel (Makefile): MIPT_PART 0 holds everything but the shading
 // kernel's instances (host code, the other kernels), parts 1-3 hold a third of the k_shade instances each (they are 95 % of
-// the compile time). Without MIPT_PART (tools/isa_stats.py, tools/build_variants.sh) everything is one translation unit.
+// the compile time), part 4 the BSDF probe's kernels and their launcher (mi_pt_bsdf_probe: test-only code, kept out of the
+// parts a render runs). Without MIPT_PART (tools/isa_stats.py, tools/build_variants.sh) everything is one translation unit.
 #ifdef MIPT_PART
 #define MIPT_HAS_MAIN (MIPT_PART == 0)
 #else
@@ -3208,6 +3209,13 @@ __global__ void k_math_probe(int op, uint32_t n, const float *x, const float *y,
         const float cdf[10] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9}, func[9] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
         float pdf;
         o[0] = (float)SampleDiscrete(func, cdf, 1.f, 9, x0, &pdf);
+    } else if (op == 6) {   // x0 / y0 by DivBy and by DivFast with a tracker of its own
+        const Divisor dv = MakeDivisor(y0);
+        DivTrack trk;
+        trk.Reset(dv.fast);
+        o[0] = DivBy(x0, dv);
+        o[1] = DivFast(x0, y0, 1.f / y0, trk);
+        o[2] = trk.Bad() ? 1.f : 0.f;
     }
 }
 
@@ -3471,6 +3479,139 @@ MIPT_SHADE_LENS_INSTANCES(MIPT_SHADE_LENS_INSTANCE)
 MIPT_SHADE_MOTION_INSTANCES(MIPT_SHADE_MOTION_INSTANCE)
 #endif
 
+// ------------------------------------------------------------------ the BSDF on its own (mi_pt_bsdf_probe)
+// d_bsdf.h reads these bits of an instance's mask: the lobe types, the Fresnel kinds, TM_TEXTURED and TM_SCALED. The light,
+// sampler and instance bits never reach it, so the probe is compiled once per (NL, TM & TM_BSDF_BITS): the rows below, which
+// BsdfProbeRow() looks an instance of MIPT_SHADE_INSTANCES up in (tests/test_shade_plan.py: every instance has a row).
+constexpr unsigned TM_BSDF_BITS = 0x7fffu | (0xffu << 16) | TM_TEXTURED | TM_SCALED;
+#define MIPT_BSDF_PROBE_ROWS(X) \
+    X(2, TM_DIFFUSE) X(2, TM_PLASTIC) X(2, TM_GLASS) X(2, TM_GENERIC) X(2, TM_FULL) \
+    X(2, TM_DIFFUSE | TM_TEXTURED) X(2, TM_PLASTIC | TM_TEXTURED) \
+    X(4, TM_UBER) X(4, TM_GENERIC) X(4, TM_FULL) \
+    X(MI_MAX_BXDFS, TM_DISNEY) X(MI_MAX_BXDFS, TM_GENERIC) X(MI_MAX_BXDFS, TM_FULL)
+// The forms of instance (nl, tm) as bits (bit f: form f of mi_pt_bsdf_probe is compiled for it), 0 for an instance without a row.
+unsigned BsdfProbeForms(int nl, unsigned tm);
+// Launches the probe of instance (nl, tm) on the null stream; false: no row, or a form the instance does not compile.
+bool LaunchBsdfProbe(int nl, unsigned tm, const DScene &s, int material, int mode, int form, int flags, const float *dq, uint32_t n, float *dout);
+
+#if !defined(MIPT_PART) || MIPT_PART == 4
+// One query per lane, in the frame oracle_bsdf builds (ns = ng = +z, ss = +x, ts = +y), every lobe of the material on, no
+// override: the frame k_shade has at an untextured material. The 31 bins come out of the routines k_shade<NL, TM> calls:
+//   form 0  BSDF_f / BSDF_Sample_f<FILL> and EvalBin (the definition)
+//   form 1  the same lobe list through EvalQuad
+//   form 2  the straight-line form as the passes write it (the dark MIS pass: f alone, no pdf chain); the retry loop exists
+//           only inline in the stage routines (LightSampleTerm, BsdfSampleTerm, Continuation), so its three lines are repeated here
+//   form 3  AccumulateF (mode 0); AccumulateSpecular / AccumulateFLocal as BsdfSampleTerm chooses (mode 1), into a column
+//           of the lane's own
+// Lanes past n leave at once, so a wave holds exactly the queries 64 w .. 64 w + 63 (form 2's tests are per wave).
+template <int NL, unsigned TM>
+__global__ void __launch_bounds__(BLOCK) k_bsdf_probe(DScene s, int material, int mode, int form, int flags, const float *in, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *q = in + 8 * (size_t)i;
+    const int stride = form == 2 ? MI_BSDF_PROBE_STRAIGHT_FLOATS : MI_BSDF_PROBE_FLOATS;
+    float *o = out + (size_t)stride * i;
+    for (int k = 0; k < stride; ++k) o[k] = 0.f;
+    const mi_material *mat = &s.materials[material];
+    BSDFFrame fr;
+    fr.m = mat;
+    fr.mask = 0xffu;
+    fr.ov.u = fr.ov.v = 0.f; fr.ov.onU = fr.ov.onV = false;
+    fr.ov.sigMode = 0; fr.ov.sigA = fr.ov.sigB = 0.f;
+    fr.ov.disney = false; fr.ov.rough = 0.f;
+    fr.ns = V3(0, 0, 1); fr.ng = V3(0, 0, 1); fr.ss = Normalize(V3(1, 0, 0)); fr.ts = Cross(fr.ns, fr.ss);
+    LobeTexT<NL> lt;
+    const LobeTexT<NL> *ltp = nullptr;
+    if constexpr ((TM & TM_TEXTURED) != 0) {   // (what TexturedScattering leaves for a material without image textures)
+        lt.hasR = lt.hasS = lt.mulR = lt.mulS = 0u;
+        lt.rules = 0u; lt.lum = 0.f; lt.hasK = 0u;
+        lt.basis = s.rgbIllum; lt.textures = s.textures;
+        ltp = &lt;
+    }
+    const V3 wo(q[0], q[1], q[2]);
+    V3 wi(q[3], q[4], q[5]), wiLocal;
+    float pdf = 0.f;
+    int sampledType = 0;
+    BSDFEvalT<NL> ev;
+    ev.n = 0;
+    bool ok = true;
+    if (mode == 0) {
+        if (form != 3) BSDF_f<NL, TM>(fr, wo, wi, flags, &ev);
+        pdf = BSDF_Pdf<TM>(fr, wo, wi, flags);
+    } else {
+        wi = V3(0, 0, 0);
+        if (form != 3) ok = BSDF_Sample_f<NL, TM, true>(fr, wo, &wi, q[6], q[7], &pdf, flags, &sampledType, &ev, &wiLocal);
+        else if constexpr (ShadeAccum<NL, TM>) ok = BSDF_Sample_f<NL, TM, false>(fr, wo, &wi, q[6], q[7], &pdf, flags, &sampledType, &ev, &wiLocal);
+        if (!ok) return;   // (a black sample: the oracle's record is all zero)
+    }
+    o[31] = pdf; o[32] = wi.x; o[33] = wi.y; o[34] = wi.z; o[35] = (float)sampledType;
+    if (form == 0) {
+        for (int b = 0; b < MI_NSPEC; ++b) o[b] = EvalBin<NL, TM>(ev, mat->bxdf, b, ltp);
+    } else if (form == 1) {
+#pragma unroll 1
+        for (int c = 0; c < NQ; ++c) {
+            const float4 fq = EvalQuad<NL, TM>(ev, mat->bxdf, c, ltp);
+            for (int k = 0; k < 4; ++k) if (4 * c + k < MI_NSPEC) o[4 * c + k] = Get4(fq, k);
+        }
+    } else if (form == 2) {
+        if constexpr (ShadeSimpleSpectra<NL, TM>) {
+            const StraightPass<NL> sp = MakeStraightPass<NL, TM>(ev, mat->bxdf, MakePdfChain(MakeDivisor(1.f)));
+            bool retried = false, bad = false;
+#pragma unroll 1
+            for (int c = 0; c < NQ; ++c) {
+                DivTrack trk;
+                float4 fq = StraightQuadF<NL, TM, false>(sp, false, c, c == NQ - 1, trk);
+                bad |= trk.Bad();
+                if (!QuadHolds<false>(trk)) {   // (the passes' retry: the quad again, every quotient by DivBy)
+                    retried = true;
+                    fq = StraightQuadF<NL, TM, true>(sp, false, c, c == NQ - 1, trk);
+                }
+                for (int k = 0; k < 4; ++k) if (4 * c + k < MI_NSPEC) o[4 * c + k] = Get4(fq, k);
+            }
+            o[36] = retried ? 1.f : 0.f;
+            o[37] = bad ? 1.f : 0.f;
+        }
+    } else {
+        if constexpr (ShadeAccum<NL, TM>) {
+            float4 col[NQ];
+            auto rd = [&](int c) -> float4 { return col[c]; };
+            auto wr = [&](int c, const float4 &v) { col[c] = v; };
+            if (mode == 0) AccumulateF<NL, TM>(fr, wo, wi, flags, ltp, rd, wr);
+            else if (ev.n > 0) AccumulateSpecular<NL, TM>(ev.lobes[0], mat->bxdf, ltp, rd, wr);
+            else AccumulateFLocal<NL, TM>(fr, fr.WorldToLocal(wo), wiLocal, Dot(wi, fr.ng) * Dot(wo, fr.ng) > 0, flags, ltp, rd, wr);
+#pragma unroll 1
+            for (int c = 0; c < NQ; ++c)
+                for (int k = 0; k < 4; ++k) if (4 * c + k < MI_NSPEC) o[4 * c + k] = Get4(col[c], k);
+        }
+    }
+}
+
+struct BsdfProbeRow {
+    int nl;
+    unsigned tm, forms;
+    void (*kernel)(DScene, int, int, int, int, const float *, uint32_t, float *);
+};
+#define MIPT_BSDF_PROBE_ROW(NL_, TM_) {NL_, (TM_) & TM_BSDF_BITS, 3u | (ShadeSimpleSpectra<NL_, ((TM_) & TM_BSDF_BITS)> ? 4u : 0u) | (ShadeAccum<NL_, ((TM_) & TM_BSDF_BITS)> ? 8u : 0u), \
+                                       k_bsdf_probe<NL_, ((TM_) & TM_BSDF_BITS)>},
+static const BsdfProbeRow kBsdfProbeRows[] = {MIPT_BSDF_PROBE_ROWS(MIPT_BSDF_PROBE_ROW)};
+#undef MIPT_BSDF_PROBE_ROW
+static const BsdfProbeRow *BsdfProbeRowOf(int nl, unsigned tm) {
+    for (const BsdfProbeRow &r : kBsdfProbeRows)
+        if (r.nl == nl && r.tm == (tm & TM_BSDF_BITS)) return &r;
+    return nullptr;
+}
+unsigned BsdfProbeForms(int nl, unsigned tm) {
+    const BsdfProbeRow *r = BsdfProbeRowOf(nl, tm);
+    return r ? r->forms : 0u;
+}
+bool LaunchBsdfProbe(int nl, unsigned tm, const DScene &s, int material, int mode, int form, int flags, const float *dq, uint32_t n, float *dout) {
+    const BsdfProbeRow *r = BsdfProbeRowOf(nl, tm);
+    if (!r || form < 0 || form > 3 || !((r->forms >> form) & 1u)) return false;
+    hipLaunchKernelGGL(r->kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, s, material, mode, form, flags, dq, n, dout);
+    return true;
+}
+#endif   // MIPT_PART 4
+
 }  // namespace dptk
 using namespace dptk;
 
@@ -3592,6 +3733,7 @@ struct mi_pt {
     bool hasInstances = false;       // ... and with the TransformedPrimitive code (those carry the alpha-mask test too)
     uint32_t nQuadrics = 0;          // n_spheres + n_disks (mi_pt_shape_probe)
     std::vector<int> lightTypes;     // mi_light.type of every light (mi_pt_light_probe)
+    std::vector<int> materialLobes;  // mi_material.n_bxdfs of every material, -1 - n_bxdfs for one that reads an image texture (mi_pt_bsdf_probe)
     bool hasQuadrics = false;        // the scene has spheres or disks: the quadric lists of rays can overflow (k_resolve_overflow is launched)
     bool hasInfiniteLight = false;   // picks the kernels compiled with the environment-light code
     unsigned shadeClasses[N_SHADE_INSTANCES] = {0};   // per k_shade instance: the shading classes it runs (ShadeInstanceOf)
@@ -4415,6 +4557,11 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     pt->hasQuadrics = h.hasQuadrics;
     pt->nQuadrics = d->n_spheres + d->n_disks;
     for (uint32_t i = 0; i < d->n_lights; ++i) pt->lightTypes.push_back(d->lights[i].type);
+    for (uint32_t i = 0; i < d->n_materials; ++i) {
+        const mi_material &m = d->materials[i];
+        const bool tex = m.textured || m.bump_tex >= 0 || m.rough_tex[0] >= 0 || m.rough_tex[1] >= 0 || m.sigma_tex >= 0;
+        pt->materialLobes.push_back(tex ? -1 - m.n_bxdfs : m.n_bxdfs);
+    }
     pt->hasInfiniteLight = h.classes.hasInfiniteLight;
     memcpy(pt->shadeClasses, h.classes.shadeClasses, sizeof(pt->shadeClasses));
     pt->nTextures = d->n_textures;
@@ -5147,6 +5294,31 @@ int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const 
     });
 }
 
+int mi_pt_bsdf_probe(mi_pt *pt, int32_t material, int32_t instance, int32_t mode, int32_t form, int32_t flags, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (material < 0 || (size_t)material >= pt->materialLobes.size()) { g_err = "mi_pt_bsdf_probe: material index out of range"; return MI_ERR_INVALID; }
+    if (instance < 0 || instance >= N_SHADE_INSTANCES) { g_err = "mi_pt_bsdf_probe: instance index out of range"; return MI_ERR_INVALID; }
+    if (mode < 0 || mode > 1) { g_err = "mi_pt_bsdf_probe: mode must be 0 or 1"; return MI_ERR_INVALID; }
+    if (pt->materialLobes[material] < 0) { g_err = "mi_pt_bsdf_probe: the material reads an image texture"; return MI_ERR_INVALID; }
+    const ShadeInstance &si = kShadeInstances[instance];
+    if (pt->materialLobes[material] > si.nl) { g_err = "mi_pt_bsdf_probe: the material has more lobes than the instance holds"; return MI_ERR_INVALID; }
+    if (form < 0 || form > 3 || !((BsdfProbeForms(si.nl, si.tm) >> form) & 1u)) { g_err = "mi_pt_bsdf_probe: the instance does not compile this form"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_bsdf_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const size_t nOut = form == 2 ? MI_BSDF_PROBE_STRAIGHT_FLOATS : MI_BSDF_PROBE_FLOATS;
+    return RunProbe(pt->device, queries, (size_t)n * 8 * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
+        LaunchBsdfProbe(si.nl, si.tm, pt->scene, (int)material, (int)mode, (int)form, (int)flags, (const float *)dq, n, (float *)dout);
+    });
+}
+
+int mi_pt_bsdf_probe_forms(int32_t instance, uint32_t *forms) {
+    if (!forms) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (instance < 0 || instance >= N_SHADE_INSTANCES) { g_err = "mi_pt_bsdf_probe_forms: instance index out of range"; return MI_ERR_INVALID; }
+    *forms = BsdfProbeForms(kShadeInstances[instance].nl, kShadeInstances[instance].tm);
+    if (*forms == 0u) { g_err = "mi_pt_bsdf_probe_forms: the instance has no row in MIPT_BSDF_PROBE_ROWS"; return MI_ERR_INVALID; }
+    return MI_OK;
+}
+
 int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out) {
     if (!pt || !samples || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
     if (n > (1u << 24)) { g_err = "mi_pt_camera_rays: more than 2^24 samples"; return MI_ERR_INVALID; }
@@ -5370,7 +5542,7 @@ int mi_pt_trace(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hi
 int mi_pt_trace_timed(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits) { return TraceRays(pt, rays, 8, n, any_hit, hits); }
 
 int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, const float *y, float *out) {
-    if (!x || !y || !out || op < 0 || op > 5) { g_err = "mi_pt_math_probe: bad argument"; return MI_ERR_INVALID; }
+    if (!x || !y || !out || op < 0 || op > 6) { g_err = "mi_pt_math_probe: bad argument"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || device_ordinal < 0 || device_ordinal >= nDev) { g_err = "no HIP device available (this path has no CPU fallback)"; return MI_ERR_NO_DEVICE; }

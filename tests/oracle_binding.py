@@ -34,6 +34,7 @@ def lib():
         l.oracle_sample_dimension.restype = C.c_float
         l.oracle_tri_test.argtypes = [F, F, F]
         l.oracle_bsdf.argtypes = [D, C.c_int, C.c_int, F, F, F, C.c_int, F]
+        l.oracle_bsdf_n.argtypes = [D, C.c_int, C.c_int, C.c_int, C.c_uint32, F, F]
         l.oracle_light_pmf.argtypes = [D, F, F]
         l.oracle_light_voxel.argtypes = [D, C.POINTER(C.c_int32), F, F]
         l.oracle_light_table.argtypes = [D, C.c_int, F, F]
@@ -125,6 +126,17 @@ def light_probe(scene, light, mode, queries):
     if lib().oracle_light_probe(scene.desc_ptr, int(light), int(mode), q.shape[0], _f(q), _f(out)) != 0:
         raise ValueError("oracle_light_probe: bad light index or mode")
     return out[:, 0] if n_out == 1 else out
+
+
+def bsdf_n(scene, mat, mode, queries, flags=31):
+    """oracle_bsdf_n: oracle_bsdf for every row of queries [n, 8] (wo, wi, u) in one call -> [n, 36]: f[31], pdf, wi[3], the
+    sampled type. mode 0: BSDF::f and Pdf for (wo, wi); mode 1: Sample_f(wo, u). The layout of PathIntegrator.bsdf_probe."""
+    q = np.ascontiguousarray(queries, np.float32).reshape(-1, 8)
+    if not 0 <= int(mat) < scene.desc.n_materials:
+        raise ValueError("oracle_bsdf_n: material index out of range")
+    out = np.zeros((q.shape[0], 36), np.float32)
+    lib().oracle_bsdf_n(scene.desc_ptr, int(mat), int(mode), int(flags), q.shape[0], _f(q), _f(out))
+    return out
 
 
 def set_libm(mode):

@@ -239,6 +239,120 @@ def test_bsdf_sampling_matches_its_pdf(pt, ob, kind):
     assert stats.chi2.sf(chi2, dof) > 0.01 * 0.2  # same slack as the reference's Sidak-style correction
 
 
+# ---- the oracle's BSDF over the query sets of the device test (tests/test_bsdf_gpu.py compares the device with these records)
+@pytest.fixture(scope="module")
+def bsdf_records(pt, ob):
+    """Every material of shade_plan_scenes.PLAIN through oracle_bsdf_n on the random and edge sets: per material the lobe type
+    names, f / Pdf (mode 0) and Sample_f (mode 1) records."""
+    import bsdf_cases as bc
+    import shade_plan_scenes as sp
+    s = pt.Scene(text=sp.scene_text(list(sp.PLAIN), res=8, spp=1))
+    assert s.errors == [], s.errors
+    q = bc.all_queries()
+    out = []
+    for mi in range(s.desc.n_materials):
+        m = s.desc.materials[mi]
+        out.append(([pt.BXDF_TYPES[m.bxdf[j].type] for j in range(m.n_bxdfs)], ob.bsdf_n(s, mi, 0, q), ob.bsdf_n(s, mi, 1, q)))
+    return s, q, out
+
+
+def test_bsdf_n_is_oracle_bsdf_in_a_loop(pt, ob, bsdf_records):
+    s, q, recs = bsdf_records
+    for mi in (4, len(recs) - 1):
+        for mode in (0, 1):
+            for k in (0, 100, 2047, 2048, len(q) - 1):
+                one = _bsdf(ob, s, mi, mode, q[k, :3], q[k, 3:6], q[k, 6:8])
+                assert np.array_equal(one.view(np.uint32), recs[mi][1 + mode][k].view(np.uint32))
+    with pytest.raises(ValueError):
+        ob.bsdf_n(s, s.desc.n_materials, 0, q[:1])
+
+
+def test_bsdf_values_are_finite_and_non_negative(bsdf_records):
+    """f >= 0 in every bin; no NaN or infinity for any query with wo.z != 0; wo.z == 0 gives f = 0 and pdf = 0; pdf >= 0 --
+    but for one case that is the reference's own: FresnelBlend::Pdf (reflection.cpp:470-475) and MicrofacetReflection::Pdf
+    (reflection.cpp:419-423) divide by 4 * Dot(wo, wh) with wh = Normalize(wo + wi) and no absolute value, and where wi is -wo
+    up to a sliver -- 1 + wo.wi below 2^-20, the size of the directions' own normalisation error -- the float sign of that dot
+    product is noise. Sample_f of a grazing wo produces such pairs (six of the edge queries on the two materials with a
+    FresnelBlend lobe, pdf down to -0.43); the oracle restates those lines, so the assertion excepts exactly them."""
+    s, q, recs = bsdf_records
+    wz = q[:, 2] != 0
+    for mi, (sig, e0, e1) in enumerate(recs):
+        assert np.isfinite(e0[wz][:, :32]).all() and np.isfinite(e1[wz][:, :36]).all(), mi
+        assert (e0[:, :31] >= 0).all() and (e1[:, :31] >= 0).all(), mi
+        assert (e0[~wz][:, :32] == 0).all() and (e1[~wz][:, :32] == 0).all(), mi
+        assert (e0[:, 31] >= 0).all(), mi
+        neg = e1[:, 31] < 0
+        if neg.any():
+            assert "fresnel_blend" in sig or "microfacet_reflection" in sig, (mi, sig)
+            wo, wi = q[neg, :3].astype(np.float64), e1[neg, 32:35].astype(np.float64)
+            assert (1 + (wo * wi).sum(1) < 2.0 ** -20).all(), (mi, q[neg], e1[neg, 31:35])
+
+
+def test_sample_f_returns_f_and_pdf_of_its_direction(ob, bsdf_records):
+    """Wherever Sample_f returns a non-specular type and pdf > 0, its f is bitwise BSDF::f(wo, wi) at the returned wi, and its pdf
+    bitwise BSDF::Pdf(wo, wi) -- the latter for materials without a microfacet or FresnelBlend lobe only: the reference's
+    MicrofacetReflection::Sample_f takes the pdf from the half vector it sampled (reflection.cpp:415) where Pdf rebuilds the half
+    vector from wo + wi (reflection.cpp:419-422), MicrofacetTransmission and FresnelBlend likewise (reflection.cpp:437-447,
+    450-475), and the two round differently. The oracle does what those lines do."""
+    s, q, recs = bsdf_records
+    n_checked = 0
+    for mi, (sig, e0, e1) in enumerate(recs):
+        pick = ((e1[:, 35].astype(np.int32) & 16) == 0) & (e1[:, 31] > 0)
+        if not pick.any():
+            continue
+        q2 = q[pick].copy()
+        q2[:, 3:6] = e1[pick, 32:35]
+        again = ob.bsdf_n(s, mi, 0, q2)
+        assert np.array_equal(again[:, :31].view(np.uint32), e1[pick, :31].view(np.uint32)), (mi, sig)
+        if not any(t.startswith("microfacet") or t == "fresnel_blend" for t in sig):
+            assert np.array_equal(again[:, 31].view(np.uint32), e1[pick, 31].view(np.uint32)), (mi, sig)
+        n_checked += int(pick.sum())
+    assert n_checked > 100000
+
+
+def test_reflection_lobes_are_reciprocal(ob, bsdf_records):
+    """f(wo, wi) against f(wi, wo) for the materials whose lobes are all reflection lobes with a symmetric f (Lambertian,
+    Oren-Nayar, microfacet reflection, FresnelBlend: matte, plastic, metal, substrate, Disney's metallic lobe and their
+    mirror-free mixes), per bin relative to the larger of the two. Measured on the random set: at most 1.974e-5 (plastic with a
+    black Kd, alpha 0.1: the half vector is normalised from a sum that differs in the last place when its terms swap). The bar
+    is 4 times that, 7.9e-5, on both sets; and a bin is zero one way round only if it is the other way round."""
+    s, q, recs = bsdf_records
+    symmetric = ("lambertian_reflection", "oren_nayar", "microfacet_reflection", "fresnel_blend")
+    qs = q.copy()
+    qs[:, :3], qs[:, 3:6] = q[:, 3:6], q[:, :3]
+    worst, n_mats = 0., 0
+    for mi, (sig, e0, _) in enumerate(recs):
+        if not sig or any(t not in symmetric for t in sig):
+            continue
+        n_mats += 1
+        a, b = e0[:, :31].astype(np.float64), ob.bsdf_n(s, mi, 0, qs)[:, :31].astype(np.float64)
+        assert np.array_equal(a == 0, b == 0), (mi, sig)
+        den = np.maximum(np.abs(a), np.abs(b))
+        rel = np.where(den > 0, np.abs(a - b) / np.where(den > 0, den, 1), 0)
+        worst = max(worst, float(rel[:2048].max()))
+        assert rel.max() <= 7.9e-5, (mi, sig, float(rel.max()), q[int(rel.max(1).argmax())])
+    print("reciprocity: worst relative difference on the random set %.3e over %d materials" % (worst, n_mats))
+    assert n_mats >= 15
+
+
+def test_the_retry_operands_leave_the_fast_range_of_the_divisor(pt, ob, bsdf_records):
+    """bsdf_cases.RETRY_WO / RETRY_WI: the microfacet denominator 4 cos_o cos_i is below DivBy's 1e-18 while f is a finite
+    positive value (the oracle divides plainly), and the wave's other lanes are far from every guard."""
+    import bsdf_cases as bc
+    s, _, recs = bsdf_records
+    hit, calm = bc.retry_waves()
+    wo, wi = hit[bc.RETRY_LANE, :3], hit[bc.RETRY_LANE, 3:6]
+    assert np.float32(4) * abs(wi[2]) * abs(wo[2]) < np.float32(1e-18) and abs(wo[2]) > 0
+    assert np.array_equal(wo, np.array(bc.RETRY_WO, np.float32)) and (wo.astype(np.float64) ** 2).sum() == pytest.approx(1, abs=1e-7)
+    plastic = next(i for i, (sig, _, _) in enumerate(recs) if sig == ["lambertian_reflection", "microfacet_reflection"])
+    f = ob.bsdf_n(s, plastic, 0, hit)[:, :31]
+    assert np.isfinite(f).all() and (f > 0).all() and f[bc.RETRY_LANE].min() > 1e6
+    others = np.arange(64) != bc.RETRY_LANE
+    assert (4 * hit[others, 2] * hit[others, 5] > 1e-3).all() and (f[others] < 1e6).all() and (f[others] > 1e-6).all()
+    g = ob.bsdf_n(s, plastic, 0, calm)[:, :31]
+    assert (g[bc.RETRY_LANE] == 0).all() and np.array_equal(g[others], f[others])
+
+
 def test_spatial_light_distribution_is_a_pmf_favouring_near_lights(pt, ob):
     s = pt.Scene(text=st.material_zoo())
     assert s.desc.light_distrib.type == 2 and s.desc.n_lights == 5   # 2 area-light triangles, point, distant, spot

@@ -318,6 +318,21 @@ def test_every_instance_has_a_row_and_every_row_an_instance(pt):
     assert not missing, "k_shade instances without a row in tests/test_shade_instances_gpu.py (index, NL, TM): %s" % [(i, nl, hex(tm)) for i, nl, tm in missing]
 
 
+def test_every_instance_has_a_bsdf_probe_instantiation(pt):
+    """A new k_shade instance fails here, without a GPU, until MIPT_BSDF_PROBE_ROWS (pt_kernels.hip) has a row for its lobe
+    count and BSDF bits: tests/test_bsdf_gpu.py reaches the BSDF code of an instance through that row alone. The forms of a row
+    are those its instance's spectral passes are compiled as (ShadeSimpleSpectra, ShadeAccum)."""
+    not_simple = pt.lobe_bits("fresnel_conductor", "fresnel_disney", "fresnel_blend", "disney_clearcoat", "disney_diffuse", "disney_retro") | pt.TM_TEXTURED | pt.TM_SCALED
+    for i, (nl, tm) in enumerate(pt.shade_instances()):
+        forms = pt.bsdf_probe_forms(i)   # (ValueError: no row)
+        want = (0, 1) + ((2,) if nl <= 2 and not tm & not_simple else ()) + ((3,) if nl > 2 or tm & pt.TM_TEXTURED else ())
+        assert forms == want, (i, nl, hex(tm), forms)
+    with pytest.raises(ValueError, match="out of range"):
+        pt.bsdf_probe_forms(len(pt.shade_instances()))
+    with pytest.raises(ValueError, match="out of range"):
+        pt.bsdf_probe_forms(-1)
+
+
 @pytest.mark.parametrize("name", list(rows.ROWS))
 def test_the_rows_plans_hold(pt, assets, monkeypatch, name):
     """What each GPU row asserts from the plan before it renders, here without a device; and the contract for its scene."""

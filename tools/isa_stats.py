@@ -2,7 +2,7 @@
 instruction-fetch bound; VGPRs, LDS and the private segment set occupancy and scratch traffic).
 Usage: python tools/isa_stats.py [--part N] [--json FILE] [extra hipcc flags]
 --part N compiles one MIPT_PART of the file as the Makefile does (0: every kernel but k_shade, 1-3: the k_shade instances in
-three groups); without it the whole file is one translation unit. --json FILE also writes {function: figures}.
+three groups, 4: the BSDF probe's kernels); without it the whole file is one translation unit. --json FILE also writes {function: figures}.
 The report is about resources only: instruction classes are counted by prefix, no particular instruction is looked for."""
 import collections, json, os, re, shutil, subprocess, sys, tempfile
 
