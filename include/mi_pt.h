@@ -244,7 +244,7 @@ typedef struct mi_material {
  * thin surface's transmission lobe, whose p[7] = 0.65 eta - 0.35 (0 elsewhere). */
 #define MI_ROUGH_DISNEY 4u
 
-/* ImageTexture<RGBSpectrum, Spectrum> with UVMapping2D (src/textures/imagemap.h, src/core/texture.cpp:91-99) over a
+/* ImageTexture<RGBSpectrum, Spectrum> with UVMapping2D (or, opt-in, another TextureMapping2D: mi_tex_mapping) (src/textures/imagemap.h, src/core/texture.cpp:91-99) over a
  * MIPMap<RGBSpectrum> (src/core/mipmap.h). The pyramid is built on the host exactly as the reference builds it (y flip,
  * scale, inverse gamma, power-of-two Lanczos resampling, 2x2 box levels); the render side filters it per hit with the
  * reference's EWA / trilinear lookup from the hit's (u, v) and its screen-space derivatives. */
@@ -269,7 +269,13 @@ typedef struct mi_texture {   /* spectrum textures: RGB pyramid; float textures:
     float spec1[MI_NSPEC], spec2[MI_NSPEC]; /* checkerboard: "tex1" / "tex2" (constant spectra) */
     int32_t octaves;        /* noise textures ("fbm", "wrinkled"): "octaves", 0..32 */
     float omega;            /* noise textures ("fbm", "wrinkled"): "roughness" */
-    float w2t[16];          /* noise textures: IdentityMapping3D's WorldToTexture, row major */
+    float w2t[16];          /* noise textures and MI_TEX_CHECKERBOARD3D: IdentityMapping3D's WorldToTexture, row major; the spherical
+                             * and cylindrical mappings: their WorldToTexture (the inverse of the CTM at the Texture statement) */
+    int32_t is_float;       /* the record was declared as a "float" texture (a value), not as a "spectrum" / "color" one */
+    /* the opt-in mappings and classes (MIPT_TEXTURES=all; zero in every record made without the switch) */
+    int32_t mapping;        /* mi_tex_mapping of a class over a TextureMapping2D; MI_MAP_PLANAR keeps ds, dt in du, dv */
+    float vs[3], vt[3];     /* MI_MAP_PLANAR: "vector v1", "vector v2" */
+    float bilerp[4];        /* MI_TEX_BILERP: v00, v01, v10, v11 */
 } mi_texture;
 /* MI_TEX_CHECKERBOARD: Checkerboard2DTexture<Spectrum> over UVMapping2D (src/textures/checkerboard.h:47-86): the value is
  * (1 - a) * spec1 + a * spec2 with a = 0 / 1 inside a check and the box-filtered area fraction across an edge. */
@@ -277,8 +283,27 @@ typedef struct mi_texture {   /* spectrum textures: RGB pyramid; float textures:
  * src/core/texture.cpp:157-251), evaluated at the hit point with its world-space footprint dpdx / dpdy. No pyramid: mipmap is -1.
  * A float one yields the value times post_scale, a spectrum one Spectrum(value). Not legal as a mesh's alpha_tex / shadow_alpha_tex.
  * (spec1 / spec2 of such a record are ignored: the device copy carries 0 and 1 there, the compact form Spectrum(value) is expanded from.) */
-typedef enum mi_tex_type { MI_TEX_IMAGEMAP = 0, MI_TEX_CHECKERBOARD = 1, MI_TEX_FBM = 2, MI_TEX_WRINKLED = 3, MI_TEX_WINDY = 4 } mi_tex_type;
+/* MI_TEX_DOTS / MI_TEX_UV / MI_TEX_BILERP / MI_TEX_CHECKERBOARD3D (the front end makes them only under MIPT_TEXTURES=all):
+ *   DOTS (src/textures/dots.h:59-78), float and spectrum: spec1 where the point lies outside the cell's dot, spec2 inside it
+ *     (a float record keeps its two operands in spec1[0] / spec2[0]). The reference hands the parameter "inside" to the
+ *     constructor's outsideDot (dots.cpp:62-66, 91-95 against dots.h:53-55), so spec1 is "inside" and spec2 is "outside".
+ *   UV (uv.h:54-59), spectrum only: FromRGB({s - floor(s), t - floor(t), 0}).
+ *   BILERP (bilerp.h:56-62), float only: bilerp[] bilinear in (s, t).
+ *   CHECKERBOARD3D (checkerboard.h:118-128), float and spectrum: spec1 / spec2 by the parity of floor(x) + floor(y) + floor(z)
+ *     of w2t(p); point sampled. MI_TEX_CHECKERBOARD may now be a float record too: (1 - a) * spec1[0] + a * spec2[0].
+ * A float record's value is multiplied by post_scale. None of them is legal as a mesh's alpha_tex / shadow_alpha_tex, and an
+ * image texture is only under MI_MAP_UV: the traversal kernels hold neither the mappings nor these classes. */
+typedef enum mi_tex_type { MI_TEX_IMAGEMAP = 0, MI_TEX_CHECKERBOARD = 1, MI_TEX_FBM = 2, MI_TEX_WRINKLED = 3, MI_TEX_WINDY = 4,
+                           MI_TEX_DOTS = 5, MI_TEX_UV = 6, MI_TEX_BILERP = 7, MI_TEX_CHECKERBOARD3D = 8 } mi_tex_type;
 #define MI_TEX_IS_NOISE(type) ((type) >= MI_TEX_FBM && (type) <= MI_TEX_WINDY)
+/* TextureMapping2D::Map (src/core/texture.cpp:91-155) of imagemap, checkerboard, dots, uv and bilerp records */
+typedef enum mi_tex_mapping { MI_MAP_UV = 0, MI_MAP_SPHERICAL = 1, MI_MAP_CYLINDRICAL = 2, MI_MAP_PLANAR = 3 } mi_tex_mapping;
+#define MI_TEX_HAS_MAPPING2D(type) ((type) == MI_TEX_IMAGEMAP || (type) == MI_TEX_CHECKERBOARD || ((type) >= MI_TEX_DOTS && (type) <= MI_TEX_BILERP))
+/* "this record needs the hit point": a 3-D class, or a 2-D one under another mapping than uv */
+#define MI_TEX_NEEDS_POINT(t) (MI_TEX_IS_NOISE((t).type) || (t).type == MI_TEX_CHECKERBOARD3D || (MI_TEX_HAS_MAPPING2D((t).type) && (t).mapping != MI_MAP_UV))
+/* a record only the general texture-evaluating k_shade instances can evaluate: it needs the point or is one of the opt-in classes
+ * (a float checkerboard among them) */
+#define MI_TEX_IS_GENERAL(t) (MI_TEX_NEEDS_POINT(t) || (t).type >= MI_TEX_DOTS || ((t).type == MI_TEX_CHECKERBOARD && (t).is_float))
 #define MI_NOISE_MAX_OCTAVES 32
 
 /* ---- lights */
@@ -678,6 +703,16 @@ int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *querie
  * float per query, the value times post_scale (no material clamp). MI_ERR_INVALID for any other texture type
  * (mi_pt_texture_lookup answers for image textures). Host pointers. */
 int mi_pt_texture_probe(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *out);
+
+/* Parity tool for every texture record, the opt-in mappings and classes among them: texture `tex` at n interactions, through
+ * the device functions k_shade calls. queries: MI_TEXTURE_EVAL_QUERY_FLOATS floats each -- p[3], dpdx[3], dpdy[3], u, v, dudx,
+ * dvdx, dudy, dvdy. n <= 2^24. Host pointers.
+ *   mode 0: TextureMapping2D::Map -> 6 floats per query: s, t, dsdx, dtdx, dsdy, dtdy. MI_ERR_INVALID for a record without a 2-D
+ *           mapping (the noise textures, MI_TEX_CHECKERBOARD3D).
+ *   mode 1: Texture::Evaluate -> MI_NSPEC floats per query. A spectrum record gives its bins, formed as k_shade forms them (the
+ *           material's Clamp() included); a float record (is_float) gives its value times post_scale in bin 0 and 0 elsewhere. */
+#define MI_TEXTURE_EVAL_QUERY_FLOATS 15
+int mi_pt_texture_eval_probe(mi_pt *pt, int32_t tex, int32_t mode, uint32_t n, const float *queries, float *out);
 
 /* Parity tool for the quadrics (ABI v14): quadric `quadric` of the scene (the index space of mi_prim.shape: spheres, then
  * disks) on its own, through the device functions the traversal, shading and light-sampling code call. Host pointers.

@@ -61,6 +61,8 @@ void mi_scene_free(mi_scene *s);
 const char *mi_scene_last_error(void);
 /* The permutation table behind the noise textures' Noise() (MI_TEX_FBM / WRINKLED / WINDY), both halves; needs no scene. */
 void mi_noise_perm(int32_t out[512]);
+/* sizeof(mi_texture) of this build: a binding that mirrors the record checks its own layout against it. */
+uint32_t mi_texture_struct_size(void);
 
 /* The host BVH builders on raw bounds, as the front end runs them on a scene's primitives. prim_bounds: n x {min xyz, max xyz}
  * float32; split_method: one of MI_BVH_SPLIT_*; nodes_out: room for nodes_capacity nodes (2 n always suffices); ordered_out:

@@ -90,10 +90,13 @@ class Texture(C.Structure):
     _fields_ = [("mipmap", C.c_int32), ("filter", C.c_int32), ("max_aniso", C.c_float),
                 ("su", C.c_float), ("sv", C.c_float), ("du", C.c_float), ("dv", C.c_float), ("post_scale", C.c_float),
                 ("type", C.c_int32), ("aa_none", C.c_int32), ("spec1", C.c_float * NSPEC), ("spec2", C.c_float * NSPEC),
-                ("octaves", C.c_int32), ("omega", C.c_float), ("w2t", C.c_float * 16)]
+                ("octaves", C.c_int32), ("omega", C.c_float), ("w2t", C.c_float * 16),
+                # the opt-in mappings and classes (MIPT_TEXTURES=all)
+                ("is_float", C.c_int32), ("mapping", C.c_int32), ("vs", C.c_float * 3), ("vt", C.c_float * 3), ("bilerp", C.c_float * 4)]
 
 
-TEX_IMAGEMAP, TEX_CHECKERBOARD, TEX_FBM, TEX_WRINKLED, TEX_WINDY = range(5)   # mi_tex_type
+TEX_IMAGEMAP, TEX_CHECKERBOARD, TEX_FBM, TEX_WRINKLED, TEX_WINDY, TEX_DOTS, TEX_UV, TEX_BILERP, TEX_CHECKERBOARD3D = range(9)   # mi_tex_type
+MAP_UV, MAP_SPHERICAL, MAP_CYLINDRICAL, MAP_PLANAR = range(4)   # mi_tex_mapping
 
 
 class Light(C.Structure):
@@ -259,6 +262,8 @@ def host_lib():
         lib.mi_scene_last_error.restype = C.c_char_p
         lib.mi_noise_perm.argtypes = [C.POINTER(C.c_int32)]
         lib.mi_noise_perm.restype = None
+        lib.mi_texture_struct_size.argtypes = []
+        lib.mi_texture_struct_size.restype = C.c_uint32
         lib.mi_film_write_dat.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float]
         lib.mi_film_read_dat.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float),
                                          C.c_uint64]
@@ -310,6 +315,8 @@ def hip_lib():
         lib.mi_pt_shape_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_texture_probe.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.mi_pt_light_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        if hasattr(lib, "mi_pt_texture_eval_probe"):   # (as below)
+            lib.mi_pt_texture_eval_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         if hasattr(lib, "mi_pt_bsdf_probe"):   # (as below: a parent's library behind MIPT_HIP_LIB has none)
             lib.mi_pt_bsdf_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
             lib.mi_pt_bsdf_probe_forms.argtypes = [C.c_int32, C.POINTER(C.c_uint32)]
@@ -629,6 +636,15 @@ class PathIntegrator:
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, 9)
         out = np.zeros(q.shape[0], np.float32)
         _check(hip_lib().mi_pt_texture_probe(self._h, int(tex), q.shape[0], _fptr(q), _fptr(out)), "mi_pt_texture_probe")
+        return out
+
+    def texture_eval_probe(self, tex, mode, queries):
+        """Any texture record at given interactions on the device (mi_pt_texture_eval_probe): queries [n, 15] = (p, dpdx, dpdy,
+        u, v, dudx, dvdx, dudy, dvdy). mode 0 -> [n, 6] (s, t, dsdx, dtdx, dsdy, dtdy) of the record's 2-D mapping; mode 1 ->
+        [n, NSPEC], a spectrum texture's bins or a float texture's value times post_scale in bin 0."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, 15)
+        out = np.zeros((q.shape[0], 6 if int(mode) == 0 else NSPEC), np.float32)
+        _check(hip_lib().mi_pt_texture_eval_probe(self._h, int(tex), int(mode), q.shape[0], _fptr(q), _fptr(out)), "mi_pt_texture_eval_probe")
         return out
 
     def shape_probe(self, quadric, mode, queries):

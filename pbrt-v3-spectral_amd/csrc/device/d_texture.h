@@ -1,6 +1,7 @@
 // d_texture.h -- image textures at a path vertex (ABI v5: mi_texture / mi_mipmap / mi_lobe_tex).
 //   SurfaceInteraction::ComputeDifferentials          src/core/interaction.cpp:99-143
-//   UVMapping2D::Map                                  src/core/texture.cpp:91-99
+//   UVMapping2D / SphericalMapping2D / CylindricalMapping2D / PlanarMapping2D::Map   src/core/texture.cpp:91-155
+//   DotsTexture, UVTexture, BilerpTexture, Checkerboard3DTexture::Evaluate           src/textures/{dots,uv,bilerp,checkerboard}.h
 //   MIPMap::Lookup (trilinear, EWA), triangle, Texel  src/core/mipmap.h:213-385
 //   convertOut + SampledSpectrum::FromRGB (Illuminant, its default) src/textures/imagemap.h:113-117, src/core/spectrum.cpp:98-180
 // The pyramid is the host's (the reference's own construction); only the per-hit lookup runs here. A texture value
@@ -305,16 +306,118 @@ DEV bool DiskTexCoords(const mi_disk &k, const V3 &ro, const V3 &rd, float *u, f
     return true;
 }
 
+// TextureMapping2D::Map(si, &dstdx, &dstdy): st and its screen-space differentials
+struct TexCoord2D {
+    float s, t, dsdx, dtdx, dsdy, dtdy;
+};
+// SphericalMapping2D::sphere (texture.cpp:123-127; SphericalTheta / SphericalPhi, geometry.h:1483-1490) and
+// CylindricalMapping2D::cylinder (texture.h:93-96) of world point p
+DEV void SphereST(const float *w2t, const V3 &p, float *s, float *t) {
+    const V3 vec = Normalize(XfPoint(w2t, p));
+    const float theta = acosF(clampf(vec.z, -1, 1));
+    const float ph = atan2F(vec.y, vec.x);
+    const float phi = (ph < 0) ? (ph + 2 * kPi) : ph;
+    *s = theta * kInvPi;
+    *t = phi * 0.15915494309189533577f;
+}
+DEV void CylinderST(const float *w2t, const V3 &p, float *s, float *t) {
+    const V3 vec = Normalize(XfPoint(w2t, p));
+    *s = (kPi + atan2F(vec.y, vec.x)) * 0.15915494309189533577f;
+    *t = vec.z;
+}
+// "Handle sphere mapping discontinuity for coordinate differentials" (texture.cpp:111-119, 136-145): component [1] only
+DEV float WrapDifferential(float d) {
+    if (d > .5f) return 1 - d;
+    if (d < -.5f) return -(d + 1);
+    return d;
+}
+// {Spherical,Cylindrical,Planar}Mapping2D::Map (texture.cpp:101-155): the mappings that read the hit point and its footprint.
+// A call, like the noise textures' value: only the general k_shade instances and the probe hold it.
+static DEV_CALL TexCoord2D MapPoint2D(const mi_texture *t, float px, float py, float pz, float dxx, float dxy, float dxz, float dyx, float dyy, float dyz) {
+    const V3 p(px, py, pz), dpdx(dxx, dxy, dxz), dpdy(dyx, dyy, dyz);
+    TexCoord2D c;
+    if (t->mapping == MI_MAP_PLANAR) {
+        const V3 vs(t->vs[0], t->vs[1], t->vs[2]), vt(t->vt[0], t->vt[1], t->vt[2]);
+        c.dsdx = Dot(dpdx, vs); c.dtdx = Dot(dpdx, vt);
+        c.dsdy = Dot(dpdy, vs); c.dtdy = Dot(dpdy, vt);
+        c.s = t->du + Dot(p, vs); c.t = t->dv + Dot(p, vt);
+        return c;
+    }
+    const bool sphere = t->mapping == MI_MAP_SPHERICAL;
+    const float delta = sphere ? .1f : .01f;
+    float sx, tx, sy, ty;
+    if (sphere) {
+        SphereST(t->w2t, p, &c.s, &c.t);
+        SphereST(t->w2t, p + delta * dpdx, &sx, &tx);
+        SphereST(t->w2t, p + delta * dpdy, &sy, &ty);
+    } else {
+        CylinderST(t->w2t, p, &c.s, &c.t);
+        CylinderST(t->w2t, p + delta * dpdx, &sx, &tx);
+        CylinderST(t->w2t, p + delta * dpdy, &sy, &ty);
+    }
+    const float inv = 1.f / delta;   // Vector2f / Float multiplies by the reciprocal (geometry.h:121-125)
+    c.dsdx = (sx - c.s) * inv; c.dtdx = WrapDifferential((tx - c.t) * inv);
+    c.dsdy = (sy - c.s) * inv; c.dtdy = WrapDifferential((ty - c.t) * inv);
+    return c;
+}
+// The record's TextureMapping2D at the hit: UVMapping2D (texture.cpp:93-99), or (NOISE: the instance holds that code) one of
+// the mappings over the point
+template <bool NOISE>
+DEV TexCoord2D MapTexture2D(const mi_texture &t, float u, float v, const V3 &p, const TexDifferentials &td) {
+    if constexpr (NOISE) {
+        if (t.mapping != MI_MAP_UV) return MapPoint2D(&t, p.x, p.y, p.z, td.dpdx.x, td.dpdx.y, td.dpdx.z, td.dpdy.x, td.dpdy.y, td.dpdy.z);
+    }
+    TexCoord2D c;
+    c.s = t.su * u + t.du; c.t = t.sv * v + t.dv;
+    c.dsdx = t.su * td.dudx; c.dtdx = t.sv * td.dvdx;
+    c.dsdy = t.su * td.dudy; c.dtdy = t.sv * td.dvdy;
+    return c;
+}
+
+// DotsTexture::Evaluate (dots.h:59-78): 1 where st lies inside the dot of its cell, 0 outside (Noise(x, y) is Noise(x, y, .5f))
+static DEV_CALL float DotsInside(float s, float t) {
+    const int sCell = (int)floorf(s + .5f), tCell = (int)floorf(t + .5f);
+    if (Noise(sCell + .5f, tCell + .5f, .5f) > 0) {
+        const float radius = .35f;
+        const float maxShift = 0.5f - radius;
+        const float sCenter = sCell + maxShift * Noise(sCell + 1.5f, tCell + 2.8f, .5f);
+        const float tCenter = tCell + maxShift * Noise(sCell + 4.5f, tCell + 9.8f, .5f);
+        const float ds = s - sCenter, dt = t - tCenter;
+        if (ds * ds + dt * dt < radius * radius) return 1.f;
+    }
+    return 0.f;
+}
+// Checkerboard3DTexture::Evaluate over IdentityMapping3D (checkerboard.h:118-128): 0 for tex1, 1 for tex2
+DEV float Checkerboard3DWeight(const mi_texture &t, const V3 &p) {
+    const V3 P = XfPoint(t.w2t, p);
+    return (((int)floorf(P.x) + (int)floorf(P.y) + (int)floorf(P.z)) % 2 == 0) ? 0.f : 1.f;
+}
+DEV float CheckerboardArea2(float st0, float st1, float dx0, float dx1, float dy0, float dy1, bool aaNone);
+// Texture<Float>::Evaluate(si) of the float classes beside the image and noise textures (without post_scale): "checkerboard"
+// in two and three dimensions, "dots", "bilerp"
+DEV float FloatClassValue(const mi_texture &t, float u, float v, const V3 &p, const TexDifferentials &td) {
+    if (t.type == MI_TEX_CHECKERBOARD3D) return Checkerboard3DWeight(t, p) != 0.f ? t.spec2[0] : t.spec1[0];
+    const TexCoord2D c = MapTexture2D<true>(t, u, v, p, td);
+    if (t.type == MI_TEX_DOTS) return DotsInside(c.s, c.t) != 0.f ? t.spec2[0] : t.spec1[0];
+    if (t.type == MI_TEX_BILERP)   // bilerp.h:59-60
+        return (1 - c.s) * (1 - c.t) * t.bilerp[0] + (1 - c.s) * (c.t) * t.bilerp[1] + (c.s) * (1 - c.t) * t.bilerp[2] + (c.s) * (c.t) * t.bilerp[3];
+    const float a = CheckerboardArea2(c.s, c.t, c.dsdx, c.dtdx, c.dsdy, c.dtdy, t.aa_none != 0);   // MI_TEX_CHECKERBOARD
+    return (1 - a) * t.spec1[0] + a * t.spec2[0];
+}
+
 // Texture<Float>::Evaluate(si) of float texture `tex`: an image texture at (u, v), or (NOISE: the instance holds that code)
-// a noise texture at the world point p, both with the footprint in td
+// a noise texture at the world point p, an image texture under another mapping, or one of the other classes, all with the
+// footprint in td
 template <bool NOISE>
 DEV float EvalFloatImageTexture(const DScene &s, int tex, float u, float v, const V3 &p, const TexDifferentials &td) {
     const mi_texture &t = s.textures[tex];
     if constexpr (NOISE) {
         if (MI_TEX_IS_NOISE(t.type)) return NoiseTextureValue(t, p, td.dpdx, td.dpdy) * t.post_scale;
+        if (t.type != MI_TEX_IMAGEMAP) return FloatClassValue(t, u, v, p, td) * t.post_scale;
     }
     const mi_mipmap &m = s.mipmaps[t.mipmap];
-    return MipLookup(s, m, t.su * u + t.du, t.sv * v + t.dv, t.su * td.dudx, t.sv * td.dvdx, t.su * td.dudy, t.sv * td.dvdy, t.filter, t.max_aniso).r * t.post_scale;
+    const TexCoord2D c = MapTexture2D<NOISE>(t, u, v, p, td);
+    return MipLookup(s, m, c.s, c.t, c.dsdx, c.dtdx, c.dsdy, c.dtdy, t.filter, t.max_aniso).r * t.post_scale;
 }
 // Material::Bump (material.cpp:47-84): updates the interaction's shading normal and shading dpdu (what the BSDF frame is
 // built from). The shifted evaluations move uv and (for a 3-D displacement, NOISE) p; the footprint stays the interaction's.
@@ -360,16 +463,46 @@ DEV IllumRGB EvalImageTexture(const DScene &s, int tex, float u, float v, const 
             q.w0 = NoiseTextureValue(t, p, td.dpdx, td.dpdy);
             return q;
         }
+        if (t.type == MI_TEX_CHECKERBOARD3D) {   // spec1 or spec2: the same form
+            IllumRGB q;
+            q.i1 = -1; q.i2 = tex; q.w1 = q.w2 = 0.f;
+            q.w0 = Checkerboard3DWeight(t, p);
+            return q;
+        }
+        if (t.type == MI_TEX_DOTS || t.type == MI_TEX_UV) {
+            const TexCoord2D c = MapTexture2D<true>(t, u, v, p, td);
+            if (t.type == MI_TEX_UV) {   // uv.h:57-59
+                const float rgb[3] = {c.s - floorf(c.s), c.t - floorf(c.t), 0.f};
+                return MakeIllumRGB(rgb);
+            }
+            IllumRGB q;
+            q.i1 = -1; q.i2 = tex; q.w1 = q.w2 = 0.f;
+            q.w0 = DotsInside(c.s, c.t);
+            return q;
+        }
     }
+    if constexpr (!NOISE) {   // UVMapping2D written out: through MapTexture2D<false> the textured matte instance came out with two more spilled registers
+        if (t.type == MI_TEX_CHECKERBOARD) {
+            IllumRGB q;
+            q.i1 = -1; q.i2 = tex; q.w1 = q.w2 = 0.f;
+            q.w0 = CheckerboardArea2(t.su * u + t.du, t.sv * v + t.dv, t.su * td.dudx, t.sv * td.dvdx, t.su * td.dudy, t.sv * td.dvdy, t.aa_none != 0);
+            return q;
+        }
+        const mi_mipmap &m = s.mipmaps[t.mipmap];
+        const RGB3 mem = MipLookup(s, m, t.su * u + t.du, t.sv * v + t.dv, t.su * td.dudx, t.sv * td.dvdx, t.su * td.dudy, t.sv * td.dvdy,
+                                   t.filter, t.max_aniso);
+        const float rgb[3] = {mem.r, mem.g, mem.b};
+        return MakeIllumRGB(rgb);
+    }
+    const TexCoord2D c = MapTexture2D<true>(t, u, v, p, td);
     if (t.type == MI_TEX_CHECKERBOARD) {
         IllumRGB q;
         q.i1 = -1; q.i2 = tex; q.w1 = q.w2 = 0.f;
-        q.w0 = CheckerboardArea2(t.su * u + t.du, t.sv * v + t.dv, t.su * td.dudx, t.sv * td.dvdx, t.su * td.dudy, t.sv * td.dvdy, t.aa_none != 0);
+        q.w0 = CheckerboardArea2(c.s, c.t, c.dsdx, c.dtdx, c.dsdy, c.dtdy, t.aa_none != 0);
         return q;
     }
     const mi_mipmap &m = s.mipmaps[t.mipmap];
-    const RGB3 mem = MipLookup(s, m, t.su * u + t.du, t.sv * v + t.dv, t.su * td.dudx, t.sv * td.dvdx, t.su * td.dudy, t.sv * td.dvdy,
-                               t.filter, t.max_aniso);
+    const RGB3 mem = MipLookup(s, m, c.s, c.t, c.dsdx, c.dtdx, c.dsdy, c.dtdy, t.filter, t.max_aniso);
     const float rgb[3] = {mem.r, mem.g, mem.b};
     return MakeIllumRGB(rgb);
 }

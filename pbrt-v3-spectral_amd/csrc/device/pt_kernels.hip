@@ -3111,6 +3111,35 @@ __global__ void k_texture_probe(DScene s, int tex, const float *q, uint32_t n, f
     out[i] = EvalFloatImageTexture<true>(s, tex, 0.f, 0.f, V3(r[0], r[1], r[2]), td);
 }
 
+// mi_pt_texture_eval_probe: any texture record at an interaction given in full, through the routines k_shade evaluates it with.
+// mode 0: the record's 2-D mapping; mode 1: its value -- a spectrum texture's bins (TexBin over the compact form, as the lobes
+// read it), a float texture's value times post_scale in bin 0
+__global__ void k_texture_eval_probe(DScene s, int tex, int mode, const float *q, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = q + MI_TEXTURE_EVAL_QUERY_FLOATS * (size_t)i;
+    const V3 p(r[0], r[1], r[2]);
+    TexDifferentials td;
+    td.dpdx = V3(r[3], r[4], r[5]); td.dpdy = V3(r[6], r[7], r[8]);
+    const float u = r[9], v = r[10];
+    td.dudx = r[11]; td.dvdx = r[12]; td.dudy = r[13]; td.dvdy = r[14];
+    const mi_texture &t = s.textures[tex];
+    if (mode == 0) {
+        const TexCoord2D c = MapTexture2D<true>(t, u, v, p, td);
+        float *o = out + 6 * (size_t)i;
+        o[0] = c.s; o[1] = c.t; o[2] = c.dsdx; o[3] = c.dtdx; o[4] = c.dsdy; o[5] = c.dtdy;
+        return;
+    }
+    float *o = out + MI_NSPEC * (size_t)i;
+    if (t.is_float) {
+        o[0] = EvalFloatImageTexture<true>(s, tex, u, v, p, td);
+        for (int b = 1; b < MI_NSPEC; ++b) o[b] = 0.f;
+        return;
+    }
+    const IllumRGB value = EvalImageTexture<true>(s, tex, u, v, p, td);
+    for (int b = 0; b < MI_NSPEC; ++b) o[b] = TexBin(s.rgbIllum, s.textures, value, b);
+}
+
 // ------------------------------------------------------------------ one quadric on its own (mi_pt_shape_probe)
 __global__ void k_shape_probe(DScene s, int q, int mode, const float *in, uint32_t n, float *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3680,7 +3709,8 @@ constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstanc
 // and plastic instances.
 // `disks`: the scene has disks, whose code only the instances compiled for every lobe, light and sampler hold (TM_HOLDS_DISKS):
 // no class of such a scene fits an instance compiled for a subset, so those are the code they were before disks.
-// `noise`: the scene has noise textures, whose code only the general texture-evaluating instances hold (TM_HOLDS_NOISE): every
+// `noise`: the scene has noise textures, or textures of the other classes and mappings that need the hit point or came with them
+// (MI_TEX_IS_GENERAL), whose code only the general texture-evaluating instances hold (TM_HOLDS_NOISE): every
 // textured class of such a scene goes there, and the textured matte and plastic instances are the code they were before.
 // `projection`: the scene has a projection light, whose code the same instances hold as the disks' (TM_HOLDS_PROJECTION): any
 // class can draw that light, so every class of such a scene goes where a scene with disks sends it.
@@ -3908,6 +3938,11 @@ struct SceneViewGuard {
 // -----------------------------------------------------------------------------
 // mi_pt_create, step 1: every refusal that depends on the description alone, before anything touches the device
 // -----------------------------------------------------------------------------
+// a float record of the classes beside the image and noise textures (EvalFloatImageTexture in the general instances): what a
+// roughness, sigma or bump parameter may name besides those two
+static bool FloatClassRecord(const mi_texture &t) {
+    return t.is_float && (t.type == MI_TEX_CHECKERBOARD || t.type == MI_TEX_DOTS || t.type == MI_TEX_BILERP || t.type == MI_TEX_CHECKERBOARD3D);
+}
 int CheckSceneDesc(const mi_scene_desc *d) {
     if (d->n_prims && !d->n_nodes) { g_err = "primitives without BVH nodes"; return MI_ERR_INVALID; }
     for (uint32_t i = 0; i < d->n_nodes; ++i) {
@@ -3942,16 +3977,17 @@ int CheckSceneDesc(const mi_scene_desc *d) {
         const mi_material &m = d->materials[i];
         if (m.n_bxdfs < 0 || m.n_bxdfs > MI_MAX_BXDFS) { g_err = "material lobe count out of range"; return MI_ERR_INVALID; }
         if (m.bump_tex >= (int)d->n_textures || m.bump_tex < -1) { g_err = "mi_material.bump_tex out of range"; return MI_ERR_INVALID; }
+        if (m.bump_tex >= 0 && d->textures[m.bump_tex].type == MI_TEX_UV) { g_err = "mi_material.bump_tex names a MI_TEX_UV record, which has no float value"; return MI_ERR_INVALID; }
         for (int k = 0; k < 2; ++k) {   // roughness maps: float image textures with a pyramid behind them, or noise textures (EvalFloatImageTexture)
             const int rt = m.rough_tex[k];
             if (rt < -1 || rt >= (int)d->n_textures) { g_err = "mi_material.rough_tex out of range"; return MI_ERR_INVALID; }
-            if (rt >= 0 && !MI_TEX_IS_NOISE(d->textures[rt].type) && (d->textures[rt].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[rt].mipmap >= d->n_mipmaps)) {
+            if (rt >= 0 && !MI_TEX_IS_NOISE(d->textures[rt].type) && !FloatClassRecord(d->textures[rt]) && (d->textures[rt].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[rt].mipmap >= d->n_mipmaps)) {
                 g_err = "mi_material.rough_tex must name an image texture with a mipmap or a noise texture"; return MI_ERR_INVALID;
             }
         }
         // (ABI v10) the sigma map, the lobe rules and the glass switch: what the shading kernels index with them
         if (m.sigma_tex < -1 || m.sigma_tex >= (int)d->n_textures ||
-            (m.sigma_tex >= 0 && !MI_TEX_IS_NOISE(d->textures[m.sigma_tex].type) &&
+            (m.sigma_tex >= 0 && !MI_TEX_IS_NOISE(d->textures[m.sigma_tex].type) && !FloatClassRecord(d->textures[m.sigma_tex]) &&
              (d->textures[m.sigma_tex].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[m.sigma_tex].mipmap >= d->n_mipmaps))) {
             g_err = "mi_material.sigma_tex must be -1 or name an image texture with a mipmap or a noise texture"; return MI_ERR_INVALID;
         }
@@ -3959,6 +3995,8 @@ int CheckSceneDesc(const mi_scene_desc *d) {
             const mi_lobe_tex &lt = m.tex[k];
             if (lt.rule < MI_LOBE_IF_R || lt.rule > MI_LOBE_METAL) { g_err = "mi_lobe_tex.rule is not a mi_lobe_rule"; return MI_ERR_INVALID; }
             if (lt.tex_R < -1 || lt.tex_R >= (int)d->n_textures || lt.tex_S < -1 || lt.tex_S >= (int)d->n_textures) { g_err = "mi_lobe_tex texture index out of range"; return MI_ERR_INVALID; }
+            for (int tx : {lt.tex_R, lt.tex_S})   // (it has no pyramid either: the spectrum evaluation would look one up)
+                if (tx >= 0 && d->textures[tx].type == MI_TEX_BILERP) { g_err = "mi_lobe_tex names a MI_TEX_BILERP record, which has no spectrum value"; return MI_ERR_INVALID; }
             if (lt.rule >= MI_LOBE_DISNEY_SHEEN && lt.rule <= MI_LOBE_DISNEY_STRANS && lt.tex_R < 0) { g_err = "a \"disney\" lobe rule needs the colour's texture in tex_R"; return MI_ERR_INVALID; }
         }
         if ((m.rough_flags & MI_ROUGH_GLASS) && (m.n_bxdfs < 1 || m.bxdf[0].type != MI_BXDF_FRESNEL_SPECULAR)) {
@@ -3967,15 +4005,20 @@ int CheckSceneDesc(const mi_scene_desc *d) {
     }
     for (uint32_t i = 0; i < d->n_textures; ++i) {
         const mi_texture &t = d->textures[i];
-        if (t.type < MI_TEX_IMAGEMAP || t.type > MI_TEX_WINDY) { g_err = "mi_texture.type is not a mi_tex_type"; return MI_ERR_INVALID; }
+        if (t.type < MI_TEX_IMAGEMAP || t.type > MI_TEX_CHECKERBOARD3D) { g_err = "mi_texture.type is not a mi_tex_type"; return MI_ERR_INVALID; }
+        if (t.mapping < MI_MAP_UV || t.mapping > MI_MAP_PLANAR) { g_err = "mi_texture.mapping is not a mi_tex_mapping"; return MI_ERR_INVALID; }
+        if (t.mapping != MI_MAP_UV && !MI_TEX_HAS_MAPPING2D(t.type)) { g_err = "mi_texture.mapping set on a record without a 2-D mapping"; return MI_ERR_INVALID; }
+        if ((t.type == MI_TEX_UV && t.is_float) || (t.type == MI_TEX_BILERP && !t.is_float)) { g_err = "MI_TEX_UV is a spectrum record and MI_TEX_BILERP a float one"; return MI_ERR_INVALID; }
         if (t.type == MI_TEX_IMAGEMAP && (uint32_t)t.mipmap >= d->n_mipmaps) { g_err = "mi_texture.mipmap out of range"; return MI_ERR_INVALID; }
         // (the octave loops run per lane: bounded here as the front end bounds them)
         if (MI_TEX_IS_NOISE(t.type) && (t.octaves < 0 || t.octaves > MI_NOISE_MAX_OCTAVES)) { g_err = "mi_texture.octaves outside 0..32"; return MI_ERR_INVALID; }
     }
-    // the traversal kernels hold no noise code: a mask is an image texture
+    // the traversal kernels hold no noise code, no other class and no mapping but UVMapping2D: a mask is an image texture under it
     for (uint32_t i = 0; i < d->n_meshes; ++i)
-        for (int a : {d->meshes[i].alpha_tex, d->meshes[i].shadow_alpha_tex})
+        for (int a : {d->meshes[i].alpha_tex, d->meshes[i].shadow_alpha_tex}) {
             if (a >= 0 && d->textures[a].type != MI_TEX_IMAGEMAP) { g_err = "mi_mesh alpha textures must be image textures"; return MI_ERR_INVALID; }
+            if (a >= 0 && d->textures[a].mapping != MI_MAP_UV) { g_err = "mi_mesh alpha textures must be image textures under the uv mapping"; return MI_ERR_INVALID; }
+        }
     for (uint32_t i = 0; i < d->n_mipmaps; ++i) {
         const mi_mipmap &m = d->mipmaps[i];
         if (m.n_levels < 1 || m.n_levels > MI_MAX_MIP_LEVELS || !m.texels || m.width < 1 || m.height < 1) { g_err = "malformed mi_mipmap"; return MI_ERR_INVALID; }
@@ -4258,8 +4301,10 @@ int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, Sh
     int (&classLobes)[MAX_CLASSES] = sc.classLobes;
     unsigned (&classTypes)[MAX_CLASSES] = sc.classTypes;
     std::vector<std::vector<int>> signatures;
+    // (`noise`: some texture needs the hit point or is one of the classes beside image, 2-D spectrum checkerboard and noise --
+    // the code the TM_HOLDS_NOISE instances alone hold)
     bool noise = false, projection = false;
-    for (uint32_t i = 0; i < d->n_textures; ++i) noise |= MI_TEX_IS_NOISE(d->textures[i].type);
+    for (uint32_t i = 0; i < d->n_textures; ++i) noise |= MI_TEX_IS_GENERAL(d->textures[i]);
     for (uint32_t i = 0; i < d->n_lights; ++i) projection |= d->lights[i].type == MI_LIGHT_PROJECTION;
     for (uint32_t i = 0; i < d->n_materials; ++i) {
         const mi_material &m = d->materials[i];
@@ -5262,6 +5307,19 @@ int mi_pt_texture_probe(mi_pt *pt, int32_t tex, uint32_t n, const float *queries
     if (n == 0) return MI_OK;
     return RunProbe(pt->device, queries, (size_t)n * 9 * sizeof(float), out, (size_t)n * sizeof(float), [&](void *dq, void *dout) {
         hipLaunchKernelGGL(k_texture_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)tex, (float *)dq, n, (float *)dout);
+    });
+}
+
+int mi_pt_texture_eval_probe(mi_pt *pt, int32_t tex, int32_t mode, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
+    if (mode < 0 || mode > 1) { g_err = "mi_pt_texture_eval_probe: mode must be 0 or 1"; return MI_ERR_INVALID; }
+    if (mode == 0 && !MI_TEX_HAS_MAPPING2D(pt->textureTypes[tex])) { g_err = "mi_pt_texture_eval_probe: the record has no 2-D mapping"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_texture_eval_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const size_t nOut = mode == 0 ? 6 : MI_NSPEC;
+    return RunProbe(pt->device, queries, (size_t)n * MI_TEXTURE_EVAL_QUERY_FLOATS * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_texture_eval_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)tex, (int)mode, (float *)dq, n, (float *)dout);
     });
 }
 

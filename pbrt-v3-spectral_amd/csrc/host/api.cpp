@@ -137,6 +137,13 @@ int AlphaTexture(Api &a, const ParamSet &params, const char *param) {
                 a.Err("Noise texture \"" + texName + "\" as \"" + param + "\" of a shape is outside the hot-path scope; the shape is left unmasked");
                 return -1;
             }
+            // (MIPT_TEXTURES=all) the traversal kernels hold neither the 2-D mappings nor the classes beside the image texture: a mask
+            // of any of them would put that code there, whether or not it needs the hit point
+            if (MI_TEX_IS_GENERAL(a.scene->textures[it->second])) {
+                a.Err("Texture \"" + texName + "\" as \"" + param + "\" of a shape is outside the hot-path scope (only a \"uv\"-mapped image texture masks a shape: "
+                      "the traversal kernels hold no other mapping or class); the shape is left unmasked");
+                return -1;
+            }
             return it->second;
         }
         auto c = a.gs.textures.floatTex.find(texName);
@@ -147,6 +154,7 @@ int AlphaTexture(Api &a, const ParamSet &params, const char *param) {
     mi_texture t{};
     t.mipmap = ConstantFloatMipMap(a.scene, 0.f);
     t.filter = MI_TEX_TRILINEAR; t.max_aniso = 8.f; t.su = t.sv = 1.f; t.post_scale = 1.f;
+    t.is_float = 1;
     a.scene->textures.push_back(t);
     return (int)a.scene->textures.size() - 1;
 }
@@ -493,6 +501,107 @@ void BindImageTexture(Api &a, const std::string &name, bool isFloat, const mi_te
     else a.gs.textures.spectrumTex.erase(name);
     (isFloat ? a.gs.textures.floatImageTex : a.gs.textures.imageTex)[name] = (int)a.scene->textures.size();
     a.scene->textures.push_back(t);
+    a.scene->textures.back().is_float = isFloat ? 1 : 0;
+}
+
+// The TextureMapping2D of a Create*Texture (the block every 2-D class repeats, e.g. checkerboard.cpp:50-71) into `t`: "uv" with
+// uscale / vscale / udelta / vdelta; with MIPT_TEXTURES=all also "spherical" and "cylindrical" (WorldToTexture = the inverse of
+// the CTM here) and "planar" (v1, v2, udelta, vdelta; no transform). false: the mapping is refused (a reported error).
+bool Mapping2D(Api &a, const std::string &name, const ParamSet &ps, mi_texture *t) {
+    const std::string mapping = ps.FindOneString("mapping", "uv");
+    if (mapping != "uv" && !a.allTextures) {
+        a.Err("Texture \"" + name + "\": 2D texture mapping \"" + mapping + "\" is outside the hot-path scope (\"uv\" only)");
+        return false;
+    }
+    t->mapping = MI_MAP_UV;
+    t->su = t->sv = 1.f; t->du = t->dv = 0.f;
+    if (mapping == "uv") {
+        t->su = ps.FindOneFloat("uscale", 1.f); t->sv = ps.FindOneFloat("vscale", 1.f);
+        t->du = ps.FindOneFloat("udelta", 0.f); t->dv = ps.FindOneFloat("vdelta", 0.f);
+    } else if (mapping == "spherical" || mapping == "cylindrical") {
+        t->mapping = mapping == "spherical" ? MI_MAP_SPHERICAL : MI_MAP_CYLINDRICAL;
+        std::memcpy(t->w2t, a.ctm.mInv.m, sizeof(t->w2t));
+    } else if (mapping == "planar") {
+        t->mapping = MI_MAP_PLANAR;
+        const Vec3 v1 = ps.FindOneVector3("v1", Vec3(1, 0, 0)), v2 = ps.FindOneVector3("v2", Vec3(0, 1, 0));
+        t->vs[0] = v1.x; t->vs[1] = v1.y; t->vs[2] = v1.z;
+        t->vt[0] = v2.x; t->vt[1] = v2.y; t->vt[2] = v2.z;
+        t->du = ps.FindOneFloat("udelta", 0.f); t->dv = ps.FindOneFloat("vdelta", 0.f);
+    } else
+        a.Err("2D texture mapping \"" + mapping + "\" unknown");   // then `map.reset(new UVMapping2D)`: the default one
+    return true;
+}
+
+// (MIPT_TEXTURES=all) the two operands of a "dots" or "checkerboard": constants only, into spec1 / spec2 (a float record's in [0])
+bool TwoConstantOperands(Api &a, const std::string &name, const char *cls, bool isFloat, const TextureParams &tp, const char *n1, float d1,
+                         const char *n2, float d2, mi_texture *t) {
+    if (isFloat) {
+        if (tp.GetFloatImageTexture(n1) >= 0 || tp.GetFloatImageTexture(n2) >= 0) {
+            a.Err("Texture \"" + name + "\": a \"" + cls + "\" of image textures is outside the hot-path scope (constant " + n1 + " / " + n2 + ")");
+            return false;
+        }
+        t->spec1[0] = tp.GetFloat(n1, d1); t->spec2[0] = tp.GetFloat(n2, d2);
+        return true;
+    }
+    const SpectrumParam p1 = tp.GetSpectrumParam(n1, Spectrum(d1)), p2 = tp.GetSpectrumParam(n2, Spectrum(d2));
+    if (p1.tex >= 0 || p2.tex >= 0) {
+        a.Err("Texture \"" + name + "\": a \"" + cls + "\" of image textures is outside the hot-path scope (constant " + n1 + " / " + n2 + ")");
+        return false;
+    }
+    CopySpectrum(p1.s, t->spec1);
+    CopySpectrum(p2.s, t->spec2);
+    return true;
+}
+
+// (MIPT_TEXTURES=all) Create{Dots,UV,Bilerp}{Float,Spectrum}Texture, src/textures/{dots,uv,bilerp}.cpp
+bool MappedClassTexture(Api &a, const std::string &name, const std::string &texname, bool isFloat, const ParamSet &ps, const TextureParams &tp) {
+    if (texname == "bilerp" && !isFloat) {
+        a.Err("Texture \"" + name + "\": a spectrum \"bilerp\" is a sum of four spectra, which the two-spectrum form of a texture value on this path cannot carry; "
+              "outside the hot-path scope (float \"bilerp\" only)");
+        return false;
+    }
+    if (texname == "uv" && isFloat) return false;   // CreateUVFloatTexture returns nullptr (uv.cpp:41-44): no texture, no message
+    mi_texture t{};
+    t.mipmap = -1;
+    t.post_scale = 1.f; t.max_aniso = 8.f;
+    if (!Mapping2D(a, name, ps, &t)) return false;
+    if (texname == "dots") {
+        t.type = MI_TEX_DOTS;
+        // DotsTexture(mapping, outsideDot, insideDot) is handed "inside" first (dots.cpp:62-66, 91-95 against dots.h:53-55):
+        // spec1, the value outside the dots, is the parameter "inside"
+        if (!TwoConstantOperands(a, name, "dots", isFloat, tp, "inside", 1.f, "outside", 0.f, &t)) return false;
+    } else if (texname == "uv")
+        t.type = MI_TEX_UV;
+    else {
+        t.type = MI_TEX_BILERP;
+        t.bilerp[0] = ps.FindOneFloat("v00", 0.f); t.bilerp[1] = ps.FindOneFloat("v01", 1.f);
+        t.bilerp[2] = ps.FindOneFloat("v10", 0.f); t.bilerp[3] = ps.FindOneFloat("v11", 1.f);
+    }
+    BindImageTexture(a, name, isFloat, t);
+    return true;
+}
+
+// (MIPT_TEXTURES=all) CreateCheckerboard{Float,Spectrum}Texture, checkerboard.cpp:40-152, in full: float and spectrum, 2-D over
+// any mapping, 3-D over IdentityMapping3D
+bool CheckerboardTextureAll(Api &a, const std::string &name, bool isFloat, const ParamSet &ps, const TextureParams &tp) {
+    const int dim = ps.FindOneInt("dimension", 2);
+    if (dim != 2 && dim != 3) { a.Err(std::to_string(dim) + " dimensional checkerboard texture not supported"); return false; }
+    mi_texture t{};
+    t.mipmap = -1;
+    t.su = t.sv = 1.f; t.post_scale = 1.f; t.max_aniso = 8.f;
+    if (!TwoConstantOperands(a, name, "checkerboard", isFloat, tp, "tex1", 1.f, "tex2", 0.f, &t)) return false;
+    if (dim == 2) {
+        t.type = MI_TEX_CHECKERBOARD;
+        if (!Mapping2D(a, name, ps, &t)) return false;
+        const std::string aa = ps.FindOneString("aamode", "closedform");
+        if (aa == "none") t.aa_none = 1;
+        else if (aa != "closedform") a.Warn("Antialiasing mode \"" + aa + "\" not understood by Checkerboard2DTexture; using \"closedform\"");
+    } else {
+        t.type = MI_TEX_CHECKERBOARD3D;
+        std::memcpy(t.w2t, a.ctm.mInv.m, sizeof(t.w2t));   // IdentityMapping3D(tex2world), as NoiseTexture
+    }
+    BindImageTexture(a, name, isFloat, t);
+    return true;
 }
 
 // Create{FBm,Wrinkled,Windy}{Float,Spectrum}Texture, src/textures/{fbm,wrinkled,windy}.cpp
@@ -521,6 +630,7 @@ bool NoiseTexture(Api &a, const std::string &name, const std::string &texname, b
 
 // CreateCheckerboardSpectrumTexture, checkerboard.cpp:99-150
 bool CheckerboardTexture(Api &a, const std::string &name, bool isFloat, const ParamSet &ps, const TextureParams &tp) {
+    if (a.allTextures) return CheckerboardTextureAll(a, name, isFloat, ps, tp);
     if (isFloat) { a.Err("Texture \"" + name + "\": float \"checkerboard\" textures are outside the hot-path scope"); return false; }
     if (ps.FindOneInt("dimension", 2) != 2) { a.Err("Texture \"" + name + "\": 3D \"checkerboard\" textures are outside the hot-path scope"); return false; }
     const std::string mapping = ps.FindOneString("mapping", "uv");
@@ -544,11 +654,8 @@ bool CheckerboardTexture(Api &a, const std::string &name, bool isFloat, const Pa
 
 // CreateImage{Float,Spectrum}Texture, imagemap.cpp:152-197
 bool ImageMapTexture(Api &a, const std::string &name, bool isFloat, const ParamSet &ps) {
-    const std::string mapping = ps.FindOneString("mapping", "uv");
-    if (mapping != "uv") { a.Err("Texture \"" + name + "\": 2D texture mapping \"" + mapping + "\" is outside the hot-path scope (\"uv\" only)"); return false; }
     mi_texture t{};
-    t.su = ps.FindOneFloat("uscale", 1.f); t.sv = ps.FindOneFloat("vscale", 1.f);
-    t.du = ps.FindOneFloat("udelta", 0.f); t.dv = ps.FindOneFloat("vdelta", 0.f);
+    if (!Mapping2D(a, name, ps, &t)) return false;
     t.post_scale = 1.f;
     t.max_aniso = ps.FindOneFloat("maxanisotropy", 8.f);
     if (!(t.max_aniso <= 64.f)) {   // an EWA footprint is up to 2 x maxanisotropy texels long: keep the per-lane loop bounded
@@ -614,6 +721,7 @@ void MixTexture(Api &a, const std::string &name, bool isFloat, const TexturePara
 Api::Api(HostScene *s, const LoadOverrides &o) : scene(s), ov(o) {
     if (const char *e = getenv("MIPT_INSTANCES")) expandInstances = std::string(e) == "expand";
     if (const char *e = getenv("MIPT_OBJECT_MOTION")) objectMotion = std::string(e) == "1";
+    if (const char *e = getenv("MIPT_TEXTURES")) allTextures = std::string(e) == "all";
     // default material: matte with default params (GraphicsState ctor, api.cpp:214-222)
     gs.currentMaterial = NewMaterialInstance("matte", ParamSet());
 }
@@ -744,7 +852,18 @@ void Api::Texture(const std::string &name, const std::string &type, const std::s
     // Apart from the image and noise classes every texture on this path evaluates to a constant, so "scale" and "mix" of such
     // textures fold into constants with the reference's arithmetic (src/textures/scale.h:56-58, mix.h:57-61, scale.cpp, mix.cpp).
     const bool isNoise = texname == "fbm" || texname == "wrinkled" || texname == "windy";
-    if (texname != "constant" && texname != "scale" && texname != "mix" && texname != "imagemap" && texname != "checkerboard" && !isNoise) {
+    // MIPT_TEXTURES=all: "dots", "uv" and "bilerp" besides; "marble" and "ptex" stay errors, with their reasons
+    const bool isMapped = allTextures && (texname == "dots" || texname == "uv" || texname == "bilerp");
+    if (allTextures && texname == "marble") {
+        Err("Texture class \"marble\" is outside the hot-path scope: its spline mixes FromRGB of colours that need three basis spectra plus white, "
+            "more than the two-spectrum form of a texture value on this path carries");
+        return;
+    }
+    if (allTextures && texname == "ptex") {
+        Err("Texture class \"ptex\" is outside the hot-path scope: it reads per-face texture files through the Ptex library, which this path does not hold");
+        return;
+    }
+    if (texname != "constant" && texname != "scale" && texname != "mix" && texname != "imagemap" && texname != "checkerboard" && !isNoise && !isMapped) {
         Err("Texture class \"" + texname + "\" is outside the hot-path scope (\"constant\", \"scale\", \"mix\", \"imagemap\", \"checkerboard\", \"fbm\", \"wrinkled\", \"windy\")");
         return;
     }
@@ -755,6 +874,7 @@ void Api::Texture(const std::string &name, const std::string &type, const std::s
     WarnIfAnimated("Texture");   // api.cpp:1231, 1249
     bool made = true;
     if (isNoise) made = NoiseTexture(*this, name, texname, isFloat, ps);
+    else if (isMapped) made = MappedClassTexture(*this, name, texname, isFloat, ps, tp);
     else if (texname == "checkerboard") made = CheckerboardTexture(*this, name, isFloat, ps, tp);
     else if (texname == "imagemap") made = ImageMapTexture(*this, name, isFloat, ps);
     else if (texname == "constant") ConstantTexture(*this, name, isFloat, tp);

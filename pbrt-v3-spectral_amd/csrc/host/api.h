@@ -78,6 +78,7 @@ struct Api {
     struct InstanceRec { std::string object; Transform i2w; uint32_t instanceId = 0; bool moving = false; Transform i2wEnd; };
     std::vector<InstanceRec> instanceRecs;
     bool objectMotion = false;   // MIPT_OBJECT_MOTION=1: shapes and instances under an animated CTM become moving primitives
+    bool allTextures = false;    // MIPT_TEXTURES=all: the 2-D mappings beside "uv" and the classes "dots", "uv", "bilerp", float and 3-D "checkerboard"
     int nMovingShapes = 0;
     std::vector<std::string> instanceNames;   // one per ObjectInstance call that created something, in file order
     bool expandInstances = false;

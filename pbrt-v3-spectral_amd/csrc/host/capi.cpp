@@ -136,6 +136,8 @@ void mi_scene_free(mi_scene *s) {
 
 const char *mi_scene_last_error(void) { return g_err.c_str(); }
 
+uint32_t mi_texture_struct_size(void) { return (uint32_t)sizeof(mi_texture); }
+
 void mi_noise_perm(int32_t out[512]) {
     static const unsigned char perm[512] = {
 #include "noise_perm.inc"

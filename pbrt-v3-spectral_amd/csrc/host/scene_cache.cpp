@@ -2,7 +2,7 @@
 // each parse the same .pbrt text and build the same BVH: rank 0 loads and saves, the others read the arrays back.
 // (The reference is one process: its pbrtWorldEnd() builds the scene once, src/core/api.cpp:1617-1737.)
 // Layout: magic, ABI version, sizeof checks, the POD part of mi_scene_desc (pointers are rebuilt by
-// HostScene::Finalize), then every owning array as {uint64 count, bytes}. Host-endian, same-build only: a cache is a
+// HostScene::Finalize), then every owning array as {uint64 count, bytes}, then sizeof(mi_texture). Host-endian, same-build only: a cache is a
 // hand-over between processes of one job, not an interchange format.
 #include <algorithm>
 #include <cstdio>
@@ -101,6 +101,8 @@ bool SaveSceneCache(const HostScene &scene, const std::string &path, std::string
     for (const HostMipMap &m : scene.mipStore) {
         o.Str(m.key); o.Pod(m.width); o.Pod(m.height); o.Pod(m.wrap); o.Vec(m.texels); o.Vec(m.levelOffset);
     }
+    // mi_texture grew (texture mappings and classes) under an unchanged ABI number, magic and header: its size closes the file
+    o.Pod<uint32_t>((uint32_t)sizeof(mi_texture));
     const bool ok = o.ok && fclose(f) == 0;
     if (!ok) { *err = "short write to " + tmp; remove(tmp.c_str()); return false; }
     if (rename(tmp.c_str(), path.c_str()) != 0) { *err = "cannot rename " + tmp; return false; }   // readers never see half a file
@@ -192,6 +194,9 @@ HostScene *LoadSceneCache(const std::string &path, std::string *err) {
         }
     }
     if (!consistent) { *err = "scene cache \"" + path + "\" is truncated or inconsistent"; return nullptr; }
+    uint32_t sTex = 0;   // (a file of the build before ends without it; with textures in it, it has failed the checks above already)
+    in.Pod(sTex);
+    if (!in.ok || sTex != sizeof(mi_texture)) { *err = "\"" + path + "\" is not a scene cache of this build"; return nullptr; }
     s->Finalize();
     return s.release();
 }
