@@ -610,6 +610,19 @@ struct BSDFEvalT {
     int n;  // number of contributing lobes
     LobeEval lobes[NL];
 };
+// ev->lobes[ev->n++] = le. A store through a run-time index keeps the whole list in private memory, and every later read of
+// it is a scratch load. A list of two is filled through its slots by name instead: slot 0 takes the first lobe, slot 1
+// whatever comes last (what it holds while n < 2 is never read: every reader stops at n). Same lobes in the same slots.
+template <int NL>
+DEV void AppendLobe(BSDFEvalT<NL> *ev, const LobeEval &le) {
+    if constexpr (NL == 2) {
+        if (ev->n == 0) ev->lobes[0] = le;
+        ev->lobes[1] = le;
+        ev->n += 1;
+    } else {
+        ev->lobes[ev->n++] = le;
+    }
+}
 
 // BSDF::f(woW, wiW, flags): fills the lobe list (reflection.cpp:670-683).
 template <int NL, unsigned TM>
@@ -626,7 +639,7 @@ DEV void BSDF_f(const BSDFFrame &fr, const V3 &woW, const V3 &wiW, int flags, BS
             if (MatchesFlags(b, flags) &&
                 ((reflect && (b.flags & MI_BSDF_REFLECTION)) || (!reflect && (b.flags & MI_BSDF_TRANSMISSION)))) {
                 LobeEval le = LobeF<TM>(b, i, wo, wi, fr.ov);
-                if ((le.kind & 0xff) != LK_NONE) ev->lobes[ev->n++] = le;
+                if ((le.kind & 0xff) != LK_NONE) AppendLobe<NL>(ev, le);
             }
         }
     }
@@ -1111,7 +1124,7 @@ DEV bool BSDF_Sample_f(const BSDFFrame &fr, const V3 &woWorld, V3 *wiWorld, floa
                 if (MatchesFlags(bb, type) &&
                     ((reflect && (bb.flags & MI_BSDF_REFLECTION)) || (!reflect && (bb.flags & MI_BSDF_TRANSMISSION)))) {
                     LobeEval le = LobeF<TM>(bb, i, wo, wi, fr.ov);
-                    if ((le.kind & 0xff) != LK_NONE) ev->lobes[ev->n++] = le;
+                    if ((le.kind & 0xff) != LK_NONE) AppendLobe<NL>(ev, le);
                 }
             }
         }

@@ -141,22 +141,24 @@ struct TriRay {
     int kz;
     float Sx, Sy, Sz;
 };
+DEV V3 PermuteZ(const V3 &v, int kz) {  // (v[kx], v[ky], v[kz]) with kx = kz+1, ky = kz+2 (mod 3)
+    // written as scalar selects so that it compiles to v_cndmask instead of branches. Selects of VALUES: `c ? v.y : v.z` is an
+    // lvalue, one load through a selected address, and an object read through computed addresses stays in private memory
+    // with the struct around it (a Ray, for its direction). The unary plus makes every operand a prvalue.
+    const float vx = v.x, vy = v.y, vz = v.z;
+    const bool k0 = kz == 0, k1 = kz == 1;
+    const float x = k0 ? +vy : (k1 ? +vz : +vx);
+    const float y = k0 ? +vz : (k1 ? +vx : +vy);
+    const float z = k0 ? +vx : (k1 ? +vy : +vz);
+    return V3(x, y, z);
+}
 DEV TriRay MakeTriRay(const V3 &rd) {
     TriRay tr;
     tr.kz = MaxDimension(Abs(rd));
-    int kx = tr.kz + 1; if (kx == 3) kx = 0;
-    int ky = kx + 1; if (ky == 3) ky = 0;
-    V3 d = V3(rd[kx], rd[ky], rd[tr.kz]);
+    // (selects, not rd[kx]: a V3 indexed at run time is stored to private memory and read back through computed addresses)
+    V3 d = PermuteZ(rd, tr.kz);
     tr.Sx = -d.x / d.z; tr.Sy = -d.y / d.z; tr.Sz = 1.f / d.z;
     return tr;
-}
-DEV V3 PermuteZ(const V3 &v, int kz) {  // (v[kx], v[ky], v[kz]) with kx = kz+1, ky = kz+2 (mod 3)
-    // written as scalar selects so that it compiles to v_cndmask instead of branches
-    const bool k0 = kz == 0, k1 = kz == 1;
-    const float x = k0 ? v.y : (k1 ? v.z : v.x);
-    const float y = k0 ? v.z : (k1 ? v.x : v.y);
-    const float z = k0 ? v.x : (k1 ? v.y : v.z);
-    return V3(x, y, z);
 }
 // (detOut / tScaledOut: the two quantities of the only tMax-dependent line of the test, for callers that re-apply it with a
 // smaller tMax -- the cooperative leaf test of k_trav)
@@ -666,8 +668,10 @@ DEV void InstanceI2W(const DScene &s, int k, float time, float *m) {
 // phiMax >= 2 pi AS FLOATS, so that `phi > phiMax` cannot hold for any phi that atan2 + 2 pi can produce -- passes the clipping
 // tests of sphere.cpp:91-110 whatever the hit point is, so the point, its re-projection (a square root and a division) and
 // phi (atan2) are not formed: a third of the function.
+// (out of line: the ray comes by value, in registers -- by reference the caller's ray, and the struct that holds it, would
+// have to live in private memory for the sake of this call, on every vertex and not only those that meet a sphere)
 template <bool WANT_POINT>
-__device__ __attribute__((noinline)) bool SphereRoots(const mi_sphere &s, const V3 &ro, const V3 &rd, float tMaxIn, V3 *rayObjD, V3 *pHitOut, float *phiOut, float *tOut) {
+__device__ __attribute__((noinline)) bool SphereRoots(const mi_sphere &s, const V3 ro, const V3 rd, float tMaxIn, V3 *rayObjD, V3 *pHitOut, float *phiOut, float *tOut) {
     V3 oErr, dErr;
     V3 o = XfPointErr(s.w2o, ro, &oErr);
     V3 d = XfVectorErr(s.w2o, rd, &dErr);

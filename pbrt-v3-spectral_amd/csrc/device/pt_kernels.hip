@@ -38,10 +38,10 @@
 
 using namespace dpt;
 
-// The library is built from this file five times in parallel (Makefile): MIPT_PART 0 holds everything but the shading
-// kernel's instances (host code, the other kernels), parts 1-3 hold a third of the k_shade instances each (they are 95 % of
-// the compile time), part 4 the BSDF probe's kernels and their launcher (mi_pt_bsdf_probe: test-only code, kept out of the
-// parts a render runs). Without MIPT_PART (tools/isa_stats.py, tools/build_variants.sh) everything is one translation unit.
+// The library is built from this file six times in parallel (Makefile): MIPT_PART 0 holds everything but the shading
+// kernel's instances (host code, the other kernels), parts 1-3 and 5 hold the k_shade instances (95 % of the compile
+// time; MIPT_SHADE_INSTANCES says which), part 4 the BSDF probe's kernels and their launcher (mi_pt_bsdf_probe: test-only code, kept out of the
+// parts a render runs). Without MIPT_PART (tools/isa_stats.py without --part) everything is one translation unit.
 #ifdef MIPT_PART
 #define MIPT_HAS_MAIN (MIPT_PART == 0)
 #else
@@ -3447,42 +3447,44 @@ __global__ void __launch_bounds__(BLOCK) k_commit_metadata(DScene s, Pool pool, 
 #endif   // MIPT_HAS_MAIN
 
 // Every k_shade instance, in launch order (LaunchShade): X(part, NL, TM). The part is the MIPT_PART that compiles the
-// instance (three groups of about equal compile time); without MIPT_PART the kernel table instantiates them all.
+// instance; without MIPT_PART the kernel table instantiates them all. The parts also carry the device compile flags (Makefile,
+// HIPFLAGS_part<N>): 1 (the matte and plastic instances) and 2 (the other instances without image textures) are built without
+// SLP packing, 3 and 5 (every instance that reads image textures, TM_TEXTURED) at plain -O3 -- DESIGN section 4, round 8.
 // A new instance needs a row in tests/test_shade_instances_gpu.py (the suite fails without a GPU until it has one).
 constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_TEXTURED;
 #define MIPT_SHADE_INSTANCES(X) \
     X(1, 2, TM_DIFFUSE | TM_LIGHTS_ALL) X(1, 2, TM_DIFFUSE | TM_LIGHTS_NO_ENV) \
     X(1, 2, TM_DIFFUSE | TM_LIGHTS_ALL | TM_SAMPLERS) X(1, 2, TM_DIFFUSE | TM_LIGHTS_NO_ENV | TM_SAMPLERS) \
-    X(2, 2, TM_PLASTIC | TM_LIGHTS_ALL) X(2, 2, TM_PLASTIC | TM_LIGHTS_NO_ENV) \
-    X(2, 2, TM_PLASTIC | TM_LIGHTS_ALL | TM_SAMPLERS) X(2, 2, TM_PLASTIC | TM_LIGHTS_NO_ENV | TM_SAMPLERS) \
-    X(1, 2, TM_GENERIC) \
-    X(3, 2, TM_GLASS | TM_LIGHTS_ALL | TM_SAMPLERS) \
-    X(3, 4, TM_UBER | TM_LIGHTS_ALL | TM_SAMPLERS) \
-    X(3, MI_MAX_BXDFS, TM_DISNEY | TM_LIGHTS_ALL | TM_SAMPLERS) \
-    X(1, 4, TM_GENERIC) \
+    X(1, 2, TM_PLASTIC | TM_LIGHTS_ALL) X(1, 2, TM_PLASTIC | TM_LIGHTS_NO_ENV) \
+    X(1, 2, TM_PLASTIC | TM_LIGHTS_ALL | TM_SAMPLERS) X(1, 2, TM_PLASTIC | TM_LIGHTS_NO_ENV | TM_SAMPLERS) \
+    X(2, 2, TM_GENERIC) \
+    X(2, 2, TM_GLASS | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(2, 4, TM_UBER | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(2, MI_MAX_BXDFS, TM_DISNEY | TM_LIGHTS_ALL | TM_SAMPLERS) \
+    X(2, 4, TM_GENERIC) \
     X(3, 4, TM_FULL) \
-    X(3, MI_MAX_BXDFS, TM_GENERIC) \
+    X(2, MI_MAX_BXDFS, TM_GENERIC) \
     X(3, 2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) \
     X(3, 2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) \
-    X(2, 2, TM_FULL) \
-    X(2, MI_MAX_BXDFS, TM_FULL) \
-    X(2, 2, TM_ALL) \
-    X(1, MI_MAX_BXDFS, TM_ALL)
+    X(3, 2, TM_FULL) \
+    X(3, MI_MAX_BXDFS, TM_FULL) \
+    X(5, 2, TM_ALL) \
+    X(5, MI_MAX_BXDFS, TM_ALL)
 // The LENS = true twins of the instances above that read image textures (TM_TEXTURED): not part of the plan's table, a launch
 // takes the twin where the scene has a realistic camera in front of textures (LaunchShade).
 #define MIPT_SHADE_LENS_INSTANCES(X) \
     X(3, 4, TM_FULL) \
     X(3, 2, TM_DIFFUSE | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) \
     X(3, 2, TM_PLASTIC | TM_TEXTURED | TM_LIGHTS_ALL | TM_SAMPLERS) \
-    X(2, 2, TM_FULL) \
-    X(2, MI_MAX_BXDFS, TM_FULL) \
-    X(2, 2, TM_ALL) \
-    X(1, MI_MAX_BXDFS, TM_ALL)
+    X(3, 2, TM_FULL) \
+    X(3, MI_MAX_BXDFS, TM_FULL) \
+    X(5, 2, TM_ALL) \
+    X(5, MI_MAX_BXDFS, TM_ALL)
 // The MOTION = true twins of the instances that hold the instance code (TM_INSTANCES), each with its LENS twin: a launch takes
 // them where the scene has moving instances (LaunchShade). Not part of the plan's table either.
 #define MIPT_SHADE_MOTION_INSTANCES(X) \
-    X(2, 2, TM_ALL) \
-    X(1, MI_MAX_BXDFS, TM_ALL)
+    X(5, 2, TM_ALL) \
+    X(5, MI_MAX_BXDFS, TM_ALL)
 #ifdef MIPT_PART   // each part defines its own instances and declares the others
 #if MIPT_PART == 1
 #define MIPT_SHADE_IN_1
@@ -3498,6 +3500,11 @@ constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_
 #define MIPT_SHADE_IN_3
 #else
 #define MIPT_SHADE_IN_3 extern
+#endif
+#if MIPT_PART == 5
+#define MIPT_SHADE_IN_5
+#else
+#define MIPT_SHADE_IN_5 extern
 #endif
 #define MIPT_SHADE_INSTANCE(P_, NL_, TM_) MIPT_SHADE_IN_##P_ template __global__ void k_shade<NL_, (TM_)>(DScene, Pool, DevCounters *, unsigned);
 MIPT_SHADE_INSTANCES(MIPT_SHADE_INSTANCE)

@@ -1,19 +1,29 @@
 """Instruction counts and resources per device function of pt_kernels.hip (code size matters: the shading kernels are
 instruction-fetch bound; VGPRs, LDS and the private segment set occupancy and scratch traffic).
 Usage: python tools/isa_stats.py [--part N] [--json FILE] [extra hipcc flags]
---part N compiles one MIPT_PART of the file as the Makefile does (0: every kernel but k_shade, 1-3: the k_shade instances in
-three groups, 4: the BSDF probe's kernels); without it the whole file is one translation unit. --json FILE also writes {function: figures}.
+--part N compiles one MIPT_PART of the file as the Makefile does (0: every kernel but k_shade, 1-3 and 5: the k_shade instances in
+four groups, 4: the BSDF probe's kernels); without it the whole file is one translation unit. --json FILE also writes {function: figures}.
+The compile flags are the Makefile's (`make print-hipflags`: those of the part, or without --part the ones every unit shares);
+extra flags come after them, so `-Xarch_device -fslp-vectorize` shows a part as plain -O3 makes it.
 The report is about resources only: instruction classes are counted by prefix, no particular instruction is looked for."""
 import collections, json, os, re, shutil, subprocess, sys, tempfile
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def compile_asm(flags, workdir):
+def makefile_flags(part):
+    """The device compile flags of the Makefile (its print-hipflags target): those of unit part<N>, or without a part the
+    flags every unit shares."""
+    out = subprocess.check_output(["make", "-s", "--no-print-directory", "print-hipflags", "UNIT=" + ("" if part is None else "part%d" % part)],
+                                  cwd=root, text=True)
+    return out.split()
+
+
+def compile_asm(flags, workdir, part=None):
     out = os.path.join(workdir, "pt_isa.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-I" + root + "/include",
-                           "--offload-device-only", "-S", root + "/pbrt-v3-spectral_amd/csrc/device/pt_kernels.hip", "-o", out] + flags,
-                          stderr=subprocess.DEVNULL)
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + makefile_flags(part) +
+                          ["--offload-device-only", "-S", "pbrt-v3-spectral_amd/csrc/device/pt_kernels.hip", "-o", out] + flags,
+                          cwd=root, stderr=subprocess.DEVNULL)
     with open(out) as f:
         return f.read().split("\n")
 
@@ -59,6 +69,8 @@ def stats(lines):
         rows[n] = {"insts": sum(c.values()), "gload": g(("global_load", "flat_load", "buffer_load")),
                    "gstore": g(("global_store", "flat_store", "buffer_store")), "scratch": g("scratch_"),
                    "f64": sum(v for k, v in c.items() if "f64" in k), "call": c["s_swappc_b64"],
+                   "valu": g("v_"), "pk_f32": sum(v for k, v in c.items() if k.startswith("v_pk_") and k.endswith("_f32")),
+                   "vmov": g("v_mov_"), "vgpr_spills": field("vgpr_spill_count"),
                    "vgpr": field("vgpr_count") if r else vg.get(n, "?")[:12], "private_bytes": field("private_segment_fixed_size"),
                    "lds_bytes": field("group_segment_fixed_size")}
     return rows
@@ -78,14 +90,14 @@ def main(argv):
         flags.append("-DMIPT_PART=%d" % part)
     workdir = tempfile.mkdtemp(prefix="isa_stats_")
     try:
-        rows = stats(compile_asm(flags, workdir))
+        rows = stats(compile_asm(flags, workdir, part))
     finally:
         shutil.rmtree(workdir, ignore_errors=True)
     show = lambda v: "-" if v is None else str(v)
     for n, r in rows.items():
-        print("%-62s insts %6d gload %4d gstore %3d scratch %4d f64 %5d call %3d vgpr %s private %s lds %s" % (
-            short_name(n)[:62], r["insts"], r["gload"], r["gstore"], r["scratch"], r["f64"], r["call"], show(r["vgpr"]),
-            show(r["private_bytes"]), show(r["lds_bytes"])))
+        print("%-62s insts %6d valu %6d pk_f32 %4d vmov %4d gload %4d gstore %3d scratch %4d f64 %5d call %3d vgpr %s spills %s private %s lds %s" % (
+            short_name(n)[:62], r["insts"], r["valu"], r["pk_f32"], r["vmov"], r["gload"], r["gstore"], r["scratch"], r["f64"], r["call"],
+            show(r["vgpr"]), show(r["vgpr_spills"]), show(r["private_bytes"]), show(r["lds_bytes"])))
     if json_file:
         with open(json_file, "w") as f:
             json.dump(rows, f, indent=1)
