@@ -743,6 +743,15 @@ int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, cons
 #define MI_LIGHT_PROBE_SAMPLE_FLOATS (10 + MI_NSPEC)
 int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const float *queries, float *out);
 
+/* Parity tool for the Halton sampler's device routines: the scrambled radical inverse of `indices[i]` in `group` consecutive
+ * dimensions from `first_dims[i]` on, through the routines the shading kernel calls. Host pointers.
+ *   group 5, 2, 1: the grouped routines (five dimensions of the direct-lighting estimate, two of the next direction, one of the
+ *                  roulette draw), which read the per-dimension records built at create and take 32-bit indices;
+ *   group 0:       the single-dimension routine with its 64-bit digit loop (one value per query, any index).
+ * out: max(group, 1) floats per query. MI_ERR_INVALID for a dimension below 2 or a group that ends beyond the sampler's tables
+ * (mi_sampler.n_dims), and for an index beyond 32 bits with a group other than 0. Neighbouring queries share a wave. */
+int mi_pt_sampler_probe(mi_pt *pt, int32_t group, uint32_t n, const uint64_t *indices, const int32_t *first_dims, float *out);
+
 /* Parity tool for the BSDF code: material `material` of the scene through the BSDF routines of shading-kernel instance `instance`
  * (an index into the table mi_pt_shade_instances reports), one query at a time. Host pointers. The frame is the canonical one
  * (ns = ng = +z, ss = +x, ts = +y), every lobe of the material is on and nothing is overridden: what the kernel has at a

@@ -320,6 +320,8 @@ def hip_lib():
         if hasattr(lib, "mi_pt_bsdf_probe"):   # (as below: a parent's library behind MIPT_HIP_LIB has none)
             lib.mi_pt_bsdf_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
             lib.mi_pt_bsdf_probe_forms.argtypes = [C.c_int32, C.POINTER(C.c_uint32)]
+        if hasattr(lib, "mi_pt_sampler_probe"):   # (as above)
+            lib.mi_pt_sampler_probe.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
         lib.mi_pt_light_distribution.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]
         lib.mi_pt_debug_path.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         lib.mi_pt_shade_instances.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -674,6 +676,20 @@ class PathIntegrator:
         out = np.zeros((q.shape[0], n_out), np.float32)
         _check(hip_lib().mi_pt_light_probe(self._h, int(light), int(mode), q.shape[0], _fptr(q), _fptr(out)), "mi_pt_light_probe")
         return out[:, 0] if n_out == 1 else out
+
+    def sampler_probe(self, group, indices, first_dims):
+        """The Halton routines of the shading kernel on their own (mi_pt_sampler_probe): per query the scrambled radical inverse
+        of indices[i] in `group` consecutive dimensions from first_dims[i] on. group 5, 2, 1: the grouped routines (32-bit
+        indices) -> [n, group]; group 0: the single-dimension routine with its 64-bit loop -> [n, 1]. What the library refuses
+        is a RuntimeError with its message."""
+        idx = np.ascontiguousarray(indices, np.uint64).reshape(-1)
+        dims = np.ascontiguousarray(first_dims, np.int32).reshape(-1)
+        if idx.shape != dims.shape:
+            raise ValueError("sampler_probe: one first dimension per index")
+        out = np.zeros((idx.shape[0], max(int(group), 1)), np.float32)
+        _check(hip_lib().mi_pt_sampler_probe(self._h, int(group), idx.shape[0], idx.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             dims.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(out)), "mi_pt_sampler_probe")
+        return out
 
     def bsdf_probe(self, material, instance, mode, form, queries, flags=31):
         """One material of the scene through the BSDF routines of one k_shade instance (mi_pt_bsdf_probe; `instance` indexes

@@ -135,9 +135,80 @@ DEV float SampleDimension(const DScene &s, uint64_t index, int dim) {  // halton
 }
 // The same for dim >= 2 (every dimension after the film position) as one shared, out-of-line copy: the
 // integrator draws 8 dimensions per path vertex, and the shading kernels are bound by instruction fetch.
+// (The instances compiled for the Halton sampler alone call it for indices beyond 32 bits only: ScrambledDimensions5 / 2 / 1 below.)
 static DEV_CALL float ScrambledDimension(const int32_t *primes, const int32_t *primeSums, const uint16_t *perms,
                                          const uint64_t *primeMagic, uint64_t index, int dim) {
     return ScrambledRadicalInverseBase(primes[dim], primeMagic[dim], &perms[primeSums[dim]], index);
+}
+// Several consecutive dimensions (>= 2) of one 32-bit index in one out-of-line call, from the Halton records (HaltonDim,
+// d_scene.h): what a stage of the path vertex draws -- five for the direct-lighting estimate, two for the next direction.
+//  - The table comes through a pointer that says "global memory" (the callee of ScrambledDimension has lost the address space:
+//    flat loads, which count on both wait counters); the records are all fetched before the first digit.
+//  - invBase and the tail term come from the record: no division here (the single-dimension routine runs two IEEE
+//    sequences per call for values that depend on the dimension alone).
+//  - The K digit loops advance together, one digit of every chain per step, so the chains' multiplies and permutation loads
+//    overlap; a chain that has run out of digits idles (its load reads perm[0] and is not used). Inside a callee the
+//    caller-saved registers are free, so the K chains cost the calling kernel no register.
+//  - Per chain the operations and their order are those of ScrambledRadicalInverseBase's 32-bit loop: every value is bit-equal.
+// An index beyond 32 bits takes ScrambledDimension: nothing here divides a 64-bit number. (These routines name no __shared__
+// object and are handed the table, not the DScene: see the notes at PathSampler below.)
+typedef const __attribute__((address_space(1))) HaltonDim *HaltonDimTable;
+DEV HaltonDimTable HaltonTable(const HaltonDim *p) { return (HaltonDimTable)p; }
+template <int K>
+DEV void ScrambledDimensionsInterleaved(HaltonDimTable table, uint32_t index, int dim, float (&u)[K]) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4 *RecordWords;
+    typedef const __attribute__((address_space(1))) uint16_t *GlobalPerm;
+    const RecordWords words = (RecordWords)(table + dim);
+    u32x4 lo[K], hi[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { lo[k] = words[2 * k]; hi[k] = words[2 * k + 1]; }
+    uint32_t a[K];
+    uint64_t reversedDigits[K];
+    float invBaseN[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { a[k] = index; reversedDigits[k] = 0; invBaseN[k] = 1; }
+    for (;;) {
+        uint32_t any = a[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) any |= a[k];
+        if (!any) break;
+        uint32_t next[K], perm[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const uint32_t ub = lo[k].x;
+            next[k] = DivMagic(a[k], (uint64_t)lo[k].z | ((uint64_t)lo[k].w << 32));
+            const uint32_t digit = a[k] - next[k] * ub;
+            perm[k] = ((GlobalPerm)table)[lo[k].y + digit];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (a[k]) {   // (written as selects this compiles to the same branches, and to two callee-saved registers on the stack)
+                reversedDigits[k] = reversedDigits[k] * lo[k].x + perm[k];
+                invBaseN[k] *= __uint_as_float(hi[k].x);
+            }
+            a[k] = next[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) u[k] = minf(invBaseN[k] * ((float)reversedDigits[k] + __uint_as_float(hi[k].y)), kOneMinusEpsilon);
+}
+struct Halton5 { float u0, u1, u2, u3, u4; };
+struct Halton2 { float u0, u1; };
+static DEV_CALL Halton5 ScrambledDimensions5(HaltonDimTable table, uint32_t index, int dim) {
+    float u[5];
+    ScrambledDimensionsInterleaved<5>(table, index, dim, u);
+    return Halton5{u[0], u[1], u[2], u[3], u[4]};
+}
+static DEV_CALL Halton2 ScrambledDimensions2(HaltonDimTable table, uint32_t index, int dim) {
+    float u[2];
+    ScrambledDimensionsInterleaved<2>(table, index, dim, u);
+    return Halton2{u[0], u[1]};
+}
+static DEV_CALL float ScrambledDimensions1(HaltonDimTable table, uint32_t index, int dim) {
+    float u[1];
+    ScrambledDimensionsInterleaved<1>(table, index, dim, u);
+    return u[0];
 }
 DEV float SampleDimensionFrom2(const DScene &s, uint64_t index, int dim) {
     if (s.samplerType == MI_SAMPLER_SOBOL) return SobolSampleFloat(s.sobolMatrices, index, dim);

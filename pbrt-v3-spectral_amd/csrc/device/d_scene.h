@@ -26,6 +26,18 @@ namespace dpt {
 #define PRIM_FLAG_ALPHA 32u   // the triangle's mesh has an "alpha" / "shadowalpha" mask (mi_mesh.alpha_tex)
 #define PRIM_CLASS_SHIFT 8      /* bits 8-11: shading class of the primitive's material (15 = no BSDF) */
 
+// What the scrambled radical inverse needs of one Halton dimension, as two 16-byte loads (built at create, BuildHaltonDims in
+// pt_kernels.hip). permOffset counts uint16 entries from the table's first byte to the dimension's permutation: the
+// permutations lie behind the records. invBase = 1.f / (float)base and tail = invBase * (float)perm[0] / (1 - invBase),
+// the two quotients that depend on the dimension alone.
+struct alignas(32) HaltonDim {
+    uint32_t base, permOffset;
+    uint64_t magic;   // ceil(2^64 / base), DScene::primeMagic
+    float invBase, tail;
+    uint32_t pad[2];
+};
+static_assert(sizeof(HaltonDim) == 32, "HaltonDim: two 16-byte loads");
+
 struct DScene {
     const float4 *nodes;
     const float4 *wnodes;  // wide nodes (see pt_kernels.hip): bvhWidth 2 -> 64 B per BVH2 interior node (both children's boxes);
@@ -113,6 +125,9 @@ struct DScene {
     // the path spawns), allocated and written only when motions is set.
     const mi_motion *motions;
     int timePlane;
+    // Halton records (appended, as above): one HaltonDim per sampler dimension, and behind the last record, in the same
+    // allocation, a copy of the digit permutations -- so the grouped sampler routines (d_sampling.h) take one pointer.
+    const HaltonDim *haltonDims;
 };
 
 struct Interaction {

@@ -2690,14 +2690,31 @@ DEV int DirectLighting(const DScene &s, const Pool &pool, SpectrumTile &tile, ui
             const uint32_t di = LightDistribIndex(s, isect.p);
             float selPdf;
             // the five dimensions of the estimate (light choice, light sample, BSDF sample)
-            float u5[5];
-            u5[0] = Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot);
+            // (Halton, 32-bit indices: all five in one call -- ScrambledDimensions5, d_sampling.h. The four of the estimate are
+            // then there before the light is chosen; the dimension counter still moves as the reference's does, by one here
+            // and by four more only where the estimate is made.)
+            float u5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+            const bool grouped = HALTON_ONLY && s.index32;
+            if (grouped) {
+                const Halton5 r = ScrambledDimensions5(HaltonTable(s.haltonDims), (uint32_t)ps.index, ps.dim);
+                u5[0] = r.u0; u5[1] = r.u1; u5[2] = r.u2; u5[3] = r.u3; u5[4] = r.u4;
+                ps.dim += 1;
+            } else u5[0] = Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot);
             const int lightNum = SampleDiscrete(s.ldFunc + (size_t)di * s.nLights, s.ldCdf + (size_t)di * (s.nLights + 1),
                                                 s.ldFuncInt[di], (int)s.nLights, u5[0], &selPdf);
             if (selPdf != 0) {
                 // uLight = Get2D(), uScattering = Get2D() (integrator.cpp:100-101)
-                Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[1], &u5[2]);
-                Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[3], &u5[4]);
+                if (grouped) ps.dim += 4;
+                else if constexpr (HALTON_ONLY) {   // (indices beyond 32 bits: the single-dimension routine, one call site)
+#pragma unroll 1
+                    for (int k = 1; k < 5; ++k) {   // (selects, not u5[k]: an array indexed by a loop counter lives in private memory)
+                        const float v = Get1D<true>(s, ps, pixelPlane, samplePlane, slot);
+                        u5[1] = k == 1 ? v : u5[1]; u5[2] = k == 2 ? v : u5[2]; u5[3] = k == 3 ? v : u5[3]; u5[4] = k == 4 ? v : u5[4];
+                    }
+                } else {
+                    Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[1], &u5[2]);
+                    Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u5[3], &u5[4]);
+                }
                 const float uL0 = u5[1], uL1 = u5[2], uS0 = u5[3], uS1 = u5[4];
                 const mi_light &light = s.lights[lightNum];
                 const bool selIsOne = (selPdf == 1.f);  // x / 1 == x: skip the division
@@ -2724,8 +2741,18 @@ DEV int Continuation(const DScene &s, const Pool &pool, SpectrumTile &tile, uint
     V3 wo = -rd, wi;
     float pdf = 0;
     int sflags = 0;
-    float u2[2];
-    Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u2[0], &u2[1]);
+    float u2[2] = {0.f, 0.f};
+    if (HALTON_ONLY && s.index32) {   // (as in DirectLighting: both dimensions in one call)
+        const Halton2 r = ScrambledDimensions2(HaltonTable(s.haltonDims), (uint32_t)ps.index, ps.dim);
+        u2[0] = r.u0; u2[1] = r.u1;
+        ps.dim += 2;
+    } else if constexpr (HALTON_ONLY) {
+#pragma unroll 1
+        for (int k = 0; k < 2; ++k) {
+            const float v = Get1D<true>(s, ps, pixelPlane, samplePlane, slot);
+            u2[0] = k == 0 ? v : u2[0]; u2[1] = k == 1 ? v : u2[1];
+        }
+    } else Get2D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot, &u2[0], &u2[1]);
     const float u0 = u2[0], u1 = u2[1];
     BSDFEvalT<NL> ev;
     V3 wiLocal;
@@ -2803,7 +2830,10 @@ DEV int Continuation(const DScene &s, const Pool &pool, SpectrumTile &tile, uint
             // Russian roulette, path.cpp:176-184
             if (maxRR < s.rrThreshold && h.bounces > 3) {
                 float q = maxf(.05f, 1 - maxRR);
-                if (Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot) < q) killed = true;
+                float uRR;
+                if (HALTON_ONLY && s.index32) uRR = ScrambledDimensions1(HaltonTable(s.haltonDims), (uint32_t)ps.index, ps.dim++);
+                else uRR = Get1D<HALTON_ONLY>(s, ps, pixelPlane, samplePlane, slot);
+                if (uRR < q) killed = true;
                 else {
                     const Divisor inv = MakeDivisor(1 - q);
 #pragma unroll 1
@@ -3220,6 +3250,26 @@ __global__ void k_light_probe(DScene s, int light, int mode, const float *in, ui
         const V3 wi(r[6], r[7], r[8]);
         out[i] = IsDeltaLight(l) ? 0.f : (l.type == MI_LIGHT_INFINITE ? InfinitePdfLi(s, l, wi) : ShapePdf<true>(s, l.shape, l.area, ref, wi));
     }
+}
+
+// ------------------------------------------------------------------ the Halton routines on their own (mi_pt_sampler_probe)
+// Query i = (index, first dimension) as two 64-bit words; `group` values per query: the grouped routines k_shade calls (5, 2, 1;
+// 32-bit indices) or ScrambledDimension (0: one value, any index). Neighbouring lanes get what the caller gives them: different
+// dimensions and digit counts in one wave run the interleaved loops with some chains finished and others not.
+__global__ void k_sampler_probe(DScene s, int group, const uint64_t *in, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t index = in[2 * (size_t)i];
+    const int dim = (int)in[2 * (size_t)i + 1];
+    if (group == 5) {
+        const Halton5 r = ScrambledDimensions5(HaltonTable(s.haltonDims), (uint32_t)index, dim);
+        float *o = out + 5 * (size_t)i;
+        o[0] = r.u0; o[1] = r.u1; o[2] = r.u2; o[3] = r.u3; o[4] = r.u4;
+    } else if (group == 2) {
+        const Halton2 r = ScrambledDimensions2(HaltonTable(s.haltonDims), (uint32_t)index, dim);
+        out[2 * (size_t)i] = r.u0; out[2 * (size_t)i + 1] = r.u1;
+    } else if (group == 1) out[i] = ScrambledDimensions1(HaltonTable(s.haltonDims), (uint32_t)index, dim);
+    else out[i] = ScrambledDimension(s.primes, s.primeSums, s.perms, s.primeMagic, index, dim);
 }
 
 // ------------------------------------------------------------------ scalar helpers on their own (mi_pt_math_probe)
@@ -3769,6 +3819,7 @@ struct mi_pt {
     bool hasAlphaMasks = false;      // picks the traversal kernels compiled with the alpha-mask test
     bool hasInstances = false;       // ... and with the TransformedPrimitive code (those carry the alpha-mask test too)
     uint32_t nQuadrics = 0;          // n_spheres + n_disks (mi_pt_shape_probe)
+    int samplerDims = 0;             // mi_sampler.n_dims: the dimensions the Halton tables hold (mi_pt_sampler_probe)
     std::vector<int> lightTypes;     // mi_light.type of every light (mi_pt_light_probe)
     std::vector<int> materialLobes;  // mi_material.n_bxdfs of every material, -1 - n_bxdfs for one that reads an image texture (mi_pt_bsdf_probe)
     bool hasQuadrics = false;        // the scene has spheres or disks: the quadric lists of rays can overflow (k_resolve_overflow is launched)
@@ -4502,6 +4553,28 @@ std::vector<uint64_t> BuildPrimeMagics(const mi_sampler &sm) {
     return magic;
 }
 
+// The Halton records (HaltonDim, d_scene.h) of every sampler dimension, and behind them a copy of the permutations, which
+// permOffset reaches from the table's start. invBase and tail are computed here in float, in the expression order of
+// ScrambledRadicalInverseBase (d_sampling.h): this file is compiled without contraction on both sides and IEEE division is
+// correctly rounded on both, so the two floats are the bits the device's own divisions give.
+std::vector<HaltonDim> BuildHaltonDims(const mi_sampler &sm, const std::vector<uint64_t> &magic) {
+    const size_t nDims = (size_t)sm.n_dims, permBytes = (size_t)sm.n_perms * sizeof(uint16_t);
+    std::vector<HaltonDim> table(nDims + (permBytes + sizeof(HaltonDim) - 1) / sizeof(HaltonDim));
+    memset(table.data(), 0, table.size() * sizeof(HaltonDim));
+    for (size_t i = 0; i < nDims; ++i) {
+        HaltonDim &r = table[i];
+        const uint16_t *perm = sm.perms + sm.prime_sums[i];
+        r.base = (uint32_t)sm.primes[i];
+        r.permOffset = (uint32_t)(nDims * (sizeof(HaltonDim) / sizeof(uint16_t)) + (size_t)sm.prime_sums[i]);
+        r.magic = magic[i];
+        const float invBase = 1.f / (float)sm.primes[i];
+        r.invBase = invBase;
+        r.tail = invBase * (float)perm[0] / (1 - invBase);
+    }
+    if (permBytes) memcpy((void *)(table.data() + nDims), sm.perms, permBytes);
+    return table;
+}
+
 // The per-pixel Halton index offsets over a 128 x 128 tile (GetIndexForSample, halton.cpp:98-118).
 std::vector<uint32_t> BuildPixelOffsets(const mi_sampler &sm) {
     std::vector<uint32_t> table(128 * 128, 0);
@@ -4542,6 +4615,7 @@ struct HostTables {
     std::vector<float4> primTri, lightBounds;
     std::vector<int> lightPrim;
     std::vector<uint64_t> primeMagic;
+    std::vector<HaltonDim> haltonDims;
     std::vector<uint32_t> pixelOffsets;
     std::vector<float> ewaWeights;
     bool hasAlphaMasks = false, hasQuadrics = false, misAny = false;
@@ -4556,6 +4630,7 @@ int BuildHostTables(const mi_scene_desc *d, HostTables &h) {
     h.lightBounds = BuildLightBounds(d);
     h.lightPrim = BuildLightPrims(d, h.misAny);
     h.primeMagic = BuildPrimeMagics(d->sampler);
+    h.haltonDims = BuildHaltonDims(d->sampler, h.primeMagic);
     h.pixelOffsets = BuildPixelOffsets(d->sampler);
     h.ewaWeights = BuildEwaWeights();
     return MI_OK;
@@ -4608,6 +4683,7 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     pt->hasInstances = d->n_instances > 0;
     pt->hasQuadrics = h.hasQuadrics;
     pt->nQuadrics = d->n_spheres + d->n_disks;
+    pt->samplerDims = d->sampler.n_dims;
     for (uint32_t i = 0; i < d->n_lights; ++i) pt->lightTypes.push_back(d->lights[i].type);
     for (uint32_t i = 0; i < d->n_materials; ++i) {
         const mi_material &m = d->materials[i];
@@ -4662,6 +4738,7 @@ int UploadScene(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
         up(d->sampler.sobol_vdc_inv, (size_t)MI_SOBOL_MATRIX_SIZE, s.sobolVdcInv);
     }
     up(h.primeMagic.data(), h.primeMagic.size(), s.primeMagic);
+    up(h.haltonDims.data(), h.haltonDims.size(), s.haltonDims);
     up(h.pixelOffsets.data(), h.pixelOffsets.size(), s.pixelOffsetTable);
     std::vector<mi_envmap> envs(d->envmaps, d->envmaps + d->n_envmaps);
     for (mi_envmap &m : envs) {
@@ -5356,6 +5433,24 @@ int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const 
     const size_t nOut = mode == 0 ? MI_LIGHT_PROBE_SAMPLE_FLOATS : (mode == 1 ? 1 : MI_NSPEC);
     return RunProbe(pt->device, queries, (size_t)n * nIn * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
         hipLaunchKernelGGL(k_light_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)light, (int)mode, (float *)dq, n, (float *)dout);
+    });
+}
+
+int mi_pt_sampler_probe(mi_pt *pt, int32_t group, uint32_t n, const uint64_t *indices, const int32_t *first_dims, float *out) {
+    if (!pt || !indices || !first_dims || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (group != 0 && group != 1 && group != 2 && group != 5) { g_err = "mi_pt_sampler_probe: group must be 0, 1, 2 or 5"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_sampler_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    const int count = group == 0 ? 1 : group;
+    std::vector<uint64_t> q(2 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (first_dims[i] < 2 || first_dims[i] + count > pt->samplerDims) { g_err = "mi_pt_sampler_probe: dimensions outside [2, n_dims)"; return MI_ERR_INVALID; }
+        if (group != 0 && (indices[i] >> 32)) { g_err = "mi_pt_sampler_probe: the grouped routines take 32-bit indices"; return MI_ERR_INVALID; }
+        q[2 * (size_t)i] = indices[i];
+        q[2 * (size_t)i + 1] = (uint64_t)first_dims[i];
+    }
+    if (n == 0) return MI_OK;
+    return RunProbe(pt->device, q.data(), q.size() * sizeof(uint64_t), out, (size_t)n * count * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_sampler_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)group, (const uint64_t *)dq, n, (float *)dout);
     });
 }
 
