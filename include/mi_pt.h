@@ -379,7 +379,12 @@ typedef struct mi_lightdistrib {
 } mi_lightdistrib;
 
 /* ---- camera: perspective (src/cameras/perspective.cpp:45-146) or, ABI v13, realistic (src/cameras/realistic.cpp) */
-typedef enum mi_camera_type { MI_CAMERA_PERSPECTIVE = 0, MI_CAMERA_REALISTIC = 1 } mi_camera_type;
+/* MI_CAMERA_ORTHOGRAPHIC (src/cameras/orthographic.cpp) and MI_CAMERA_ENVIRONMENT (src/cameras/environment.cpp, the fork's
+ * omnistereo camera) are made by the front end under MIPT_CAMERAS=all only. Orthographic: raster_to_camera =
+ * Inverse(Orthographic(0, 1)) * RasterToScreen, lens_radius / focal_distance as parsed. Environment: lens_radius is 0 (no lens
+ * dimensions are evaluated), raster_to_camera is the perspective stand-in nothing renders with, and the four env_* fields of
+ * mi_scene_desc hold the omnistereo parameters. Both have ray weight 1. */
+typedef enum mi_camera_type { MI_CAMERA_PERSPECTIVE = 0, MI_CAMERA_REALISTIC = 1, MI_CAMERA_ORTHOGRAPHIC = 2, MI_CAMERA_ENVIRONMENT = 3 } mi_camera_type;
 /* ABI v13 -- Camera "realistic": the lens system as RealisticCamera's constructor leaves it (realistic.cpp:126-187). Plain
  * data. elements[i] = {curvature radius, thickness, eta, aperture radius} of interface i, front (scene side) first, in
  * metres (the file's mm * .001, the diameter halved); curvature radius 0 is the aperture stop, whose aperture is the
@@ -543,6 +548,10 @@ typedef struct mi_scene_desc {
     const mi_lens *lens;           /* ABI v13: MI_CAMERA_REALISTIC: the lens system; NULL for a perspective camera */
     uint32_t n_disks; const mi_disk *disks; /* ABI v14: quadric indices [n_spheres, n_spheres + n_disks) */
     uint32_t n_motions; const mi_motion *motions; /* object motion: the records mi_instance.motion points into */
+    /* MI_CAMERA_ENVIRONMENT (appended under an unchanged ABI number; read for that camera type only): "ipd" (0),
+     * "poleMergeAngleTo" (90), "poleMergeAngleFrom" (90) -- compared as given against an altitude in radians, as the
+     * reference does -- and "convergencedistance" (Infinity: parallel convergence) */
+    float env_ipd, env_pole_merge_to, env_pole_merge_from, env_convergence_distance;
 } mi_scene_desc;
 
 /* Counters with the reference's STAT names (src/core/integrator.cpp:48,

@@ -125,7 +125,7 @@ class LightDistrib(C.Structure):
 
 MAX_LENS_ELEMENTS = 32
 EXIT_PUPIL_BOUNDS = 64
-CAMERA_PERSPECTIVE, CAMERA_REALISTIC = 0, 1
+CAMERA_PERSPECTIVE, CAMERA_REALISTIC, CAMERA_ORTHOGRAPHIC, CAMERA_ENVIRONMENT = 0, 1, 2, 3
 
 
 class Lens(C.Structure):
@@ -191,7 +191,10 @@ class SceneDesc(C.Structure):
                 ("prim_meta", C.POINTER(PrimMeta)),
                 ("camera_type", C.c_int32), ("lens", C.POINTER(Lens)),
                 ("n_disks", C.c_uint32), ("disks", C.POINTER(Disk)),
-                ("n_motions", C.c_uint32), ("motions", C.POINTER(Motion))]
+                ("n_motions", C.c_uint32), ("motions", C.POINTER(Motion)),
+                # Camera "environment" (MIPT_CAMERAS=all): the omnistereo parameters
+                ("env_ipd", C.c_float), ("env_pole_merge_to", C.c_float), ("env_pole_merge_from", C.c_float),
+                ("env_convergence_distance", C.c_float)]
 
 
 class Counters(C.Structure):

@@ -111,7 +111,7 @@ struct DScene {
     int index32, storePixelSample;
     int cameraType;        // mi_camera_type
     const mi_lens *lens;   // Camera "realistic": the device copy of mi_scene_desc.lens (d_lens.h reads the table from here)
-    int lensDiff;          // a realistic camera in front of a textured material: the pool carries the camera ray's differentials (P_LENSDIFF)
+    int lensDiff;          // a camera other than the perspective one in front of a textured material: the pool carries the camera ray's differentials (P_LENSDIFF)
     int ignoreRayWeight;   // set per pass: Integrator "metadata" adds its samples with weight 1 (a realistic camera's ray weight is ignored)
     const float *pixTab1, *pixTab2;
     int pixelDims, xSamples, ySamples, jitter;
@@ -128,6 +128,10 @@ struct DScene {
     // Halton records (appended, as above): one HaltonDim per sampler dimension, and behind the last record, in the same
     // allocation, a copy of the digit permutations -- so the grouped sampler routines (d_sampling.h) take one pointer.
     const HaltonDim *haltonDims;
+    // Camera "orthographic" / "environment" (appended, as above; d_camera.h): Film::fullResolution and the omnistereo
+    // parameters of mi_scene_desc, read by the two cameras' k_generate instances and the camera probe only.
+    int fullRes[2];
+    float envIpd, envPoleMergeTo, envPoleMergeFrom, envConvergenceDistance;
 };
 
 struct Interaction {

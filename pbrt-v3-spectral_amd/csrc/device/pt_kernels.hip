@@ -35,6 +35,7 @@
 #include "d_sampling.h"
 #include "d_texture.h"
 #include "d_lens.h"
+#include "d_camera.h"
 
 using namespace dpt;
 
@@ -1590,8 +1591,11 @@ DEV void CameraRay(const DScene &s, float pFilmX, float pFilmY, float lensU, flo
 // "spectralpath" band that is vignetted restarts as the next band like any finished one.
 // TIME: the scene has moving instances: the ray's time -- Lerp(time sample, shutterOpen, shutterClose), perspective.cpp:141 --
 // goes to the pool's time plane (PathTime), so the time sample is evaluated in front of a camera that stands still too.
-template <bool MOVING, bool REAL, bool TIME = false>
+// CAM: the camera's mi_camera_type. MI_CAMERA_ORTHOGRAPHIC / MI_CAMERA_ENVIRONMENT (d_camera.h): weight 1, no weight plane; in
+// front of textures (DScene::lensDiff) the ray's differentials go to the planes the realistic camera's go to.
+template <bool MOVING, int CAM, bool TIME = false>
 __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *film, DevCounters *ctr, WorkDesc wd) {
+    constexpr bool REAL = CAM == MI_CAMERA_REALISTIC;
     __shared__ float sL[BLOCK * 33];
     __shared__ float sFilter[256];  // the 16x16 filter table, one LDS copy per block
     __shared__ unsigned sWant[SLOT_CHUNKS][BLOCK / 64], sPrim[SLOT_CHUNKS][BLOCK / 64], sCont[SLOT_CHUNKS][BLOCK / 64];
@@ -1920,6 +1924,16 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
                     }
                 }
                 pool.F(P_WEIGHT, slot) = s.ignoreRayWeight ? 1.f : rayWeight;   // (Integrator "metadata": IgnoreRayWeight)
+            } else if constexpr (CAM == MI_CAMERA_ORTHOGRAPHIC || CAM == MI_CAMERA_ENVIRONMENT) {
+                if (s.lensDiff) {   // (uniform; the environment camera's offset rays are two more rays: made only where a texture reads them)
+                    V3 diff[4];
+                    OptInCameraRay<CAM, MOVING>(s, pfx, pfy, lu, lv, tu, &ray, nullptr, diff, s.invSqrtSpp);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        pool.F(P_LENSDIFF + 3 * k, slot) = diff[k].x; pool.F(P_LENSDIFF + 3 * k + 1, slot) = diff[k].y; pool.F(P_LENSDIFF + 3 * k + 2, slot) = diff[k].z;
+                    }
+                } else
+                    OptInCameraRay<CAM, MOVING>(s, pfx, pfy, lu, lv, tu, &ray, nullptr, nullptr, 0.f);
             } else
                 CameraRay<MOVING>(s, pfx, pfy, lu, lv, &ray, tu);
             ++cam;
@@ -1984,12 +1998,21 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
 // The k_generate of a scene's camera: a uniform choice per launch.
 using GenerateKernel = void (*)(DScene, Pool, float *, DevCounters *, WorkDesc);
 static GenerateKernel GenerateKernelOf(const DScene &s) {
+    const bool moving = s.camera.animated != 0;
     if (s.motions) {
-        if (s.cameraType == MI_CAMERA_REALISTIC) return s.camera.animated ? k_generate<true, true, true> : k_generate<false, true, true>;
-        return s.camera.animated ? k_generate<true, false, true> : k_generate<false, false, true>;
+        switch (s.cameraType) {
+        case MI_CAMERA_REALISTIC: return moving ? k_generate<true, MI_CAMERA_REALISTIC, true> : k_generate<false, MI_CAMERA_REALISTIC, true>;
+        case MI_CAMERA_ORTHOGRAPHIC: return moving ? k_generate<true, MI_CAMERA_ORTHOGRAPHIC, true> : k_generate<false, MI_CAMERA_ORTHOGRAPHIC, true>;
+        case MI_CAMERA_ENVIRONMENT: return moving ? k_generate<true, MI_CAMERA_ENVIRONMENT, true> : k_generate<false, MI_CAMERA_ENVIRONMENT, true>;
+        default: return moving ? k_generate<true, MI_CAMERA_PERSPECTIVE, true> : k_generate<false, MI_CAMERA_PERSPECTIVE, true>;
+        }
     }
-    if (s.cameraType == MI_CAMERA_REALISTIC) return s.camera.animated ? k_generate<true, true> : k_generate<false, true>;
-    return s.camera.animated ? k_generate<true, false> : k_generate<false, false>;
+    switch (s.cameraType) {
+    case MI_CAMERA_REALISTIC: return moving ? k_generate<true, MI_CAMERA_REALISTIC> : k_generate<false, MI_CAMERA_REALISTIC>;
+    case MI_CAMERA_ORTHOGRAPHIC: return moving ? k_generate<true, MI_CAMERA_ORTHOGRAPHIC> : k_generate<false, MI_CAMERA_ORTHOGRAPHIC>;
+    case MI_CAMERA_ENVIRONMENT: return moving ? k_generate<true, MI_CAMERA_ENVIRONMENT> : k_generate<false, MI_CAMERA_ENVIRONMENT>;
+    default: return moving ? k_generate<true, MI_CAMERA_PERSPECTIVE> : k_generate<false, MI_CAMERA_PERSPECTIVE>;
+    }
 }
 
 #endif   // MIPT_HAS_MAIN
@@ -3090,7 +3113,8 @@ __global__ void k_camera_rays(DScene s, const int32_t *__restrict__ samples, uin
 }
 
 // mi_pt_camera_rays_ex: the same with the ray's weight and its scaled differentials; a realistic camera's through LensCameraRay.
-template <bool MOVING, bool REAL>
+// CAM: the camera's mi_camera_type (the orthographic and environment cameras through OptInCameraRay, d_camera.h).
+template <bool MOVING, int CAM>
 __global__ void k_camera_rays_ex(DScene s, const int32_t *__restrict__ samples, uint32_t n, int band, float *__restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -3103,9 +3127,11 @@ __global__ void k_camera_rays_ex(DScene s, const int32_t *__restrict__ samples, 
     Ray ray;
     float weight = 1.f;
     V3 diff[4];
-    if constexpr (REAL) {
+    if constexpr (CAM == MI_CAMERA_REALISTIC) {
         const float wavelength = s.nBands > 1 ? BandWavelength(s.bandDelta, band) : 550.f;
         weight = LensCameraRay<MOVING>(s, pfx, pfy, lu, lv, tu, wavelength, &ray, &time, diff, s.invSqrtSpp);
+    } else if constexpr (CAM == MI_CAMERA_ORTHOGRAPHIC || CAM == MI_CAMERA_ENVIRONMENT) {
+        OptInCameraRay<CAM, MOVING>(s, pfx, pfy, lu, lv, tu, &ray, &time, diff, s.invSqrtSpp);   // (every band gets the same ray: neither camera reads the wavelength)
     } else {
         CameraRay<MOVING>(s, pfx, pfy, lu, lv, &ray, tu, &time);
         float m[16];
@@ -3887,7 +3913,9 @@ int Alloc(mi_pt *pt, size_t bytes, T **dst, const char *what) {
 // Spectral quad planes of a path slot: spectralpath keeps one set more, the stitched spectrum of the camera sample (Q_LCA).
 int QuadPlanes(const DScene &s) { return Q_COUNT + (s.nBands > 1 ? NQ : 0); }
 // Float planes of a path slot: a realistic camera keeps the ray weight (P_WEIGHT).
-int FloatPlanes(const DScene &s) { return P_COUNT + (s.cameraType == MI_CAMERA_REALISTIC ? 1 + (s.lensDiff ? N_LENSDIFF : 0) : 0) + (s.motions ? 1 : 0); }
+// (the orthographic and environment cameras have weight 1 and no such plane -- except in front of textures, where the
+// differentials' planes keep their numbers behind it)
+int FloatPlanes(const DScene &s) { return P_COUNT + (s.cameraType == MI_CAMERA_REALISTIC || s.lensDiff ? 1 : 0) + (s.lensDiff ? N_LENSDIFF : 0) + (s.motions ? 1 : 0); }
 // (the time plane of a scene with moving instances: the last one)
 int TimePlaneOf(const DScene &s) { return s.motions ? FloatPlanes(s) - 1 : 0; }
 // Samples per pixel of one pass.
@@ -4107,7 +4135,7 @@ int CheckSceneDesc(const mi_scene_desc *d) {
         if (nVox == 0 || nVox * d->n_lights > (1ull << 31)) { g_err = "spatial light distribution too large for the dense per-voxel table"; return MI_ERR_UNSUPPORTED; }
     }
     if (d->integrator.n_ca_bands < 1 || d->integrator.n_ca_bands > MI_NSPEC) { g_err = "n_ca_bands must be in [1, 31]"; return MI_ERR_INVALID; }
-    if (d->camera_type != MI_CAMERA_PERSPECTIVE && d->camera_type != MI_CAMERA_REALISTIC) { g_err = "unknown mi_scene_desc.camera_type"; return MI_ERR_INVALID; }
+    if (d->camera_type < MI_CAMERA_PERSPECTIVE || d->camera_type > MI_CAMERA_ENVIRONMENT) { g_err = "unknown mi_scene_desc.camera_type"; return MI_ERR_INVALID; }
     if (d->camera_type == MI_CAMERA_REALISTIC) {
         const mi_lens *l = d->lens;
         if (!l || l->n_elements < 1 || l->n_elements > MI_MAX_LENS_ELEMENTS || l->full_res[0] < 1 || l->full_res[1] < 1 || !(l->film_diagonal > 0)) {
@@ -4657,8 +4685,11 @@ void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
     s.lens = nullptr;   // (UploadScene: the device copy)
     s.motions = nullptr; s.timePlane = 0;   // (UploadScene, when an instance moves)
     s.lensDiff = 0;
-    if (d->camera_type == MI_CAMERA_REALISTIC)
+    if (d->camera_type != MI_CAMERA_PERSPECTIVE)   // (k_shade restates the perspective camera's offset rays itself)
         for (uint32_t i = 0; i < d->n_materials; ++i) if (d->materials[i].textured) s.lensDiff = 1;
+    s.fullRes[0] = d->film.full_res[0]; s.fullRes[1] = d->film.full_res[1];
+    s.envIpd = d->env_ipd; s.envPoleMergeTo = d->env_pole_merge_to; s.envPoleMergeFrom = d->env_pole_merge_from;
+    s.envConvergenceDistance = d->env_convergence_distance;
     for (int i = 0; i < 4; ++i) { s.croppedBounds[i] = d->film.cropped_bounds[i]; s.sampleBounds[i] = d->film.sample_bounds[i]; s.pixelBounds[i] = d->integrator.pixel_bounds[i]; }
     s.filterRadius[0] = d->film.filter_radius[0]; s.filterRadius[1] = d->film.filter_radius[1];
     s.maxSampleLuminance = d->film.max_sample_luminance;
@@ -5484,7 +5515,7 @@ int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out)
     if (n > (1u << 24)) { g_err = "mi_pt_camera_rays: more than 2^24 samples"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
     const DScene &s = pt->scene;
-    if (s.cameraType == MI_CAMERA_REALISTIC) {   // the lens camera's ray at 550 nm (band 0), in this call's layout
+    if (s.cameraType != MI_CAMERA_PERSPECTIVE) {   // the lens camera's ray at 550 nm (band 0) or an opt-in camera's, in this call's layout
         std::vector<float> ex((size_t)n * MI_CAMERA_RAY_EX_FLOATS);
         const int rc = mi_pt_camera_rays_ex(pt, samples, n, 0, ex.data());
         if (rc != MI_OK) return rc;
@@ -5504,9 +5535,11 @@ int mi_pt_camera_rays_ex(mi_pt *pt, const int32_t *samples, uint32_t n, int32_t 
     if (band < 0 || band >= std::max(1, s.nBands)) { g_err = "mi_pt_camera_rays_ex: no such band"; return MI_ERR_INVALID; }
     if (n == 0) return MI_OK;
     if (const int rc = CheckCameraSamples(pt, samples, n, "mi_pt_camera_rays_ex")) return rc;
-    const bool real = s.cameraType == MI_CAMERA_REALISTIC, moving = s.camera.animated != 0;
-    auto kernel = real ? (moving ? k_camera_rays_ex<true, true> : k_camera_rays_ex<false, true>)
-                       : (moving ? k_camera_rays_ex<true, false> : k_camera_rays_ex<false, false>);
+    const bool moving = s.camera.animated != 0;
+    auto kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_PERSPECTIVE> : k_camera_rays_ex<false, MI_CAMERA_PERSPECTIVE>;
+    if (s.cameraType == MI_CAMERA_REALISTIC) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_REALISTIC> : k_camera_rays_ex<false, MI_CAMERA_REALISTIC>;
+    if (s.cameraType == MI_CAMERA_ORTHOGRAPHIC) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_ORTHOGRAPHIC> : k_camera_rays_ex<false, MI_CAMERA_ORTHOGRAPHIC>;
+    if (s.cameraType == MI_CAMERA_ENVIRONMENT) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_ENVIRONMENT> : k_camera_rays_ex<false, MI_CAMERA_ENVIRONMENT>;
     return RunProbe(pt->device, samples, (size_t)n * 3 * sizeof(int32_t), out, (size_t)n * MI_CAMERA_RAY_EX_FLOATS * sizeof(float), [&](void *ds, void *dout) {
         hipLaunchKernelGGL(kernel, ProbeGrid(n), dim3(BLOCK), 0, 0, s, (int32_t *)ds, n, (int)band, (float *)dout);
     });

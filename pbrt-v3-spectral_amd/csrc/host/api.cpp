@@ -722,6 +722,7 @@ Api::Api(HostScene *s, const LoadOverrides &o) : scene(s), ov(o) {
     if (const char *e = getenv("MIPT_INSTANCES")) expandInstances = std::string(e) == "expand";
     if (const char *e = getenv("MIPT_OBJECT_MOTION")) objectMotion = std::string(e) == "1";
     if (const char *e = getenv("MIPT_TEXTURES")) allTextures = std::string(e) == "all";
+    if (const char *e = getenv("MIPT_CAMERAS")) allCameras = std::string(e) == "all";
     // default material: matte with default params (GraphicsState ctor, api.cpp:214-222)
     gs.currentMaterial = NewMaterialInstance("matte", ParamSet());
 }

@@ -79,6 +79,7 @@ struct Api {
     std::vector<InstanceRec> instanceRecs;
     bool objectMotion = false;   // MIPT_OBJECT_MOTION=1: shapes and instances under an animated CTM become moving primitives
     bool allTextures = false;    // MIPT_TEXTURES=all: the 2-D mappings beside "uv" and the classes "dots", "uv", "bilerp", float and 3-D "checkerboard"
+    bool allCameras = false;     // MIPT_CAMERAS=all: Camera "orthographic" and "environment" are built instead of reported
     int nMovingShapes = 0;
     std::vector<std::string> instanceNames;   // one per ObjectInstance call that created something, in file order
     bool expandInstances = false;

@@ -163,6 +163,9 @@ Transform Perspective(float fov, float n, float f) {
     return Scale(invTan, invTan, 1) * Transform(proj);
 }
 
+// Orthographic projection of z in [n, f] onto [0, 1] (transform.cpp:299-301).
+Transform Orthographic(float n, float f) { return Scale(1, 1, 1 / (f - n)) * Translate(Vec3(0, 0, -n)); }
+
 // Order-sensitive details of Decompose kept: the iteration averages all sixteen entries, measures the change as the largest
 // row sum of absolute differences over the upper 3x3, stops after 100 rounds or when that float is no longer above the
 // double .0001; the quaternion comes from the trace branch when the trace is positive and from the largest diagonal entry

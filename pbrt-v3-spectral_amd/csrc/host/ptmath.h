@@ -199,6 +199,7 @@ Transform Scale(float x, float y, float z);
 Transform Rotate(float theta, const Vec3 &axis);
 Transform LookAt(const Vec3 &pos, const Vec3 &look, const Vec3 &up, bool *degenerate);
 Transform Perspective(float fov, float n, float f);
+Transform Orthographic(float n, float f);
 
 // One member of an AnimatedTransform, taken apart as its constructor does (transform.cpp:396-411 through Decompose,
 // 1103-1142): M = T R S with T the translation column, R the rotation the polar iteration R <- (R + R^-T) / 2 settles on,

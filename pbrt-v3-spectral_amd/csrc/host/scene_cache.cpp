@@ -162,7 +162,7 @@ HostScene *LoadSceneCache(const std::string &path, std::string *err) {
                       s->envStore.size() == d.n_envmaps && s->mipStore.size() == d.n_mipmaps && d.sampler.n_dims >= 0 && (int)s->primes.size() == d.sampler.n_dims &&
                       s->primeSums.size() == s->primes.size() && s->perms.size() == d.sampler.n_perms &&
                       (s->primMeta.empty() || s->primMeta.size() == d.n_prims) && s->namedMaterialIds.size() == s->namedMaterialNames.size() &&
-                      s->lensStore.size() == (d.camera_type == MI_CAMERA_REALISTIC ? 1u : 0u) && (d.camera_type == MI_CAMERA_PERSPECTIVE || d.camera_type == MI_CAMERA_REALISTIC) &&
+                      s->lensStore.size() == (d.camera_type == MI_CAMERA_REALISTIC ? 1u : 0u) && d.camera_type >= MI_CAMERA_PERSPECTIVE && d.camera_type <= MI_CAMERA_ENVIRONMENT &&
                       (s->lensStore.empty() || (s->lensStore[0].n_elements >= 1 && s->lensStore[0].n_elements <= MI_MAX_LENS_ELEMENTS));
     if (consistent) {   // light-selection tables (mi_lightdistrib): UNIFORM / POWER carry one distribution, SPATIAL none (built on the device)
         if (d.n_lights == 0 || d.light_distrib.type == MI_LD_SPATIAL) consistent = s->ldFunc.empty() && s->ldCdf.empty() && s->ldFuncInt.empty();

@@ -164,8 +164,11 @@ void CreateRealisticCamera(Api &a, const ParamSet &ps, const int fullRes[2], flo
 }
 
 // CreatePerspectiveCamera, perspective.cpp:235-285; ProjectiveCamera ctor camera.h:91-112. Writes d->camera and d->camera_type.
+// MIPT_CAMERAS=all: CreateOrthographicCamera (orthographic.cpp:123-164) and CreateEnvironmentCamera (environment.cpp:107-158)
+// besides; they read the shutter, the frame and the screen window as the perspective camera does.
 void CreateCamera(Api &a, const int fullRes[2], float filmDiagonal, mi_scene_desc *d) {
-    if (a.cameraName != "perspective" && a.cameraName != "realistic")
+    const bool ortho = a.allCameras && a.cameraName == "orthographic", env = a.allCameras && a.cameraName == "environment";
+    if (a.cameraName != "perspective" && a.cameraName != "realistic" && !ortho && !env)
         a.Err("Camera \"" + a.cameraName + "\" is outside the hot-path scope (SURVEY 2 row 25); using perspective.");
     const ParamSet &ps = a.cameraParams;
     mi_camera &cam = d->camera;
@@ -189,6 +192,8 @@ void CreateCamera(Api &a, const int fullRes[2], float filmDiagonal, mi_scene_des
                                Scale(1 / (screen[1] - screen[0]), 1 / (screen[2] - screen[3]), 1) *
                                Translate(Vec3(-screen[0], -screen[3], 0));
     Transform rasterToScreen = Inverse(screenToRaster);
+    // (OrthographicCamera: ProjectiveCamera(CameraToWorld, Orthographic(0, 1), ...), orthographic.h:57-59; "fov" is not read)
+    if (ortho) cameraToScreen = Orthographic(0, 1);
     Transform rasterToCamera = Inverse(cameraToScreen) * rasterToScreen;
     std::memcpy(cam.raster_to_camera, rasterToCamera.m.m, sizeof(float) * 16);
     std::memcpy(cam.camera_to_world, a.cameraToWorld.m.m, sizeof(float) * 16);
@@ -203,6 +208,17 @@ void CreateCamera(Api &a, const int fullRes[2], float filmDiagonal, mi_scene_des
     cam.shutter_open = shutteropen;
     cam.shutter_close = shutterclose;
     d->camera_type = MI_CAMERA_PERSPECTIVE;
+    d->env_ipd = 0.f; d->env_pole_merge_to = 90.f; d->env_pole_merge_from = 90.f; d->env_convergence_distance = kInfinity;
+    if (ortho) d->camera_type = MI_CAMERA_ORTHOGRAPHIC;
+    if (env) {   // "lensradius" and "focaldistance" are parsed and unused (environment.cpp:153-154): no lens dimensions are evaluated
+        d->camera_type = MI_CAMERA_ENVIRONMENT;
+        cam.lens_radius = 0.f;
+        cam.focal_distance = ps.FindOneFloat("focaldistance", 1e30f);
+        d->env_ipd = ps.FindOneFloat("ipd", 0.f);
+        d->env_pole_merge_to = ps.FindOneFloat("poleMergeAngleTo", 90.f);
+        d->env_pole_merge_from = ps.FindOneFloat("poleMergeAngleFrom", 90.f);
+        d->env_convergence_distance = ps.FindOneFloat("convergencedistance", kInfinity);
+    }
     if (a.cameraName == "realistic") CreateRealisticCamera(a, ps, fullRes, filmDiagonal, d);
     if (a.cameraToWorld.HasScale()) a.Warn("Scaling detected in world-to-camera transformation!");
 }
