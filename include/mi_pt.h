@@ -634,6 +634,13 @@ int mi_pt_shade_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *blocks);
  * the queue; rays: what they traced (= entries); resolve_skipped: dark entries that the resolve kernel of the MIS queue
  * met and skipped -- 0 for such a scene, the dark rays of the others, which keep one queue and launch nothing here. */
 int mi_pt_dark_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *entries, uint64_t *rays, uint64_t *resolve_skipped);
+/* The traversal stacks of the last render or mi_pt_trace_wavefront call, summed over the sub-renderers and over every k_trav
+ * launch of it: out[0] = the entries pushed in all, out[1] = those of them stored beyond the part of a lane's stack that
+ * lives in LDS (MIPT_STACK_LDS entries, 12 by default), i.e. in private memory. A wide-4 record's children are pushed by
+ * visiting rank while a lane stays inside the LDS part and one after the other once it leaves it; out[1] > 0 says that
+ * rays of the call took the second way. mi_pt_trace_wavefront runs on the first sub-renderer and clears the counts of the
+ * others, so after it the sums are that call's alone. */
+int mi_pt_trav_stack_stats(mi_pt *pt, uint64_t out[2]);
 void mi_pt_destroy(mi_pt *pt);
 const char *mi_pt_last_error(void);
 

@@ -334,6 +334,8 @@ def hip_lib():
             lib.mi_pt_shade_launch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         if hasattr(lib, "mi_pt_dark_launch_stats"):
             lib.mi_pt_dark_launch_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4
+        if hasattr(lib, "mi_pt_trav_stack_stats"):
+            lib.mi_pt_trav_stack_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.mi_pt_shade_plan.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32,
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -611,6 +613,13 @@ class PathIntegrator:
         fn = hip_lib().mi_pt_trace_wavefront_timed if rays.shape[1] == 8 else hip_lib().mi_pt_trace_wavefront   # (rays [n, 8]: a time per ray)
         _check(fn(self._h, _fptr(rays), n, int(mode), _fptr(hits), _fptr(extra)), "mi_pt_trace_wavefront")
         return hits, extra.view(np.int32)
+
+    def trav_stack_stats(self):
+        """(pushed, beyond_lds) of the traversal stacks in the last render or trace_wavefront call (mi_pt_trav_stack_stats):
+        the entries k_trav pushed in all, and those of them that went past the stack's LDS part into private memory."""
+        v = (C.c_uint64 * 2)()
+        _check(hip_lib().mi_pt_trav_stack_stats(self._h, v), "mi_pt_trav_stack_stats")
+        return int(v[0]), int(v[1])
 
     def light_distribution(self):
         """The spatial light-selection tables built at create: (func [nz, ny, nx, n_lights], funcInt [nz, ny, nx])."""

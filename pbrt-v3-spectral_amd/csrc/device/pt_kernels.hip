@@ -257,8 +257,10 @@ struct alignas(128) DevStats {
     // the dark MIS rays (mi_pt_dark_launch_stats): rays k_trav<4> traced, entries its launches found in Pool::darkQ, and
     // entries of Pool::misQ that k_resolve_mis skipped as dark (scenes without the queue of their own)
     unsigned long long darkRays, darkEntries, misDarkSeen;
+    // the traversal stacks (mi_pt_trav_stack_stats): entries k_trav pushed, and those of them beyond the LDS part
+    unsigned long long stackPushed, stackBeyondLds;
 };
-static_assert(sizeof(DevStats) == 128, "a stripe of the statistics is one 128-B line");
+static_assert(sizeof(DevStats) == 256, "a stripe of the statistics is two 128-B lines of its own");
 struct alignas(128) DevCursor {
     unsigned int v;
 };
@@ -476,6 +478,100 @@ DEV void StackPop(TravSpill &sp, int lane, int &n, int *node, int *meta, float *
         *node = nd; *meta = mt; *tmin = tm;
     }
 }
+// ---- where a wide-4 record's hit children go (OpenNode<4>). `perm` holds the slot visited k-th at bits 2k..2k+1 and `hm`
+// the slots whose boxes are hit. The first hit slot in visiting order is taken; the others go to the stack so that they pop
+// in that order: the last visited lowest. So the place of a slot above the stack pointer is the number of hit slots visited
+// AFTER it -- its rank --, which needs no other slot's values: the slots after slot s are a function of `perm` alone (four
+// 4-bit masks, LaterMasks), the rank is a population count, and the slot whose rank is the highest is the one taken.
+constexpr unsigned ANY_HIT_PERM = 0xE4u;   // the record's own order: slot k is visited k-th
+constexpr unsigned LaterMasks(unsigned perm) {   // bits 4s..4s+3: the slots visited after slot s
+    unsigned m = 0;
+    for (int k = 0; k < 4; ++k) {
+        unsigned later = 0;
+        for (int j = k + 1; j < 4; ++j) later |= 1u << ((perm >> (2 * j)) & 3u);
+        m |= later << (4 * ((perm >> (2 * k)) & 3u));
+    }
+    return m;
+}
+constexpr unsigned PermOf(unsigned laterMasks) {   // the order byte again: the slot with 3 - k slots after it is visited k-th
+    unsigned perm = 0;
+    for (int s = 1; s < 4; ++s) perm |= (unsigned)s << (2 * (3 - __builtin_popcount((laterMasks >> (4 * s)) & 0xfu)));
+    return perm;
+}
+constexpr int RankOf(unsigned laterMasks, unsigned hm, int s) { return __builtin_popcount(hm & (laterMasks >> (4 * s)) & 0xfu); }
+constexpr int RankOfAnyHit(unsigned hm, int s) { return __builtin_popcount((hm & 0xfu) >> (s + 1)); }   // = RankOf(LaterMasks(ANY_HIT_PERM), hm, s)
+// A compile-time model of both formulations: the slot taken (-1: none) and the slots the stack receives, lowest first.
+struct PushModel {
+    int taken = -1, n = 0;
+    int at[4] = {-1, -1, -1, -1};
+};
+constexpr PushModel ModelPushLoop(unsigned perm, unsigned hm) {   // the sequential loop (OpenNode's PushInOrder)
+    PushModel m;
+    for (int k = 3; k >= 0; --k) {
+        const int sl = (int)((perm >> (2 * k)) & 3u);
+        if ((hm >> sl) & 1u) {
+            if (m.taken >= 0) m.at[m.n++] = m.taken;
+            m.taken = sl;
+        }
+    }
+    return m;
+}
+constexpr PushModel ModelPushRank(unsigned perm, unsigned hm, bool anyHit) {   // the rank stores
+    PushModel m;
+    const int top = __builtin_popcount(hm) - 1;
+    for (int s = 0; s < 4; ++s) {
+        if (!((hm >> s) & 1u)) continue;
+        const int rank = anyHit ? RankOfAnyHit(hm, s) : RankOf(LaterMasks(perm), hm, s);
+        if (rank == top) m.taken = s;
+        else m.at[rank] = s;
+    }
+    m.n = top > 0 ? top : 0;
+    return m;
+}
+constexpr bool IsSlotPermutation(unsigned perm) {
+    unsigned seen = 0;
+    for (int k = 0; k < 4; ++k) seen |= 1u << ((perm >> (2 * k)) & 3u);
+    return seen == 0xfu;
+}
+constexpr bool PushModelsAgree(bool anyHit) {
+    int perms = 0;
+    for (unsigned perm = 0; perm < 256; ++perm) {
+        if (anyHit ? perm != ANY_HIT_PERM : !IsSlotPermutation(perm)) continue;
+        ++perms;
+        if (PermOf(LaterMasks(perm)) != perm) return false;
+        for (unsigned hm = 0; hm < 16; ++hm) {
+            const PushModel a = ModelPushLoop(perm, hm), b = ModelPushRank(perm, hm, anyHit);
+            if (a.taken != b.taken || a.n != b.n) return false;
+            for (int i = 0; i < 4; ++i) if (a.at[i] != b.at[i]) return false;
+        }
+    }
+    return perms == (anyHit ? 1 : 24);
+}
+static_assert(PushModelsAgree(false), "closest hit: for the 24 visiting orders x 16 hit masks the rank stores leave the slot taken and the stack as the sequential loop does");
+static_assert(PushModelsAgree(true), "any hit (the record's own order): the rank stores leave the slot taken and the stack as the sequential loop does");
+// The closest-hit kernels read a record's four masks from a table in LDS (256 x 16 bits, filled at kernel entry by
+// FillLaterTable, thread t entry t): one ds_read as soon as the order byte is known, ahead of the box arithmetic.
+DEV unsigned short (&LaterTable())[256] {
+    __shared__ unsigned short table[256];
+    return table;
+}
+DEV void FillLaterTable() {
+    static_assert(BLOCK >= 256, "one thread per entry of the table");
+    if (threadIdx.x < 256) LaterTable()[threadIdx.x] = (unsigned short)LaterMasks(threadIdx.x);
+    __syncthreads();
+}
+// What each lane of k_trav pushed (mi_pt_trav_stack_stats): [0] entries in all, [1] entries at places beyond the stack's LDS
+// part. A word per lane and count in LDS, added to without a result (k_trav's hot instances have no register to spare for
+// them); the kernel clears its lanes' words at entry and adds them to the statistics once, at its end.
+DEV unsigned (&PushCounts())[2][BLOCK] {
+    __shared__ unsigned counts[2][BLOCK];
+    return counts;
+}
+template <bool COUNTED>
+DEV void CountPushes(int lane, int which, unsigned n) {
+    if constexpr (COUNTED) __hip_atomic_fetch_add(&PushCounts()[which][lane], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // Open interior node `cur`: test its children's boxes, take the first one hit in the reference's visiting order, push the
 // others (with their entry distances) so that they pop in that order. Returns whether a child was taken.
 //
@@ -487,7 +583,15 @@ DEV void StackPop(TravSpill &sp, int lane, int &n, int *node, int *meta, float *
 // is monotone), and the entry-distance re-validation at pop time is the only tMax-dependent part of the test. So the lane
 // enters the same leaves in the same order against the same tMax as the BVH2 traversal -- closest hits, equal-t ties and
 // the count of primitive tests are unchanged -- with half the dependent node fetches per ray.
-template <int W, bool TMIN = true, bool FAST = false>
+//
+// The pushes of a W = 4 record (KTRAV: the caller is k_trav, which filled LaterTable and keeps PushCounts; the per-ray routines
+// compute the masks in registers and count nothing).
+// A lane whose entries all stay inside the stack's LDS part -- sp + hit children - 1 <= STACK_LDS -- stores each hit slot that
+// is not the one taken at the place its rank gives: predicated LDS stores from the slot's own registers, one depth test and
+// one update of sp per record. A lane that would cross into TravSpill takes the sequential loop (StackPush with its two store
+// paths); a wave pays for both only in passes where one of its lanes is that deep. Either way the stack holds the same
+// entries at the same places (PushModelsAgree).
+template <int W, bool TMIN = true, bool FAST = false, bool KTRAV = false>
 DEV bool OpenNode(const float4 *__restrict__ wnodes, int cur, const RayCtx &r, float tMax, TravSpill &spill, int lane, int &sp,
                   int *tkChild, int *tkMeta, unsigned &nodeCount) {
     if constexpr (W == 2) {
@@ -509,7 +613,11 @@ DEV bool OpenNode(const float4 *__restrict__ wnodes, int cur, const RayCtx &r, f
         const float tS = negAxis ? tL : tR;
         if (hitF) {
             *tkChild = chF; *tkMeta = mtF;
-            if (hitS) StackPush<TMIN>(spill, lane, sp, chS, mtS, tS);
+            if (hitS) {
+                CountPushes<KTRAV>(lane, 0, 1u);
+                if (sp >= STACK_LDS) CountPushes<KTRAV>(lane, 1, 1u);
+                StackPush<TMIN>(spill, lane, sp, chS, mtS, tS);
+            }
             return true;
         }
         if (hitS) { *tkChild = chS; *tkMeta = mtS; return true; }
@@ -520,6 +628,19 @@ DEV bool OpenNode(const float4 *__restrict__ wnodes, int cur, const RayCtx &r, f
         const unsigned c01 = __float_as_uint(q7.x), c23 = __float_as_uint(q7.y);
         const int cnt0 = (int)(c01 & 0xffffu), cnt1 = (int)(c01 >> 16), cnt2 = (int)(c23 & 0xffffu), cnt3 = (int)(c23 >> 16);
         const bool have1 = cnt1 != 0xffff, have2 = cnt2 != 0xffff, have3 = cnt3 != 0xffff;
+        // (an any-hit ray -- TMIN = false -- may take the children in any order: whether something occludes it does not
+        // depend on it, so it takes them as they lie in the record and skips the octant's visiting order: shadow launches -6 %)
+        // The octant's order byte is taken out of the record here, once, while q7 is in registers, and its masks are asked
+        // for at once: both are in hand when the box tests are through.
+        unsigned later = 0;
+        if constexpr (TMIN) {
+            const int oct = r.Octant();
+            const unsigned ordWord = (oct & 4) ? __float_as_uint(q7.w) : __float_as_uint(q7.z);
+            unsigned perm = (ordWord >> (8 * (oct & 3))) & 0xffu;
+            asm volatile("" : "+v"(perm));   // (pins the byte: otherwise the order word is loaded again behind the box tests)
+            if constexpr (KTRAV) later = LaterTable()[perm];
+            else later = LaterMasks(perm);
+        }
         float t0, t1 = 0, t2 = 0, t3 = 0;
         bool h0, h1, h2, h3;
         if constexpr (FAST) {   // (every walking lane's reciprocal direction is finite: the caller asked the wave)
@@ -535,18 +656,32 @@ DEV bool OpenNode(const float4 *__restrict__ wnodes, int cur, const RayCtx &r, f
         }
         nodeCount += 1u + (have1 ? 1u : 0u) + (have2 ? 1u : 0u) + (have3 ? 1u : 0u);
         const unsigned hm = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+        if constexpr (TMIN && KTRAV) asm volatile("" : "+v"(later));   // (the table read is issued above, not in the branch below)
         if (hm == 0u) return false;
-        // (an any-hit ray -- TMIN = false -- may take the children in any order: whether something occludes it does not
-        // depend on it, so it takes them as they lie in the record and skips the octant's visiting order: shadow launches -6 %)
-        unsigned perm = 0xE4u;   // slot visited k-th at bits 2k..2k+1
-        if constexpr (TMIN) {
-            const int oct = r.Octant();
-            const unsigned ordWord = (oct & 4) ? __float_as_uint(q7.w) : __float_as_uint(q7.z);
-            perm = (ordWord >> (8 * (oct & 3))) & 0xffu;
-        }
         const int l0 = __float_as_int(q6.x), l1 = __float_as_int(q6.y), l2 = __float_as_int(q6.z), l3 = __float_as_int(q6.w);
+        const int top = __builtin_popcount(hm) - 1;   // entries to push
+        CountPushes<KTRAV>(lane, 0, (unsigned)top);
+        if (sp + top <= STACK_LDS) {
+            const int k0 = TMIN ? RankOf(later, hm, 0) : RankOfAnyHit(hm, 0), k1 = TMIN ? RankOf(later, hm, 1) : RankOfAnyHit(hm, 1);
+            const int k2 = TMIN ? RankOf(later, hm, 2) : RankOfAnyHit(hm, 2), k3 = TMIN ? RankOf(later, hm, 3) : RankOfAnyHit(hm, 3);
+            TravLdsT<TMIN> &lds = TravStack<TMIN>();
+            int *nodeAt = &lds.node[sp][lane], *metaAt = &lds.meta[sp][lane];   // place `sp` of the lane; rank k lies k rows above
+            float *tminAt = &lds.tmin[TMIN ? sp : 0][lane];
+            if (h0 && k0 != top) { nodeAt[k0 * BLOCK] = l0; metaAt[k0 * BLOCK] = cnt0; if constexpr (TMIN) tminAt[k0 * BLOCK] = t0; }
+            if (h1 && k1 != top) { nodeAt[k1 * BLOCK] = l1; metaAt[k1 * BLOCK] = cnt1; if constexpr (TMIN) tminAt[k1 * BLOCK] = t1; }
+            if (h2 && k2 != top) { nodeAt[k2 * BLOCK] = l2; metaAt[k2 * BLOCK] = cnt2; if constexpr (TMIN) tminAt[k2 * BLOCK] = t2; }
+            if (h3 && k3 != top) { nodeAt[k3 * BLOCK] = l3; metaAt[k3 * BLOCK] = cnt3; if constexpr (TMIN) tminAt[k3 * BLOCK] = t3; }
+            sp += top;
+            const bool tk0 = h0 && k0 == top, tk1 = h1 && k1 == top, tk2 = h2 && k2 == top;   // (one hit slot has the highest rank)
+            *tkChild = tk0 ? l0 : (tk1 ? l1 : (tk2 ? l2 : l3));
+            *tkMeta = tk0 ? cnt0 : (tk1 ? cnt1 : (tk2 ? cnt2 : cnt3));
+            return true;
+        }
+        // PushInOrder, for a lane whose entries reach beyond the LDS part.
         // from the last visited to the first: a slot that is hit displaces the candidate found so far onto the stack, so the
         // stack receives the later ones first and the first one in order stays in hand
+        CountPushes<KTRAV>(lane, 1, (unsigned)(sp + top - (sp > STACK_LDS ? sp : STACK_LDS)));
+        const unsigned perm = TMIN ? PermOf(later) : ANY_HIT_PERM;   // (the masks were kept across the box tests, the byte was not)
         int cand = -1;
 #pragma unroll
         for (int k = 3; k >= 0; --k) {
@@ -778,6 +913,8 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
     const unsigned travChunk = (total >= (1u << 23)) ? 2u * (unsigned)TRAV_CHUNK : (unsigned)TRAV_CHUNK;
     const float4 *__restrict__ primTri = s.primTri;
     unsigned nodeCount = 0, triCount = 0, rayCount = 0;
+    PushCounts()[0][lane] = 0u; PushCounts()[1][lane] = 0u;   // (the lane's own words: no barrier)
+    if constexpr (W == 4 && !ANY) FillLaterTable();
     bool has = false;
     uint32_t slot = 0;
     unsigned myEntry = 0;   // MODE 1, 2: the ray's place in its queue (the answer goes beside the queue: shadowQ[n + myEntry], misQ[n + 2 myEntry])
@@ -798,7 +935,7 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
     triRay.kz = 2; triRay.Sx = triRay.Sy = 0; triRay.Sz = 1;
     bool exhausted = false;
 #ifdef MIPT_TRAV_STATS
-    unsigned long long dbgPasses = 0, dbgHas = 0, dbgWalk = 0, dbgWalkPasses = 0, dbgTriPasses = 0, dbgTri = 0;
+    unsigned long long dbgPasses = 0, dbgHas = 0, dbgWalk = 0, dbgWalkPasses = 0, dbgTriPasses = 0, dbgTri = 0, dbgDeepPasses = 0;
 #endif
     unsigned chunkNext = 0, chunkEnd = 0;  // wave-uniform: the range of the work list this wave reserved
     while (true) {
@@ -886,11 +1023,14 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
             bool needPop = false, got = false, finished = false;
             int tkChild = 0, tkMeta = 0;
             if (walking) {
-                if (__any(r.slow)) got = OpenNode<W, !ANY, false>(s.wnodes, st.cur, r, tMax, spill, lane, st.sp, &tkChild, &tkMeta, nodeCount);
-                else got = OpenNode<W, !ANY, W == 4>(s.wnodes, st.cur, r, tMax, spill, lane, st.sp, &tkChild, &tkMeta, nodeCount);
+                if (__any(r.slow)) got = OpenNode<W, !ANY, false, true>(s.wnodes, st.cur, r, tMax, spill, lane, st.sp, &tkChild, &tkMeta, nodeCount);
+                else got = OpenNode<W, !ANY, W == 4, true>(s.wnodes, st.cur, r, tMax, spill, lane, st.sp, &tkChild, &tkMeta, nodeCount);
                 needPop = !got;
                 st.cur = -1;
             }
+#ifdef MIPT_TRAV_STATS
+            if (__any(walking && got && st.sp > STACK_LDS)) ++dbgDeepPasses;   // (a lane of the wave took the sequential pushes)
+#endif
             const bool triPass = nLeaf > 0 && (nLeaf >= TRI_BATCH || !anyWalk);   // (wave-uniform)
             // ---- cooperative leaf test. A lane waiting at a triangles-only leaf hands up to COOP_KMAX of its (ray, triangle)
             // pairs to the wave: the pairs of all waiting lanes are numbered owner by owner, lane w tests pair w with the
@@ -999,6 +1139,8 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
                 if (INST && (pf & PRIM_FLAG_INSTANCE)) {
                     // TransformedPrimitive::Intersect[P]: the ray in the instance's space, then the object's BVH from its root
                     const int k = __float_as_int(primTri[3 * prim + 1].w);
+                    CountPushes<true>(lane, 0, 1u);
+                    if (st.sp >= STACK_LDS) CountPushes<true>(lane, 1, 1u);
                     StackPush<!ANY>(spill, lane, st.sp, leafOff, -(leafCnt + 1), tMax);
                     Ray ir;
                     if constexpr (MOTION) {
@@ -1124,14 +1266,16 @@ k_trav(DScene s, Pool pool, DevCounters *ctr) {
     }
 #ifdef MIPT_TRAV_STATS
     if (blockIdx.x == 7 && threadIdx.x == 0 && total > 1000000)
-        printf("TRAVSTAT mode %d total %u passes %llu has/pass %.1f walkPasses %llu walk/walkPass %.1f triPasses %llu tri/triPass %.1f\n", MODE, total, dbgPasses,
-               (double)dbgHas / dbgPasses, dbgWalkPasses, (double)dbgWalk / (dbgWalkPasses ? dbgWalkPasses : 1), dbgTriPasses, (double)dbgTri / (dbgTriPasses ? dbgTriPasses : 1));
+        printf("TRAVSTAT mode %d total %u passes %llu has/pass %.1f walkPasses %llu walk/walkPass %.1f triPasses %llu tri/triPass %.1f deepPushPasses %llu\n", MODE, total, dbgPasses,
+               (double)dbgHas / dbgPasses, dbgWalkPasses, (double)dbgWalk / (dbgWalkPasses ? dbgWalkPasses : 1), dbgTriPasses, (double)dbgTri / (dbgTriPasses ? dbgTriPasses : 1), dbgDeepPasses);
 #endif
     DevStats &st8 = Stats(ctr);
     if (MODE == 1) CountAdd(&st8.shadowRays, rayCount);
     else CountAdd(&st8.regularRays, rayCount);
     CountAdd(&st8.nodesVisited, nodeCount);
     CountAdd(&st8.triTests, triCount);
+    CountAdd(&st8.stackPushed, PushCounts()[0][lane]);
+    CountAdd(&st8.stackBeyondLds, PushCounts()[1][lane]);
     if (MODE == 0) { CountAdd(&st8.extendNodes, nodeCount); CountAdd(&st8.extendTris, triCount); CountAdd(&st8.extendRays, rayCount); }
     if (DARK) {   // (mi_pt_dark_launch_stats: what the launch found in its queue against what it traced)
         CountAdd(&st8.darkRays, rayCount);
@@ -3761,6 +3905,7 @@ struct SubRenderer {
     bool darkTimed[2] = {false, false};  // evDark[k] holds a launch whose time is not in t[5] yet
     unsigned long long darkSeq = 0;      // launches on darkStream so far (picks the set)
     unsigned long long darkLaunches = 0; // k_trav<4> launches of the last render
+    unsigned long long stackPushed = 0, stackBeyondLds = 0;   // mi_pt_trav_stack_stats: of the last render or mi_pt_trace_wavefront call
 };
 
 // The k_shade instances by their index in MIPT_SHADE_INSTANCES.
@@ -4991,6 +5136,16 @@ int QueryQueueOccupancy(mi_pt *pt) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kResolve[mode][pt->hasInstances ? 1 : 0], BLOCK, 0) != hipSuccess || nb < 1) { g_err = "occupancy query failed"; return MI_ERR_HIP; }
         pt->resolveBlocksPerCU[mode] = nb;
     }
+#ifdef MIPT_TRAV_STATS
+    {   // the traversal kernels of the scene: the grids above count on 4 blocks per CU closest-hit, 5 any-hit
+        const SceneKernel ks[5] = {TravKernel<0>(pt), TravKernel<1>(pt), TravKernel<2>(pt), TravKernel<3>(pt), TravKernel<4>(pt)};
+        for (int mode = 0; mode < 5; ++mode) {
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)ks[mode], BLOCK, 0) != hipSuccess) nb = -1;
+            fprintf(stderr, "TRAVSTAT k_trav<%d> blocks per CU %d\n", mode, nb);
+        }
+    }
+#endif
     return MI_OK;
 }
 
@@ -5260,6 +5415,8 @@ static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, in
     HarvestDark(sub, 0); HarvestDark(sub, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(&sub.result, sub.ctr, sizeof(DevCounters), hipMemcpyDeviceToHost));
+    sub.stackPushed = sub.stackBeyondLds = 0;
+    for (const DevStats &r : sub.result.stats) { sub.stackPushed += r.stackPushed; sub.stackBeyondLds += r.stackBeyondLds; }
     return MI_OK;
 }
 
@@ -5597,6 +5754,13 @@ int mi_pt_dark_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *entries, ui
     return MI_OK;
 }
 
+int mi_pt_trav_stack_stats(mi_pt *pt, uint64_t out[2]) {
+    if (!pt || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    out[0] = out[1] = 0;
+    for (const SubRenderer &sub : pt->subs) { out[0] += sub.stackPushed; out[1] += sub.stackBeyondLds; }
+    return MI_OK;
+}
+
 int mi_pt_shade_plan(const mi_scene_desc *d, int32_t *material_class, uint32_t material_capacity, int32_t *class_id,
                      int32_t *class_instance, int32_t *class_lobes, uint32_t *class_types, uint32_t class_capacity,
                      uint32_t *n_classes, uint32_t *hot) {
@@ -5797,6 +5961,10 @@ static int TraceWavefront(mi_pt *pt, const float *rays, int stride, uint32_t n, 
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(hits, dh.p, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
     if (extra) HIPCHK(hipMemcpy(extra, dx.p, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<DevStats> stripes(STAT_STRIPES);   // (the stack statistics of this call; the counters of the last render stay as they are)
+    HIPCHK(hipMemcpy(stripes.data(), sub.ctr, sizeof(DevStats) * STAT_STRIPES, hipMemcpyDeviceToHost));
+    for (SubRenderer &other : pt->subs) other.stackPushed = other.stackBeyondLds = 0;   // (the call ran on the first sub-renderer alone)
+    for (const DevStats &r : stripes) { sub.stackPushed += r.stackPushed; sub.stackBeyondLds += r.stackBeyondLds; }
     return MI_OK;
 }
 int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra) { return TraceWavefront(pt, rays, 7, n, mode, hits, extra); }
