@@ -36,21 +36,27 @@ cli: $(PKG)/pbrt_amd
 $(PKG)/libmipt_host.so: $(HOSTSRC) $(wildcard $(PKG)/csrc/host/*.h) $(wildcard $(PKG)/csrc/host/*.inc) include/mi_pt.h include/mi_scene.h
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOSTSRC) -ldl -lz
 
-# pt_kernels.hip is compiled six times side by side (MIPT_PART: the other kernels + host code, the k_shade instances in
-# four groups -- 1, 2, 3, 5 --, and the BSDF probe, 4), hlbvh.hip once; `make -j` runs them together.
-DEVDEPS  := $(wildcard $(PKG)/csrc/device/*.hip) $(wildcard $(PKG)/csrc/device/*.h) include/mi_pt.h
-DEVOBJ   := $(BUILD)/pt_part0.o $(BUILD)/pt_part1.o $(BUILD)/pt_part2.o $(BUILD)/pt_part3.o $(BUILD)/pt_part4.o $(BUILD)/pt_part5.o $(BUILD)/hlbvh.o
-$(BUILD)/pt_part%.o: $(DEVDEPS) Makefile
+# libmipt_hip.so: pt_kernels.hip, which holds every kernel, is compiled six times side by side (MIPT_PART: 0 the kernels
+# other than k_shade, their selection and the probes; the k_shade instances in four groups -- 1, 2, 3, 5 --; the BSDF probe, 4);
+# pt_create.hip and pt_render.hip, the host code of the mi_pt_* ABI, and hlbvh.hip once each; `make -j` runs them together.
+# HIPEXTRA reaches every unit: the host units read some of the tuning macros (pt_pool.h). A unit depends on its own source
+# and on the headers, so an edit to pt_create.hip or pt_render.hip rebuilds that object and the link, an edit to a header or
+# to pt_kernels.hip every unit that includes it.
+DEVDIR   := $(PKG)/csrc/device
+DEVHDRS  := $(wildcard $(DEVDIR)/*.h) $(PKG)/csrc/host/noise_perm.inc include/mi_pt.h
+DEVOBJ   := $(BUILD)/pt_part0.o $(BUILD)/pt_part1.o $(BUILD)/pt_part2.o $(BUILD)/pt_part3.o $(BUILD)/pt_part4.o $(BUILD)/pt_part5.o \
+            $(BUILD)/pt_create.o $(BUILD)/pt_render.o $(BUILD)/hlbvh.o
+$(BUILD)/pt_part%.o: $(DEVDIR)/pt_kernels.hip $(DEVHDRS) Makefile
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_part$*) $(HIPEXTRA) -DMIPT_PART=$* -c -o $@ $(PKG)/csrc/device/pt_kernels.hip
-$(BUILD)/hlbvh.o: $(DEVDEPS) Makefile
+	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_part$*) $(HIPEXTRA) -DMIPT_PART=$* -c -o $@ $<
+$(BUILD)/%.o: $(DEVDIR)/%.hip $(DEVHDRS) Makefile
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_hlbvh) $(HIPEXTRA) -c -o $@ $(PKG)/csrc/device/hlbvh.hip
+	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_$*) $(HIPEXTRA) -c -o $@ $<
 $(HIPLIB): $(DEVOBJ)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(DEVOBJ)
 
-# The flags of one device unit (UNIT = part0 .. part4 or hlbvh; none: the flags every unit shares), for the tools that
-# compile device code themselves (tools/isa_stats.py).
+# The flags of one unit (UNIT = part0 .. part5 or hlbvh; none, or pt_create / pt_render: the flags every unit shares), for
+# the tools that compile device code themselves (tools/isa_stats.py).
 print-hipflags:
 	@echo $(HIPFLAGS) $(HIPFLAGS_$(UNIT)) $(HIPEXTRA)
 

@@ -27,7 +27,7 @@ namespace dpt {
 #define PRIM_CLASS_SHIFT 8      /* bits 8-11: shading class of the primitive's material (15 = no BSDF) */
 
 // What the scrambled radical inverse needs of one Halton dimension, as two 16-byte loads (built at create, BuildHaltonDims in
-// pt_kernels.hip). permOffset counts uint16 entries from the table's first byte to the dimension's permutation: the
+// pt_create.hip). permOffset counts uint16 entries from the table's first byte to the dimension's permutation: the
 // permutations lie behind the records. invBase = 1.f / (float)base and tail = invBase * (float)perm[0] / (1 - invBase),
 // the two quotients that depend on the dimension alone.
 struct alignas(32) HaltonDim {
@@ -40,7 +40,7 @@ static_assert(sizeof(HaltonDim) == 32, "HaltonDim: two 16-byte loads");
 
 struct DScene {
     const float4 *nodes;
-    const float4 *wnodes;  // wide nodes (see pt_kernels.hip): bvhWidth 2 -> 64 B per BVH2 interior node (both children's boxes);
+    const float4 *wnodes;  // wide nodes (built in pt_create.hip, walked in pt_kernels.hip): bvhWidth 2 -> 64 B per BVH2 interior node (both children's boxes);
                            // bvhWidth 4 -> 128 B per two-level subtree (up to four grandchild boxes + the visit orders)
     int bvhWidth;
     // ObjectInstance as TransformedPrimitive (mi_instance): the instances, the wide record each one's tree starts at, and
@@ -62,9 +62,9 @@ struct DScene {
     const mi_light *lights;
     const int *lightPrim;        // [nLights]: the primitive whose shape an area light is (k_trav<3> leaves it out)
     int misAny;                  // MIS rays are traced as visibility queries (k_trav, MODE 3; pt_kernels.hip)
-    const float4 *lightBounds;   // [2 * nLights]: dilated world bounds of an area light's shape (dark MIS rays: see MIS_EXCL_DARK, pt_kernels.hip)
+    const float4 *lightBounds;   // [2 * nLights]: dilated world bounds of an area light's shape (dark MIS rays: see MIS_EXCL_DARK, pt_pool.h)
     uint32_t nNodes, nPrims, nLights, nMaterials;
-    uint32_t classMask;  // shading classes present in the scene (bit c), see pt_kernels.hip
+    uint32_t classMask;  // shading classes present in the scene (bit c), see pt_pool.h
     // light distribution: distribution d at func[d*nLights], cdf[d*(nLights+1)], funcInt[d]
     int ldType;
     int nVoxels[3];

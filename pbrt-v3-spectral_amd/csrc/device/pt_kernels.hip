@@ -1,5 +1,9 @@
-// pt_kernels.hip -- wavefront (Laine-style) spectral path tracer for gfx950 + the
-// mi_pt_* C ABI (include/mi_pt.h). One resident pool of path slots lives in HBM as
+// pt_kernels.hip -- wavefront (Laine-style) spectral path tracer for gfx950: the kernels and
+// device routines, the functions that pick a kernel instance for a launch (pt_select.h) and
+// the single-question probes of the mi_pt_* C ABI (include/mi_pt.h), each entry point under
+// its kernel. The rest of the ABI is host code of its own: pt_create.hip (mi_pt_create) and
+// pt_render.hip (the pool, the launches of an iteration, the render driver); pt_pool.h holds
+// what both sides read. One resident pool of path slots lives in HBM as
 // structure-of-arrays "planes" (plane k of slot i at base + k*pool + i, so every
 // per-bin access of a wave is one coalesced 256-B transaction). One iteration is
 //
@@ -23,11 +27,9 @@
 // No MFMA: this path is latency/bandwidth bound (traversal) and VALU bound (shading).
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <thread>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -36,131 +38,25 @@
 #include "d_texture.h"
 #include "d_lens.h"
 #include "d_camera.h"
+#include "pt_host.h"
 
 using namespace dpt;
 
-// The library is built from this file six times in parallel (Makefile): MIPT_PART 0 holds everything but the shading
-// kernel's instances (host code, the other kernels), parts 1-3 and 5 hold the k_shade instances (95 % of the compile
-// time; MIPT_SHADE_INSTANCES says which), part 4 the BSDF probe's kernels and their launcher (mi_pt_bsdf_probe: test-only code, kept out of the
-// parts a render runs). Without MIPT_PART (tools/isa_stats.py without --part) everything is one translation unit.
+// This file is compiled six times in parallel (Makefile): MIPT_PART 0 holds every kernel but the shading kernel's instances,
+// with the kernel selection and the probes; parts 1-3 and 5 hold the k_shade instances (95 % of the compile
+// time; MIPT_SHADE_INSTANCES says which), part 4 the BSDF probe's kernels and their launcher (LaunchBsdfProbe: test-only code, kept out of the
+// parts a render runs). Without MIPT_PART (tools/isa_stats.py without --part) every kernel is in one translation unit.
+// MIPT_HAS_MAIN guards part 0's kernels and what names them; the library's other host code is pt_create.hip and pt_render.hip.
 #ifdef MIPT_PART
 #define MIPT_HAS_MAIN (MIPT_PART == 0)
 #else
 #define MIPT_HAS_MAIN 1
 #endif
 
-namespace dptk {   // (named: k_shade's instances are shared between the parts, so the types in its signature need linkage)
+namespace dptk {   // (the pool's types, the counters and the tuning macros that the host units read too: pt_pool.h)
 
-static thread_local std::string g_err;
-
-// Four sub-renderer streams want four hardware queues of their own; the HIP runtime maps
-// streams onto GPU_MAX_HW_QUEUES (default 4, shared with the null stream) when it
-// initialises, which happens at the first HIP call -- after this library is loaded.
-#if MIPT_HAS_MAIN
-static struct QueueEnv { QueueEnv() { setenv("GPU_MAX_HW_QUEUES", "8", 0); } } g_queueEnv;
-#endif
-#define HIPCHK(x)                                                                         \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess) {                                                           \
-            g_err = std::string(#x) + ": " + hipGetErrorString(e_);                       \
-            return MI_ERR_HIP;                                                            \
-        }                                                                                 \
-    } while (0)
-
-constexpr int BLOCK = 256;
-#ifndef MIPT_STACK_LDS
-#define MIPT_STACK_LDS 12
-#endif
-constexpr int STACK_LDS = MIPT_STACK_LDS;       // traversal stack entries (node, meta, tMin) staged in LDS per lane
-constexpr int STACK_SPILL = 64 - STACK_LDS;     // deeper entries (pbrt allows 64 in total, bvh.cpp:670)
-static_assert(STACK_LDS >= 1 && STACK_LDS <= 63 && STACK_LDS * BLOCK * 12 <= 160 * 1024, "MIPT_STACK_LDS: 1..63 entries, and the block's stack must fit the CU's LDS");
-
-// ---- float planes
-enum : int {
-    P_FILMX = 0, P_FILMY,
-    P_TENC0, P_TENC1, P_TENC2, P_TENC3,   // the ray's tMax when the k-th postponed quadric was met (closest-hit traversals)
-    P_COUNT
-};
-// Camera "realistic" only: one more float plane behind the others (a pool is allocated with FloatPlanes(scene) of them) -- the
-// weight GenerateRayDifferential returned for the slot's camera ray, which the film flush multiplies the sample by. A plane
-// and not a second evaluation at the flush: the weight is the outcome of three to five lens traces.
-constexpr int P_WEIGHT = P_COUNT;
-// ... and, in front of image textures only (DScene::lensDiff), twelve more: the camera ray's scaled differentials rxOrigin,
-// ryOrigin, rxDirection, ryDirection as LensCameraRay leaves them (they come from the offset rays' lens traces). k_generate
-// writes them, the textured k_shade instances load them where they rebuild a perspective camera's from the film position.
-constexpr int P_LENSDIFF = P_COUNT + 1, N_LENSDIFF = 12;
-// ---- float4 record planes: values that are read and written together travel in one 16-B access
-enum : int {
-    R_RAY0 = 0,   // path ray: o.xyz, tMax
-    R_RAY1,       //           d.xyz, etaScale
-    R_SH0, R_SH1, // shadow ray (tMax = 1 - ShadowEpsilon): o.xyz d.x | d.y d.z - -
-    R_MI0, R_MI1, // MIS ray: same packing
-    R_HIT,        // t, b0, b1, b2 of the last traversal (path ray, or MIS ray)
-    R_COUNT
-};
-// The two quads of a ray are neighbours in memory ([ray][slot][2]: 32 B per slot), so the pair a shading lane stores --
-// and a traversal lane loads -- falls into ONE 64-B sector instead of two planes' sectors (the memory side moves whole
-// sectors: a scattered 16-B store cost ~45 B there, PMC of round 1).
-// ---- spectral planes. A 31-bin spectrum of a slot is stored as NQ = 8 float4 "quad planes": bins
-// 4c..4c+3 of slot i at q[(set + c) * pool + i] (bin 31 is padding, kept 0 in everything that is summed or
-// tested). One 16-B access per lane moves four bins, so a spectral pass issues a quarter of the memory
-// instructions of one-float planes and -- the lanes of a shading wave hold scattered slots -- touches fewer
-// cache lines per bin.
-constexpr int NQ = 8;
-enum : int {
-    Q_L = 0,                // radiance gathered by the path
-    Q_BETA = NQ,            // throughput
-    Q_LB = 2 * NQ,          // the second line of the path's radiance (F_L_IN_B, F_CAND)
-    Q_LMIS = 3 * NQ,        // pending BSDF-sample (MIS) contribution
-    Q_COUNT = 4 * NQ,
-    Q_LCA = Q_COUNT         // Integrator "spectralpath" only: the sample's stitched bands
-};
 DEV float Get4(const float4 &v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w)); }
 DEV void Set4(float4 &v, int k, float x) { if (k == 0) v.x = x; else if (k == 1) v.y = x; else if (k == 2) v.z = x; else v.w = x; }
-// ---- int planes
-enum : int { I_HITPRIM = 0, I_PIXEL, I_SAMPLE, I_IDXLO, I_IDXHI, I_DIM /* pixel samplers only: see StateWord */, I_FLAGS, I_MISLIGHT,
-             I_NPEND, I_PEND0, I_PEND1, I_PEND2, I_PEND3,  // quadrics postponed by the traversal kernel
-             I_BAND,                                       // spectralpath: band (path number) of the camera sample
-             I_HITINST,                                    // instance the hit primitive was reached through, -1 = none (scenes with instances)
-             I_COUNT };
-constexpr int MAX_PEND = 4;
-constexpr int PEND_OVERFLOW = 0x100;  // more quadrics met than MAX_PEND: the resolve kernel re-traverses
-// ---- slot flags
-enum : int {
-    F_ALIVE = 1, F_FINISHED = 2, F_SPECULAR = 4, F_SHADOW = 8, F_MIS = 16, F_NEE = 32, F_A_ADDED = 64,
-    // The path's radiance L has two lines, Q_L and Q_LB, and this bit says which one holds it. A light sample's contribution
-    // used to wait in a line of its own until its shadow ray was resolved, and k_resolve_shadow then read it, read L and
-    // wrote L: 384 B per unoccluded ray in a kernel that does nothing else. Now k_shade writes the CANDIDATE L + contribution
-    // into the line that does not hold L (F_CAND; it has the throughput and the contribution in hand, and L costs it one
-    // more read -- none while L is still empty), and an unoccluded ray flips this bit: the resolve moves no spectrum at all.
-    F_L_IN_B = 128,
-    // A new path has L = 0 and beta = 1. Writing those 16 quads into freshly (sparsely) refilled slots cost as
-    // much as the rest of k_generate, so they stay implicit until something else is written there:
-    F_L_ZERO = 256,     // Q_L holds no value yet; it reads as 0 (0 + x == x)
-    F_BETA_ONE = 512,   // Q_BETA holds no value yet; it reads as 1 (1 * x == x)
-    F_DIFF = 1024,      // the path ray is still the camera ray: it has ray differentials (RayDifferential::hasDifferentials)
-    // F_CAND: the line that does not hold L holds L + the pending light sample's contribution (see F_L_IN_B); the shadow ray
-    // decides. F_NEE_NZ: that contribution has a non-zero bin.
-    F_CAND = 2048, F_NEE_NZ = 4096
-};
-// A DARK MIS ray has no flag: the BSDF-sampled ray is traced (the reference traces and counts it), but it cannot reach the
-// sampled area light -- it misses the dilated bounds of the light's shape: Sphere::Pdf gives every direction the cone's pdf,
-// sphere.cpp:294-310, so the estimate goes on for rays that point away from the sphere -- so its contribution is neither
-// formed nor stored in Q_LMIS and nothing reads its answer. For the state machine such an estimate has no MIS ray at all
-// (no F_MIS): the shadow ray's commit closes it (CommitShadowVerdict), or k_shade itself when there is no shadow ray either.
-// Where the live MIS rays are visibility queries (DScene::misAny) the ray goes to a queue of its own (Pool::darkQ) and
-// k_trav<4> traces it for the counters alone. In the other scenes it still goes to the MIS queue, marked in its record
-// (MIS_EXCL_DARK), k_trav<2> answers MIS_ANSWER_DARK in the queue's answer words and touches no slot, and k_resolve_mis
-// skips the entry on that word alone.
-// The I_FLAGS word carries the path's bounce count and sampler dimension beside the flags: bits 0-13 the flags above, 14-21
-// `bounces` (mi_pt_create bounds max_depth by 255), 22-31 the next sampler dimension (the Halton / Sobol' tables end at 1000 /
-// 1024 dimensions; the random sampler only counts). Three 4-byte planes used to hold them: a shading lane read and wrote
-// all three at scattered slots (~45 B each way at the memory side, PMC of round 2), k_generate stored all three per new
-// path. One word: every kernel that reads the flags has the other two for nothing. (A pixel sampler's two table counters
-// need 32 bits: they stay in the I_DIM plane.)
-constexpr int FLAG_BITS = 14, FLAG_MASK = (1 << FLAG_BITS) - 1, BOUNCE_SHIFT = 14, DIM_SHIFT = 22;
-static_assert(F_NEE_NZ < (1 << FLAG_BITS), "slot flags outgrew their field");
 DEV int LPlane(int flags) { return (flags & F_L_IN_B) ? Q_LB : Q_L; }        // the line that holds the path's L
 DEV int LOtherPlane(int flags) { return (flags & F_L_IN_B) ? Q_L : Q_LB; }   // ... and the one for the candidate
 DEV int StateWord(int flags, int bounces, int dim) { return (flags & FLAG_MASK) | ((bounces & 0xff) << BOUNCE_SHIFT) | (int)((unsigned)(dim & 0x3ff) << DIM_SHIFT); }
@@ -183,9 +79,6 @@ DEV bool RaySpanInBox(const V3 &o, const V3 &d, const float4 &bmin, const float4
     *spanLo = t0; *spanHi = t1;
     return !(t0 > t1);
 }
-constexpr unsigned MIS_EXCL_BITS = 27, MIS_EXCL_NONE = (1u << MIS_EXCL_BITS) - 1u;
-constexpr unsigned MIS_EXCL_DARK = MIS_EXCL_NONE - 1u;   // in place of the light's primitive: a dark ray (no primitive has this number, BuildLightPrims)
-constexpr unsigned MIS_ANSWER_DARK = 0x80000000u;        // bit 31 of a MIS ray's second answer word (beside the postponed quadrics): a dark ray's
 // The two words k_trav<3> reads beside a MIS ray (R_MI1.z, .w): the end tHi of the span in which the sampled light's shape can
 // be hit, and that shape's primitive | c << 27 with tLo = tHi (1 - 2^-c) at or below the span's start (c = 0: tLo = 0).
 DEV void MisSpanWords(float lo, float hi, unsigned prim, float *tHi, float *word) {
@@ -197,47 +90,6 @@ DEV void MisSpanWords(float lo, float hi, unsigned prim, float *tHi, float *word
     *word = __uint_as_float(prim | ((unsigned)c << MIS_EXCL_BITS));
 }
 
-// Shading classes: materials with the same lobe-type list share a class (ids in order of
-// first appearance, the 15th and later share class 14); class 15 holds the vertices without a
-// BSDF (escaped rays, interface primitives). A wave of k_shade works on one class only.
-constexpr int MAX_CLASSES = 16;
-constexpr int MISS_CLASS = 15;
-
-struct Pool {
-    float *f;
-    float4 *q;   // spectral quad planes
-    float4 *r;   // record planes
-    int *i;
-    uint32_t *shadowQ, *misQ;  // compacted slot indices of this iteration's shadow / MIS rays. shadowQ[n + k]: the any-hit
-                               // traversal's answer for entry k (bit 31: occluded; below it the count of postponed quadrics |
-                               // PEND_OVERFLOW) -- in queue order, so k_resolve_shadow reads it as whole lines where the
-                               // hit words of the slot planes cost it a sector each. misQ[n + 2k], [n + 2k + 1]: hit
-                               // primitive and postponed quadrics of MIS ray k, likewise (its t and barycentrics, which
-                               // k_resolve_mis rarely needs, stay in the slot's R_HIT). A dark ray's second word is
-                               // MIS_ANSWER_DARK: k_resolve_mis skips the entry without touching its slot
-    uint32_t *darkQ;           // DScene::misAny: the slots of this iteration's dark MIS rays (n entries), which then stay out of
-                               // misQ. Nothing answers them: k_trav<4> walks this queue for the counters alone, on a stream
-                               // of its own beside the next iteration (RenderSub)
-    uint32_t *extQ;            // this iteration's path rays: new camera rays from the front (coherent: consecutive
-                               // samples of a pixel), continuing paths from the back
-    uint32_t *shadeQ;          // slots to shade: MAX_CLASSES queues of n entries, one per shading class
-    uint32_t *ovfQ;            // rays whose list of postponed quadrics overflowed: 3 queues of n entries (extend / shadow / MIS)
-    uint32_t n;
-    // where (plane, slot) lies in f / i, in q and in r: the host reads single slots back through these (mi_pt_debug_path)
-    __host__ __device__ __forceinline__ size_t ScalarIndex(int plane, uint32_t slot) const { return (size_t)plane * n + slot; }
-    // a slot's 8 quads of one spectrum are one 128-B line: [spectrum][slot][quad] ([slot][spectrum][quad], the
-    // spectra of a slot in one page, measured the same)
-    __host__ __device__ __forceinline__ size_t QuadIndex(int plane, uint32_t slot) const { return (((size_t)(plane >> 3) * n + slot) << 3) + (plane & 7); }
-    __host__ __device__ __forceinline__ size_t RecordIndex(int plane, uint32_t slot) const {
-        return plane < R_HIT ? (((size_t)(plane >> 1) * n + slot) << 1) + (plane & 1) : (size_t)plane * n + slot;
-    }
-    DEV float &F(int plane, uint32_t slot) const { return f[ScalarIndex(plane, slot)]; }
-    DEV float4 &Q(int plane, uint32_t slot) const { return q[QuadIndex(plane, slot)]; }
-    // (the choice is made here once more, between two references: with it inside the index alone k_trav<2>, k_trav<3> and
-    // k_shade come out with other register assignments and one to six instructions more or fewer)
-    DEV float4 &R(int plane, uint32_t slot) const { return plane < R_HIT ? r[RecordIndex(plane, slot)] : r[ScalarIndex(plane, slot)]; }
-    DEV int &I(int plane, uint32_t slot) const { return i[ScalarIndex(plane, slot)]; }
-};
 // Ray::time of the slot's path: the camera ray's, which every ray the path spawns keeps (Interaction::SpawnRay[To] pass the
 // interaction's time on, interaction.h:64-86). A plane of its own that exists only in scenes with moving instances and is
 // read only where a ray meets an instance; elsewhere the shutter-open time, which nothing then depends on.
@@ -245,51 +97,7 @@ DEV float PathTime(const DScene &s, const Pool &pool, uint32_t slot) { return s.
 // SurfaceInteraction::instanceId of a hit reached through instance k (primitive.cpp:89; the wrapper of a moving shape: 0)
 DEV unsigned InstanceIdOf(const mi_instance &in, int k) { return in.instance_id ? in.instance_id : (in.motion ? 0u : (unsigned)k + 1u); }
 
-// Statistics are striped: STAT_STRIPES copies, each on its own 128-B line, picked by block
-// index, so the per-wave atomics of a launch do not all serialise on one L2 line; the host
-// adds the stripes up. The queue cursors cannot be striped (they hand out consecutive
-// positions); they are bumped once per block instead (BlockReserve) and sit on lines of
-// their own.
-constexpr int STAT_STRIPES = 64;
-struct alignas(128) DevStats {
-    unsigned long long cameraRays, regularRays, shadowRays, totalPaths, zeroRadiancePaths, pathLengthSum, nodesVisited,
-        triTests, badSamples, extendNodes, extendTris, extendRays;
-    // the dark MIS rays (mi_pt_dark_launch_stats): rays k_trav<4> traced, entries its launches found in Pool::darkQ, and
-    // entries of Pool::misQ that k_resolve_mis skipped as dark (scenes without the queue of their own)
-    unsigned long long darkRays, darkEntries, misDarkSeen;
-    // the traversal stacks (mi_pt_trav_stack_stats): entries k_trav pushed, and those of them beyond the LDS part
-    unsigned long long stackPushed, stackBeyondLds;
-};
-static_assert(sizeof(DevStats) == 256, "a stripe of the statistics is two 128-B lines of its own");
-struct alignas(128) DevCursor {
-    unsigned int v;
-};
-struct DevCounters {
-    DevStats stats[STAT_STRIPES];
-    alignas(128) unsigned long long nextWork;   // global work counter
-    // cleared together every iteration:
-    DevCursor alive;                    // slots alive after generate
-    DevCursor shadowCount, misCount;    // entries in Pool::shadowQ / misQ
-    DevCursor primCount, contCount;     // entries at the front / back of Pool::extQ
-    DevCursor shadeCount[MAX_CLASSES];  // entries in shading queue c
-    DevCursor travNext[3];              // work cursors of the persistent traversal kernels (extend/shadow/mis)
-    DevCursor ovfCount[3];              // entries in Pool::ovfQ (extend/shadow/mis)
-    // NOT cleared with them: the dark traversal of iteration i runs beside iteration i + 1, whose clear it must not meet.
-    // Whoever launches k_trav<4> clears both behind it, on the kernel's stream.
-    DevCursor darkCount, darkNext;      // entries in Pool::darkQ, and the work cursor of k_trav<4>
-};
-constexpr size_t ITER_CLEAR_BYTES = sizeof(DevCursor) * (5 + MAX_CLASSES + 3 + 3);
-constexpr size_t DARK_CLEAR_BYTES = sizeof(DevCursor) * 2;
-static_assert(offsetof(DevCounters, darkCount) >= offsetof(DevCounters, alive) + ITER_CLEAR_BYTES && offsetof(DevCounters, darkNext) == offsetof(DevCounters, darkCount) + sizeof(DevCursor),
-              "the dark cursors lie behind the block that every iteration clears, side by side");
 DEV DevStats &Stats(DevCounters *ctr) { return ctr->stats[blockIdx.x & (STAT_STRIPES - 1)]; }
-
-struct WorkDesc {
-    unsigned long long totalWork;
-    int nTilesX, nTilesY, nTilesShard, shardIndex, shardCount;
-    long long spp, sampleBegin;
-    int run;   // consecutive samples of a pixel handed out together (a power of two dividing spp, at most MIPT_WORK_RUN = 16)
-};
 
 DEV unsigned long long WaveSum(unsigned long long v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -702,10 +510,6 @@ DEV bool OpenNode(const float4 *__restrict__ wnodes, int cur, const RayCtx &r, f
     }
 }
 
-// A leaf's primitive count in the traversal records carries LEAF_SIMPLE when every primitive of the leaf is a triangle (no
-// quadric to postpone, no instance to enter): those leaves go through the cooperative test of k_trav.
-constexpr int LEAF_SIMPLE = 0x4000, LEAF_COUNT_MASK = 0x3fff;
-
 // Advance until the lane holds a leaf (returns true with leafOffset/leafCount) or the
 // traversal is finished (returns false, st.cur == -1).
 template <int W>
@@ -834,18 +638,14 @@ DEV void HitInteraction(const DScene &s, int prim, const V3 &ro, const V3 &rd, f
 // ------------------------------------------------------------------ persistent traversal
 // One launch traverses every ray of a class (MODE 0: path rays of the alive slots, closest
 // hit; 1: NEE shadow rays of shadowQ, any hit; 2: MIS rays of misQ, closest hit; 3: the same rays as visibility queries,
-// see TRAV_IS_ANY below; 4: the dark MIS rays of darkQ, any hit, no answer). A fixed
+// see TRAV_IS_ANY, pt_pool.h; 4: the dark MIS rays of darkQ, any hit, no answer). A fixed
 // grid of waves pulls rays from a device-wide cursor: lanes whose ray finished fetch a new
 // one as soon as fewer than REFILL_BELOW lanes of the wave are still traversing (dynamic
 // fetch), so a long ray no longer idles the other 63 lanes. Quadrics are only recorded
 // (I_PEND*); k_resolve_* tests them afterwards at full lane utilisation.
-#ifndef MIPT_TRAV_BLOCKS_PER_CU
-#define MIPT_TRAV_BLOCKS_PER_CU 4
-#endif
 #ifndef MIPT_REFILL_BELOW
 #define MIPT_REFILL_BELOW 44   // (same-box A/B with the two-level records: 44 against 32, killeroo +1 %, the 10M-triangle scene +2 %)
 #endif
-constexpr int TRAV_BLOCKS_PER_CU = MIPT_TRAV_BLOCKS_PER_CU;
 constexpr int REFILL_BELOW = MIPT_REFILL_BELOW;
 #ifndef MIPT_TRI_BATCH
 #define MIPT_TRI_BATCH 16
@@ -854,7 +654,7 @@ constexpr int TRI_BATCH = MIPT_TRI_BATCH;
 #ifndef MIPT_COOP_KMAX
 #define MIPT_COOP_KMAX 4
 #endif
-static_assert(MIPT_TRAV_BLOCKS_PER_CU >= 1 && MIPT_TRAV_BLOCKS_PER_CU <= 8 && MIPT_REFILL_BELOW >= 1 && MIPT_REFILL_BELOW <= 64 && MIPT_TRI_BATCH >= 1 &&
+static_assert(MIPT_REFILL_BELOW >= 1 && MIPT_REFILL_BELOW <= 64 && MIPT_TRI_BATCH >= 1 &&
               MIPT_TRI_BATCH <= 64 && MIPT_COOP_KMAX >= 1 && MIPT_COOP_KMAX <= 8, "traversal tuning macros out of range");
 constexpr int COOP_KMAX = MIPT_COOP_KMAX;   // (triangle, ray) pairs a waiting lane hands to the wave per pass (pbrt's default leaf size)
 #ifndef MIPT_TRAV_CHUNK
@@ -868,9 +668,6 @@ constexpr int TRAV_CHUNK = MIPT_TRAV_CHUNK;  // work-list entries a wave reserve
 
 #ifndef MIPT_TRAV_WAVES_PER_EU
 #define MIPT_TRAV_WAVES_PER_EU 4
-#endif
-#ifndef MIPT_TRAV_WAVES_PER_EU_ANY
-#define MIPT_TRAV_WAVES_PER_EU_ANY 5   // the any-hit kernel (without the alpha-mask code): 96 VGPRs and a 24-KB stack allow five blocks per CU
 #endif
 // ALPHA: the scene has meshes with alpha masks (the mask test is compiled into this instance only)
 // INST: the scene has object instances (TransformedPrimitive, primitive.cpp:78-99). A lane that meets an instance in a world
@@ -892,7 +689,6 @@ template <int MODE, bool ALPHA, int W, bool INST = false, bool MOTION = false>
 // (k_resolve_overflow). Rays towards the environment light, and the dark rays, whose answer nothing reads (MIS_EXCL_DARK),
 // carry tLo = tHi = infinity: any hit ends them. A dark ray is traced and counted like any other -- by this kernel or by
 // MODE 2, whichever the scene uses -- but it writes nothing at its slot: its answer is MIS_ANSWER_DARK.
-#define TRAV_IS_ANY(MODE_) ((MODE_) == 1 || (MODE_) == 3 || (MODE_) == 4)
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu((TRAV_IS_ANY(MODE) && !ALPHA) ? MIPT_TRAV_WAVES_PER_EU_ANY : MIPT_TRAV_WAVES_PER_EU, (TRAV_IS_ANY(MODE) && !ALPHA) ? MIPT_TRAV_WAVES_PER_EU_ANY : MIPT_TRAV_WAVES_PER_EU)))
 k_trav(DScene s, Pool pool, DevCounters *ctr) {
     constexpr bool ANY = TRAV_IS_ANY(MODE);
@@ -1350,21 +1146,6 @@ DEV bool EndsUnshaded(int word, int prim, int maxDepth, int nInfiniteLights) {
 // over, bounces (ReportValue(pathLength, bounces)) and the sampler dimension stay.
 DEV int FinishedWord(int word) { return StateWord(F_FINISHED | (word & (F_L_IN_B | F_L_ZERO | F_BETA_ONE)), StateBounces(word), StateDim(word)); }
 
-// Slots per block of the kernels that walk the whole pool (k_generate, k_resolve_extend): SLOT_CHUNKS x 256. Every block
-// ends in a returning atomicAdd on a queue cursor, and one word takes ~88 of those per microsecond whoever issues them
-// (MI355X_MICROARCH.md, "dequeue"): with one 256-slot chunk per block a 32M-slot pool sent 131k adds to each cursor per
-// launch, a floor of 1.5 ms under kernels that have 1.4-2 ms of work. Eight chunks per block: 16k adds, 0.19 ms.
-#ifndef MIPT_SLOT_CHUNKS
-#define MIPT_SLOT_CHUNKS 8
-#endif
-constexpr int SLOT_CHUNKS = MIPT_SLOT_CHUNKS;
-// k_resolve_extend keeps a slot's rank within its (chunk, wave, class) in 8 bits per chunk of two 32-bit words (rankLo /
-// rankHi), k_generate a bit per chunk in 32-bit masks and the block's slot numbers in 16 bits: more than 8 chunks would
-// shift ranks out of their word (round 2's `-DMIPT_SLOT_CHUNKS=16` tuning build queued slots twice, overran a ray queue and
-// died of a GPU memory fault -- the "Aborted" of gpurun_out/call_var.log -- which also left the device unusable for the two
-// builds benched after it in that call). The tuning macros are checked where they are defined.
-static_assert(SLOT_CHUNKS >= 1 && SLOT_CHUNKS <= 8, "MIPT_SLOT_CHUNKS: 1..8 (rank words of k_resolve_extend, chunk masks of k_generate)");
-static_assert(SLOT_CHUNKS * BLOCK / 2 + SLOT_CHUNKS * BLOCK / 4 <= BLOCK * 33, "k_generate: the free-slot list and its flags live in the flush rows");
 // The per-(chunk, wave) counts of a block, cnt[(ch * BLOCK / 64 + w) * stride], become their exclusive prefix in place; returns
 // the total, which the caller reserves on its queue cursor in one add. Run by one thread between two barriers.
 DEV unsigned ChunkWavePrefix(unsigned *cnt, int stride) {
@@ -1645,7 +1426,6 @@ __global__ void __launch_bounds__(BLOCK) k_resolve_mis(DScene s, Pool pool, DevC
 // the three resolve kernels: re-traversed by the reference-order routine with inline quadric tests, then committed as the
 // resolve kernel would have (mode 0: hit record + shading queue; 1: occlusion + L += the light sample; 2: the MIS commit).
 // A fixed small grid walks the queue; it is empty for all but quadric-heavy scenes.
-constexpr int OVERFLOW_GRID = 512;
 template <bool INST, bool MOTION = false>
 __global__ void __launch_bounds__(BLOCK) k_resolve_overflow(DScene s, Pool pool, DevCounters *ctr, int mode) {
     const unsigned count = ctr->ovfCount[mode].v;
@@ -1716,7 +1496,7 @@ DEV void CameraRay(const DScene &s, float pFilmX, float pFilmY, float lensU, flo
 // freed slots with new camera samples, then the extend work list.
 //
 // A block owns SLOT_CHUNKS x 256 consecutive slots and makes three passes over them, so that everything it needs from a
-// shared cursor is asked for ONCE per block (a word takes ~88 returning atomics per microsecond; see SLOT_CHUNKS):
+// shared cursor is asked for ONCE per block (a word takes ~88 returning atomics per microsecond; see SLOT_CHUNKS, pt_pool.h):
 //   pass 1  flush the finished paths of each chunk into the film -- each finished lane stages its guarded radiance in LDS
 //           (row stride 33 words: conflict-free both ways); the samples of a wave that go to the same pixel are summed
 //           there and leave as ONE 128-B row update, two pixels per wave instruction (the full-rate shape for gfx950
@@ -2140,8 +1920,7 @@ __global__ void __launch_bounds__(BLOCK) k_generate(DScene s, Pool pool, float *
 }
 
 // The k_generate of a scene's camera: a uniform choice per launch.
-using GenerateKernel = void (*)(DScene, Pool, float *, DevCounters *, WorkDesc);
-static GenerateKernel GenerateKernelOf(const DScene &s) {
+GenerateKernel GenerateKernelOf(const DScene &s) {
     const bool moving = s.camera.animated != 0;
     if (s.motions) {
         switch (s.cameraType) {
@@ -3240,7 +3019,7 @@ __global__ void k_pixel_tables(DScene s, float *tab1, float *tab2, unsigned long
     }
 }
 
-// ------------------------------------------------------------------ texture lookups on their own (mi_pt_texture_lookup)
+// ------------------------------------------------------------------ camera rays and texture lookups on their own (mi_pt_camera_rays, mi_pt_texture_*)
 // mi_pt_camera_rays: CameraSampleDims and CameraRay as k_generate calls them, one listed sample per thread.
 template <bool MOVING>
 __global__ void k_camera_rays(DScene s, const int32_t *__restrict__ samples, uint32_t n, float *__restrict__ out) {
@@ -3292,12 +3071,72 @@ __global__ void k_camera_rays_ex(DScene s, const int32_t *__restrict__ samples, 
     for (int k = 0; k < 4; ++k) { o[9 + 3 * k] = diff[k].x; o[10 + 3 * k] = diff[k].y; o[11 + 3 * k] = diff[k].z; }
 }
 
+// The samples (px, py, sample number) of the camera-ray entry point `entry`: the pixel indexes per-pixel tables (Halton offsets, a
+// pixel sampler's tables), so it lies inside the sample bounds, and a pixel sampler's sample number inside its tables.
+static int CheckCameraSamples(const mi_pt *pt, const int32_t *samples, uint32_t n, const char *entry) {
+    const DScene &s = pt->scene;
+    for (uint32_t i = 0; i < n; ++i) {
+        const int px = samples[3 * i], py = samples[3 * i + 1];
+        if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3] || samples[3 * i + 2] < 0 ||
+            (s.samplerType >= MI_SAMPLER_ZEROTWO && samples[3 * i + 2] >= pt->spp)) {
+            g_err = std::string(entry) + ": a sample lies outside the sample bounds (or beyond a pixel sampler's tables)";
+            return MI_ERR_INVALID;
+        }
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out) {
+    if (!pt || !samples || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_camera_rays: more than 2^24 samples"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const DScene &s = pt->scene;
+    if (s.cameraType != MI_CAMERA_PERSPECTIVE) {   // the lens camera's ray at 550 nm (band 0) or an opt-in camera's, in this call's layout
+        std::vector<float> ex((size_t)n * MI_CAMERA_RAY_EX_FLOATS);
+        const int rc = mi_pt_camera_rays_ex(pt, samples, n, 0, ex.data());
+        if (rc != MI_OK) return rc;
+        for (uint32_t i = 0; i < n; ++i) memcpy(out + 8 * (size_t)i, ex.data() + (size_t)i * MI_CAMERA_RAY_EX_FLOATS, 8 * sizeof(float));
+        return MI_OK;
+    }
+    if (const int rc = CheckCameraSamples(pt, samples, n, "mi_pt_camera_rays")) return rc;
+    return RunProbe(pt->device, samples, (size_t)n * 3 * sizeof(int32_t), out, (size_t)n * 8 * sizeof(float), [&](void *ds, void *dout) {
+        hipLaunchKernelGGL((s.camera.animated ? k_camera_rays<true> : k_camera_rays<false>), ProbeGrid(n), dim3(BLOCK), 0, 0, s, (int32_t *)ds, n, (float *)dout);
+    });
+}
+
+extern "C" int mi_pt_camera_rays_ex(mi_pt *pt, const int32_t *samples, uint32_t n, int32_t band, float *out) {
+    if (!pt || !samples || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_camera_rays_ex: more than 2^24 samples"; return MI_ERR_INVALID; }
+    const DScene &s = pt->scene;
+    if (band < 0 || band >= std::max(1, s.nBands)) { g_err = "mi_pt_camera_rays_ex: no such band"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    if (const int rc = CheckCameraSamples(pt, samples, n, "mi_pt_camera_rays_ex")) return rc;
+    const bool moving = s.camera.animated != 0;
+    auto kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_PERSPECTIVE> : k_camera_rays_ex<false, MI_CAMERA_PERSPECTIVE>;
+    if (s.cameraType == MI_CAMERA_REALISTIC) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_REALISTIC> : k_camera_rays_ex<false, MI_CAMERA_REALISTIC>;
+    if (s.cameraType == MI_CAMERA_ORTHOGRAPHIC) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_ORTHOGRAPHIC> : k_camera_rays_ex<false, MI_CAMERA_ORTHOGRAPHIC>;
+    if (s.cameraType == MI_CAMERA_ENVIRONMENT) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_ENVIRONMENT> : k_camera_rays_ex<false, MI_CAMERA_ENVIRONMENT>;
+    return RunProbe(pt->device, samples, (size_t)n * 3 * sizeof(int32_t), out, (size_t)n * MI_CAMERA_RAY_EX_FLOATS * sizeof(float), [&](void *ds, void *dout) {
+        hipLaunchKernelGGL(kernel, ProbeGrid(n), dim3(BLOCK), 0, 0, s, (int32_t *)ds, n, (int)band, (float *)dout);
+    });
+}
+
 __global__ void k_texture_lookup(DScene s, int tex, const float *q, uint32_t n, float *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const mi_texture &t = s.textures[tex];
     const RGB3 v = MipLookup(s, s.mipmaps[t.mipmap], q[6 * i], q[6 * i + 1], q[6 * i + 2], q[6 * i + 3], q[6 * i + 4], q[6 * i + 5], t.filter, t.max_aniso);
     out[3 * i] = v.r; out[3 * i + 1] = v.g; out[3 * i + 2] = v.b;
+}
+
+extern "C" int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *rgb) {
+    if (!pt || !queries || !rgb) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
+    if (pt->textureTypes[tex] != MI_TEX_IMAGEMAP) { g_err = "mi_pt_texture_lookup: not an image texture"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    return RunProbe(pt->device, queries, (size_t)n * 6 * sizeof(float), rgb, (size_t)n * 3 * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_texture_lookup, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, tex, (float *)dq, n, (float *)dout);
+    });
 }
 
 // mi_pt_texture_probe: a noise texture's value for an interaction given by its world p, dpdx and dpdy, as k_shade asks for it
@@ -3309,6 +3148,17 @@ __global__ void k_texture_probe(DScene s, int tex, const float *q, uint32_t n, f
     td.dudx = td.dvdx = td.dudy = td.dvdy = 0;
     td.dpdx = V3(r[3], r[4], r[5]); td.dpdy = V3(r[6], r[7], r[8]);
     out[i] = EvalFloatImageTexture<true>(s, tex, 0.f, 0.f, V3(r[0], r[1], r[2]), td);
+}
+
+extern "C" int mi_pt_texture_probe(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
+    if (!MI_TEX_IS_NOISE(pt->textureTypes[tex])) { g_err = "mi_pt_texture_probe: not a noise texture"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_texture_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    return RunProbe(pt->device, queries, (size_t)n * 9 * sizeof(float), out, (size_t)n * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_texture_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)tex, (float *)dq, n, (float *)dout);
+    });
 }
 
 // mi_pt_texture_eval_probe: any texture record at an interaction given in full, through the routines k_shade evaluates it with.
@@ -3338,6 +3188,19 @@ __global__ void k_texture_eval_probe(DScene s, int tex, int mode, const float *q
     }
     const IllumRGB value = EvalImageTexture<true>(s, tex, u, v, p, td);
     for (int b = 0; b < MI_NSPEC; ++b) o[b] = TexBin(s.rgbIllum, s.textures, value, b);
+}
+
+extern "C" int mi_pt_texture_eval_probe(mi_pt *pt, int32_t tex, int32_t mode, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
+    if (mode < 0 || mode > 1) { g_err = "mi_pt_texture_eval_probe: mode must be 0 or 1"; return MI_ERR_INVALID; }
+    if (mode == 0 && !MI_TEX_HAS_MAPPING2D(pt->textureTypes[tex])) { g_err = "mi_pt_texture_eval_probe: the record has no 2-D mapping"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_texture_eval_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const size_t nOut = mode == 0 ? 6 : MI_NSPEC;
+    return RunProbe(pt->device, queries, (size_t)n * MI_TEXTURE_EVAL_QUERY_FLOATS * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_texture_eval_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)tex, (int)mode, (float *)dq, n, (float *)dout);
+    });
 }
 
 // ------------------------------------------------------------------ one quadric on its own (mi_pt_shape_probe)
@@ -3383,6 +3246,19 @@ __global__ void k_shape_probe(DScene s, int q, int mode, const float *in, uint32
     }
 }
 
+extern "C" int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (quadric < 0 || (uint32_t)quadric >= pt->nQuadrics) { g_err = "mi_pt_shape_probe: quadric index out of range"; return MI_ERR_INVALID; }
+    if (mode < 0 || mode > 2) { g_err = "mi_pt_shape_probe: mode must be 0, 1 or 2"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_shape_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const size_t nIn = mode == 0 ? 7 : (mode == 1 ? 5 : 6);
+    const size_t nOut = mode == 0 ? MI_SHAPE_PROBE_HIT_FLOATS : (mode == 1 ? MI_SHAPE_PROBE_SAMPLE_FLOATS : 1);
+    return RunProbe(pt->device, queries, (size_t)n * nIn * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_shape_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)quadric, (int)mode, (float *)dq, n, (float *)dout);
+    });
+}
+
 // ------------------------------------------------------------------ one light on its own (mi_pt_light_probe)
 // SampleLi / LiBin / ShapeSample with the full mask, as the general k_shade instance holds them; InfinitePdfLi, ShapePdf and
 // InfiniteLe as its MIS branch calls them. The reference point: no error bound, wo = +z, the query's normal.
@@ -3422,6 +3298,22 @@ __global__ void k_light_probe(DScene s, int light, int mode, const float *in, ui
     }
 }
 
+extern "C" int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const float *queries, float *out) {
+    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (light < 0 || (size_t)light >= pt->lightTypes.size()) { g_err = "mi_pt_light_probe: light index out of range"; return MI_ERR_INVALID; }
+    if (mode < 0 || mode > 2) { g_err = "mi_pt_light_probe: mode must be 0, 1 or 2"; return MI_ERR_INVALID; }
+    const int type = pt->lightTypes[light];
+    const bool delta = type == MI_LIGHT_POINT || type == MI_LIGHT_DISTANT || type == MI_LIGHT_SPOT || type == MI_LIGHT_PROJECTION;
+    if (mode == 2 && delta) { g_err = "mi_pt_light_probe: mode 2 (Le / L) on a delta light"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_light_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    const size_t nIn = mode == 0 ? 8 : (mode == 1 ? 9 : (type == MI_LIGHT_INFINITE ? 3 : 6));
+    const size_t nOut = mode == 0 ? MI_LIGHT_PROBE_SAMPLE_FLOATS : (mode == 1 ? 1 : MI_NSPEC);
+    return RunProbe(pt->device, queries, (size_t)n * nIn * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_light_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)light, (int)mode, (float *)dq, n, (float *)dout);
+    });
+}
+
 // ------------------------------------------------------------------ the Halton routines on their own (mi_pt_sampler_probe)
 // Query i = (index, first dimension) as two 64-bit words; `group` values per query: the grouped routines k_shade calls (5, 2, 1;
 // 32-bit indices) or ScrambledDimension (0: one value, any index). Neighbouring lanes get what the caller gives them: different
@@ -3440,6 +3332,24 @@ __global__ void k_sampler_probe(DScene s, int group, const uint64_t *in, uint32_
         out[2 * (size_t)i] = r.u0; out[2 * (size_t)i + 1] = r.u1;
     } else if (group == 1) out[i] = ScrambledDimensions1(HaltonTable(s.haltonDims), (uint32_t)index, dim);
     else out[i] = ScrambledDimension(s.primes, s.primeSums, s.perms, s.primeMagic, index, dim);
+}
+
+extern "C" int mi_pt_sampler_probe(mi_pt *pt, int32_t group, uint32_t n, const uint64_t *indices, const int32_t *first_dims, float *out) {
+    if (!pt || !indices || !first_dims || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
+    if (group != 0 && group != 1 && group != 2 && group != 5) { g_err = "mi_pt_sampler_probe: group must be 0, 1, 2 or 5"; return MI_ERR_INVALID; }
+    if (n > (1u << 24)) { g_err = "mi_pt_sampler_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
+    const int count = group == 0 ? 1 : group;
+    std::vector<uint64_t> q(2 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (first_dims[i] < 2 || first_dims[i] + count > pt->samplerDims) { g_err = "mi_pt_sampler_probe: dimensions outside [2, n_dims)"; return MI_ERR_INVALID; }
+        if (group != 0 && (indices[i] >> 32)) { g_err = "mi_pt_sampler_probe: the grouped routines take 32-bit indices"; return MI_ERR_INVALID; }
+        q[2 * (size_t)i] = indices[i];
+        q[2 * (size_t)i + 1] = (uint64_t)first_dims[i];
+    }
+    if (n == 0) return MI_OK;
+    return RunProbe(pt->device, q.data(), q.size() * sizeof(uint64_t), out, (size_t)n * count * sizeof(float), [&](void *dq, void *dout) {
+        hipLaunchKernelGGL(k_sampler_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)group, (const uint64_t *)dq, n, (float *)dout);
+    });
 }
 
 // ------------------------------------------------------------------ scalar helpers on their own (mi_pt_math_probe)
@@ -3466,6 +3376,25 @@ __global__ void k_math_probe(int op, uint32_t n, const float *x, const float *y,
         o[1] = DivFast(x0, y0, 1.f / y0, trk);
         o[2] = trk.Bad() ? 1.f : 0.f;
     }
+}
+
+extern "C" int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, const float *y, float *out) {
+    if (!x || !y || !out || op < 0 || op > 6) { g_err = "mi_pt_math_probe: bad argument"; return MI_ERR_INVALID; }
+    if (n == 0) return MI_OK;
+    int nDev = 0;
+    if (hipGetDeviceCount(&nDev) != hipSuccess || device_ordinal < 0 || device_ordinal >= nDev) { g_err = "no HIP device available (this path has no CPU fallback)"; return MI_ERR_NO_DEVICE; }
+    HIPCHK(hipSetDevice(device_ordinal));
+    DevBuf dx, dy, dout;   // (two inputs: not RunProbe's shape)
+    HIPCHK(dx.alloc((size_t)n * 2 * sizeof(float)));
+    HIPCHK(dy.alloc((size_t)n * 2 * sizeof(float)));
+    HIPCHK(dout.alloc((size_t)n * 3 * sizeof(float)));
+    HIPCHK(hipMemcpy(dx.p, x, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dy.p, y, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_math_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, op, n, dx.as<float>(), dy.as<float>(), dout.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return MI_OK;
 }
 
 // ------------------------------------------------------------------ standalone traversal (mi_pt_trace)
@@ -3671,7 +3600,6 @@ __global__ void __launch_bounds__(BLOCK) k_commit_metadata(DScene s, Pool pool, 
 // HIPFLAGS_part<N>): 1 (the matte and plastic instances) and 2 (the other instances without image textures) are built without
 // SLP packing, 3 and 5 (every instance that reads image textures, TM_TEXTURED) at plain -O3 -- DESIGN section 4, round 8.
 // A new instance needs a row in tests/test_shade_instances_gpu.py (the suite fails without a GPU until it has one).
-constexpr unsigned TM_FULL = TM_ALL & ~TM_INSTANCES, TM_GENERIC = TM_FULL & ~TM_TEXTURED;
 #define MIPT_SHADE_INSTANCES(X) \
     X(1, 2, TM_DIFFUSE | TM_LIGHTS_ALL) X(1, 2, TM_DIFFUSE | TM_LIGHTS_NO_ENV) \
     X(1, 2, TM_DIFFUSE | TM_LIGHTS_ALL | TM_SAMPLERS) X(1, 2, TM_DIFFUSE | TM_LIGHTS_NO_ENV | TM_SAMPLERS) \
@@ -3745,10 +3673,6 @@ constexpr unsigned TM_BSDF_BITS = 0x7fffu | (0xffu << 16) | TM_TEXTURED | TM_SCA
     X(2, TM_DIFFUSE | TM_TEXTURED) X(2, TM_PLASTIC | TM_TEXTURED) \
     X(4, TM_UBER) X(4, TM_GENERIC) X(4, TM_FULL) \
     X(MI_MAX_BXDFS, TM_DISNEY) X(MI_MAX_BXDFS, TM_GENERIC) X(MI_MAX_BXDFS, TM_FULL)
-// The forms of instance (nl, tm) as bits (bit f: form f of mi_pt_bsdf_probe is compiled for it), 0 for an instance without a row.
-unsigned BsdfProbeForms(int nl, unsigned tm);
-// Launches the probe of instance (nl, tm) on the null stream; false: no row, or a form the instance does not compile.
-bool LaunchBsdfProbe(int nl, unsigned tm, const DScene &s, int material, int mode, int form, int flags, const float *dq, uint32_t n, float *dout);
 
 #if !defined(MIPT_PART) || MIPT_PART == 4
 // One query per lane, in the frame oracle_bsdf builds (ns = ng = +z, ss = +x, ts = +y), every lobe of the material on, no
@@ -3868,54 +3792,9 @@ bool LaunchBsdfProbe(int nl, unsigned tm, const DScene &s, int material, int mod
 }
 #endif   // MIPT_PART 4
 
-}  // namespace dptk
-using namespace dptk;
-
 #if MIPT_HAS_MAIN
-// =============================================================================
-// C ABI
-// =============================================================================
-constexpr int N_EV = 8;   // events per iteration: kernel-class boundaries + the start of the closest-hit traversal launch
-struct SubRenderer {
-    Pool pool{};
-    DevCounters *ctr = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t evIter[2][N_EV] = {{nullptr}};  // per-iteration kernel boundaries, two alternating sets
-    double t[7] = {0};
-    int poolQuadPlanes = 0;   // spectral planes the pool was allocated with (spectralpath needs one set more)
-    int poolFloatPlanes = P_COUNT;   // float planes likewise (a realistic camera needs one more)
-    size_t poolBytes = 0;     // bytes of device memory behind the pool
-    unsigned long long iterations = 0;
-    DevCounters result{};
-    // what the host reads back in every iteration lands here: pinned, so the copy is one command that the device writes
-    // straight to host memory (hipHostMalloc at create, freed by mi_pt_destroy)
-    struct HostReads {
-        DevCursor shadeCount[MAX_CLASSES];   // the shading queues' lengths after the resolve stage of the path rays (ReadShadeCounts)
-        unsigned long long drawn;            // DevCounters::nextWork and alive after k_generate (round 5: pageable stack words before; the
-        unsigned alive;                      // extend class, which holds this read, 0.4500 -> 0.4489 s per three killeroo frames)
-    } *reads = nullptr;
-    unsigned long long shadeLaunches = 0, shadeBlocks = 0;   // k_shade launches of the last render and the blocks they covered
-    // The dark MIS rays of iteration i are traced beside iteration i + 1 (LaunchDarkTraversal): a stream at the lowest
-    // priority, the hand-over from k_shade (evDarkGo), the kernel's own boundaries in two alternating sets (evDark) and its
-    // end with the cursors cleared behind it (evDarkDone), which the next k_shade -- the next writer of darkQ and the
-    // R_MI planes -- waits for.
-    hipStream_t darkStream = nullptr;
-    hipEvent_t evDarkGo = nullptr, evDarkDone = nullptr, evDark[2][2] = {{nullptr}};
-    bool darkPending = false;            // evDarkDone has been recorded and nothing has waited for it yet
-    bool darkTimed[2] = {false, false};  // evDark[k] holds a launch whose time is not in t[5] yet
-    unsigned long long darkSeq = 0;      // launches on darkStream so far (picks the set)
-    unsigned long long darkLaunches = 0; // k_trav<4> launches of the last render
-    unsigned long long stackPushed = 0, stackBeyondLds = 0;   // mi_pt_trav_stack_stats: of the last render or mi_pt_trace_wavefront call
-};
-
-// The k_shade instances by their index in MIPT_SHADE_INSTANCES.
-struct ShadeInstance {
-    int nl;
-    unsigned tm;
-    // [motion][lens]: [0][1] the LENS twin of an instance that reads image textures, [1][...] the MOTION twins of an instance
-    // with the instance code; null: no such twin
-    void (*kernel[2][2])(DScene, Pool, DevCounters *, unsigned);
-};
+// ------------------------------------------------------------------ kernel selection (pt_select.h)
+// The functions and tables that name a kernel instance, for the host units: what they mention is instantiated here, in part 0.
 template <int NL, unsigned TM, bool LENS>
 constexpr auto MotionShadeKernel() -> void (*)(DScene, Pool, DevCounters *, unsigned) {
     if constexpr ((TM & TM_INSTANCES) != 0) return k_shade<NL, TM, LENS, true>;
@@ -3929,7 +3808,8 @@ constexpr auto LensShadeKernel() -> void (*)(DScene, Pool, DevCounters *, unsign
 #define MIPT_SHADE_ENTRY(P_, NL_, TM_) {NL_, (TM_), {{k_shade<NL_, (TM_)>, LensShadeKernel<NL_, (TM_)>()}, {MotionShadeKernel<NL_, (TM_), false>(), MotionShadeKernel<NL_, (TM_), true>()}}},
 static const ShadeInstance kShadeInstances[] = {MIPT_SHADE_INSTANCES(MIPT_SHADE_ENTRY)};
 #undef MIPT_SHADE_ENTRY
-constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstances[0]);
+static_assert(sizeof(kShadeInstances) / sizeof(kShadeInstances[0]) == N_SHADE_INSTANCES, "N_SHADE_INSTANCES (pt_select.h) counts the rows of MIPT_SHADE_INSTANCES");
+const ShadeInstance &ShadeInstanceAt(int i) { return kShadeInstances[i]; }
 
 // The k_shade instance of a shading class (an index into kShadeInstances, -1: none) from its lobe types and Fresnel kinds
 // `types` and its longest lobe list `lobes` (the overflow class counts MI_MAX_BXDFS lobes; the miss class has neither
@@ -3942,7 +3822,7 @@ constexpr int N_SHADE_INSTANCES = sizeof(kShadeInstances) / sizeof(kShadeInstanc
 // textured class of such a scene goes there, and the textured matte and plastic instances are the code they were before.
 // `projection`: the scene has a projection light, whose code the same instances hold as the disks' (TM_HOLDS_PROJECTION): any
 // class can draw that light, so every class of such a scene goes where a scene with disks sends it.
-static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot, bool disks, bool noise, bool projection) {
+int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned hot, bool disks, bool noise, bool projection) {
     disks |= projection;
     auto pick = [](int nl, unsigned tm) {
         for (int i = 0; i < N_SHADE_INSTANCES; ++i)
@@ -3974,1675 +3854,7 @@ static int ShadeInstanceOf(unsigned types, int lobes, bool instanced, unsigned h
     return pick(texturedDisney ? MI_MAX_BXDFS : lobes <= 2 ? 2 : lobes <= 4 ? 4 : MI_MAX_BXDFS, TM_FULL);
 }
 
-struct mi_pt {
-    int device = 0;
-    DScene scene{};
-    std::vector<void *> allocs;   // every device buffer of create (mi_pt_destroy frees them)
-    float *film = nullptr;  // [nPix][32]
-    float *stageSum = nullptr, *stageW = nullptr;   // [nPix][31] / [nPix] staging of the host hand-over
-    size_t nPix = 0;
-    int filmW = 0, filmH = 0;
-    long long spp = 0;
-    std::vector<SubRenderer> subs;
-    double lastSeconds[8] = {0};
-    uint32_t nTextures = 0;
-    std::vector<int> textureTypes;
-    bool hasAlphaMasks = false;      // picks the traversal kernels compiled with the alpha-mask test
-    bool hasInstances = false;       // ... and with the TransformedPrimitive code (those carry the alpha-mask test too)
-    uint32_t nQuadrics = 0;          // n_spheres + n_disks (mi_pt_shape_probe)
-    int samplerDims = 0;             // mi_sampler.n_dims: the dimensions the Halton tables hold (mi_pt_sampler_probe)
-    std::vector<int> lightTypes;     // mi_light.type of every light (mi_pt_light_probe)
-    std::vector<int> materialLobes;  // mi_material.n_bxdfs of every material, -1 - n_bxdfs for one that reads an image texture (mi_pt_bsdf_probe)
-    bool hasQuadrics = false;        // the scene has spheres or disks: the quadric lists of rays can overflow (k_resolve_overflow is launched)
-    bool hasInfiniteLight = false;   // picks the kernels compiled with the environment-light code
-    unsigned shadeClasses[N_SHADE_INSTANCES] = {0};   // per k_shade instance: the shading classes it runs (ShadeInstanceOf)
-    int numCUs = 256;
-    // k_resolve_shadow and k_resolve_mis walk their queues on grids sized by what the device holds at once (QueueGrid):
-    // resident blocks per CU of each, from the occupancy query at create
-    int resolveBlocksPerCU[3] = {0};    // [1]: k_resolve_shadow, [2]: k_resolve_mis ([0], k_resolve_extend, walks the pool)
-    unsigned queueBlocksCap = 0;        // MIPT_QUEUE_BLOCKS (tests): at most so many blocks for those kernels, 0 = unset
-    bool shadeGridPool = false;         // MIPT_SHADE_GRID=pool: every k_shade instance on a pool-sized grid, no read of the class counts
-    bool darkInLine = false;            // MIPT_DARK_STREAM=0: k_trav<4> on the main stream after the live MIS stage (the partner for A/B runs and tests)
-    // Integrator "metadata" (mi_pt_render_metadata): the ids of the primitives as create copied them, their device copy
-    // (made by the first metadata pass: a renderer that only renders radiance holds none) and, during such a pass, its
-    // strategy (-1: a radiance render)
-    std::vector<mi_prim_meta> primMetaHost;
-    const mi_prim_meta *primMeta = nullptr;
-    int metaStrategy = -1;
-};
-
-namespace {
-
-template <typename T>
-int Upload(mi_pt *pt, const T *src, size_t count, const T **dst) {
-    *dst = nullptr;
-    if (count == 0 || !src) {
-        void *p = nullptr;
-        HIPCHK(hipMalloc(&p, 16));
-        pt->allocs.push_back(p);
-        *dst = (const T *)p;
-        return MI_OK;
-    }
-    void *p = nullptr;
-    HIPCHK(hipMalloc(&p, count * sizeof(T) + 16));   // (16 B of slack: the kernels read spectra as 16-B quads)
-    pt->allocs.push_back(p);
-    HIPCHK(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *dst = (const T *)p;
-    return MI_OK;
-}
-
-// A run of uploads that stops at the first failure: the later ones do nothing and `rc` keeps the failure's code.
-struct Uploads {
-    mi_pt *pt;
-    int rc = MI_OK;
-    template <typename T>
-    void operator()(const T *src, size_t count, const T *&dst) {
-        if (rc == MI_OK) rc = Upload(pt, src, count, &dst);
-    }
-};
-
-// A device buffer that create fills on the device, listed in pt->allocs (freed by mi_pt_destroy) as soon as it exists.
-template <typename T>
-int Alloc(mi_pt *pt, size_t bytes, T **dst, const char *what) {
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();   // the failed hipMalloc must not poison the next call's hipGetLastError
-        g_err = std::string("hipMalloc(") + what + ") failed";
-        return MI_ERR_NOMEM;
-    }
-    pt->allocs.push_back(p);
-    *dst = (T *)p;
-    return MI_OK;
-}
-
-// Spectral quad planes of a path slot: spectralpath keeps one set more, the stitched spectrum of the camera sample (Q_LCA).
-int QuadPlanes(const DScene &s) { return Q_COUNT + (s.nBands > 1 ? NQ : 0); }
-// Float planes of a path slot: a realistic camera keeps the ray weight (P_WEIGHT).
-// (the orthographic and environment cameras have weight 1 and no such plane -- except in front of textures, where the
-// differentials' planes keep their numbers behind it)
-int FloatPlanes(const DScene &s) { return P_COUNT + (s.cameraType == MI_CAMERA_REALISTIC || s.lensDiff ? 1 : 0) + (s.lensDiff ? N_LENSDIFF : 0) + (s.motions ? 1 : 0); }
-// (the time plane of a scene with moving instances: the last one)
-int TimePlaneOf(const DScene &s) { return s.motions ? FloatPlanes(s) - 1 : 0; }
-// Samples per pixel of one pass.
-long long PassSpp(const mi_pt *pt, const mi_render_params *rp) { return rp->spp_override > 0 ? rp->spp_override : pt->spp; }
-
-// Device bytes of one path slot: planes, records, spectra and its entries in the queues.
-size_t PoolSlotBytes(int nQuadPlanes, int nFloatPlanes) {
-    return (size_t)nFloatPlanes * sizeof(float) + (size_t)nQuadPlanes * sizeof(float4) + (size_t)R_COUNT * sizeof(float4) + (size_t)I_COUNT * sizeof(int) +
-           (size_t)(7 + MAX_CLASSES + 3) * sizeof(uint32_t);
-}
-
-void FreePool(Pool &p) {
-    hipFree(p.f); hipFree(p.q); hipFree(p.r); hipFree(p.i); hipFree(p.shadowQ); hipFree(p.extQ); hipFree(p.misQ); hipFree(p.darkQ); hipFree(p.shadeQ); hipFree(p.ovfQ);
-    p = Pool{};   // n = 0, every pointer null: a later render cannot mistake a half-built pool for a usable one
-}
-
-// The one way a sub-renderer gives its pool back: the memory and every record of it, so that mi_pt_pool_info and the next
-// render's memory budget count nothing that is no longer held.
-void ReleasePool(SubRenderer &sub) {
-    FreePool(sub.pool);
-    sub.poolQuadPlanes = 0; sub.poolFloatPlanes = 0;
-    sub.poolBytes = 0;
-}
-
-// Failure-safe: the new pool is built aside and swapped in only when every allocation succeeded; after a failure the
-// sub-renderer holds no pool at all (n == 0), so the next render allocates afresh instead of launching on stale sizes.
-int EnsurePool(SubRenderer &sub, uint32_t n, int nQuadPlanes, int nFloatPlanes) {
-    Pool &p = sub.pool;
-    if (p.n == n && p.f && sub.poolQuadPlanes == nQuadPlanes && sub.poolFloatPlanes == nFloatPlanes) return MI_OK;
-    ReleasePool(sub);
-    Pool t{};
-    const bool ok = hipMalloc((void **)&t.f, (size_t)nFloatPlanes * n * sizeof(float)) == hipSuccess &&
-                    hipMalloc((void **)&t.q, (size_t)nQuadPlanes * n * sizeof(float4)) == hipSuccess &&
-                    hipMalloc((void **)&t.r, (size_t)R_COUNT * n * sizeof(float4)) == hipSuccess &&
-                    hipMalloc((void **)&t.i, (size_t)I_COUNT * n * sizeof(int)) == hipSuccess &&
-                    hipMalloc((void **)&t.shadowQ, (size_t)2 * n * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc((void **)&t.extQ, (size_t)n * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc((void **)&t.misQ, (size_t)3 * n * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc((void **)&t.darkQ, (size_t)n * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc((void **)&t.shadeQ, (size_t)MAX_CLASSES * n * sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc((void **)&t.ovfQ, (size_t)3 * n * sizeof(uint32_t)) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();   // the failed hipMalloc must not poison the next call's hipGetLastError
-        FreePool(t);
-        g_err = "hipMalloc(path pool of " + std::to_string(n) + " slots) failed";
-        return MI_ERR_NOMEM;
-    }
-    t.n = n;
-    p = t;
-    sub.poolQuadPlanes = nQuadPlanes;
-    sub.poolFloatPlanes = nFloatPlanes;
-    sub.poolBytes = (size_t)n * PoolSlotBytes(nQuadPlanes, nFloatPlanes);
-    return MI_OK;
-}
-
-// Device temporaries of the entry points: freed on every return path.
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
-// The body of an entry point that asks the device one batch of questions: `in` to the device, `launch(dIn, dOut)` (on the null
-// stream), `out` back. The entry point has checked its arguments.
-template <typename Launch>
-int RunProbe(int device, const void *in, size_t inBytes, void *out, size_t outBytes, Launch launch) {
-    HIPCHK(hipSetDevice(device));
-    DevBuf dIn, dOut;
-    HIPCHK(dIn.alloc(inBytes));
-    HIPCHK(dOut.alloc(outBytes));
-    HIPCHK(hipMemcpy(dIn.p, in, inBytes, hipMemcpyHostToDevice));
-    launch(dIn.p, dOut.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dOut.p, outBytes, hipMemcpyDeviceToHost));
-    return MI_OK;
-}
-// The grid of such a launch: a thread per question.
-dim3 ProbeGrid(uint32_t n) { return dim3((n + BLOCK - 1) / BLOCK); }
-
-// The samples (px, py, sample number) of the camera-ray entry point `entry`: the pixel indexes per-pixel tables (Halton offsets, a
-// pixel sampler's tables), so it lies inside the sample bounds, and a pixel sampler's sample number inside its tables.
-int CheckCameraSamples(const mi_pt *pt, const int32_t *samples, uint32_t n, const char *entry) {
-    const DScene &s = pt->scene;
-    for (uint32_t i = 0; i < n; ++i) {
-        const int px = samples[3 * i], py = samples[3 * i + 1];
-        if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3] || samples[3 * i + 2] < 0 ||
-            (s.samplerType >= MI_SAMPLER_ZEROTWO && samples[3 * i + 2] >= pt->spp)) {
-            g_err = std::string(entry) + ": a sample lies outside the sample bounds (or beyond a pixel sampler's tables)";
-            return MI_ERR_INVALID;
-        }
-    }
-    return MI_OK;
-}
-
-// A call that renders through a view of the scene of its own (mi_pt_render_metadata, mi_pt_debug_path) edits pt->scene in
-// place behind one of these: the renderer's DScene and its metaStrategy are back on every return path.
-struct SceneViewGuard {
-    mi_pt *pt;
-    DScene scene = pt->scene;
-    int metaStrategy = pt->metaStrategy;
-    ~SceneViewGuard() { pt->scene = scene; pt->metaStrategy = metaStrategy; }
-};
-
-// -----------------------------------------------------------------------------
-// mi_pt_create, step 1: every refusal that depends on the description alone, before anything touches the device
-// -----------------------------------------------------------------------------
-// a float record of the classes beside the image and noise textures (EvalFloatImageTexture in the general instances): what a
-// roughness, sigma or bump parameter may name besides those two
-static bool FloatClassRecord(const mi_texture &t) {
-    return t.is_float && (t.type == MI_TEX_CHECKERBOARD || t.type == MI_TEX_DOTS || t.type == MI_TEX_BILERP || t.type == MI_TEX_CHECKERBOARD3D);
-}
-int CheckSceneDesc(const mi_scene_desc *d) {
-    if (d->n_prims && !d->n_nodes) { g_err = "primitives without BVH nodes"; return MI_ERR_INVALID; }
-    for (uint32_t i = 0; i < d->n_nodes; ++i) {
-        const mi_bvh_node &n = d->nodes[i];
-        if (n.n_prims > 0) { if (n.offset < 0 || (uint32_t)n.offset + n.n_prims > d->n_prims) { g_err = "BVH leaf out of range"; return MI_ERR_INVALID; } }
-        else if (n.offset <= (int)i || (uint32_t)n.offset >= d->n_nodes || i + 1 >= d->n_nodes) { g_err = "BVH child out of range"; return MI_ERR_INVALID; }
-        if (n.n_prims > (unsigned)LEAF_COUNT_MASK) { g_err = "a BVH leaf holds more than 16383 primitives"; return MI_ERR_UNSUPPORTED; }
-    }
-    for (uint32_t i = 0; i < d->n_prims; ++i) {
-        const mi_prim &p = d->prims[i];
-        if (p.instance != 0) {
-            if (p.instance < 0 || (uint32_t)p.instance > d->n_instances || !d->instances) { g_err = "primitive instance index out of range"; return MI_ERR_INVALID; }
-            if (d->instances[p.instance - 1].root >= d->n_nodes) { g_err = "instance BVH root out of range"; return MI_ERR_INVALID; }
-            continue;
-        }
-        if (p.shape >= 0 ? (uint32_t)p.shape >= d->n_tris : (uint64_t)(uint32_t)(~p.shape) >= (uint64_t)d->n_spheres + d->n_disks) { g_err = "primitive shape index out of range"; return MI_ERR_INVALID; }
-        if (p.material >= (int)d->n_materials || p.area_light >= (int)d->n_lights) { g_err = "primitive material/light index out of range"; return MI_ERR_INVALID; }
-    }
-    if ((d->n_instances && !d->instances) || (d->n_motions && !d->motions)) { g_err = "instance or motion array missing"; return MI_ERR_INVALID; }
-    for (uint32_t k = 0; k < d->n_instances; ++k)   // (every instance, referenced by a primitive or not)
-        if (d->instances[k].motion > d->n_motions) { g_err = "instance motion index out of range"; return MI_ERR_INVALID; }
-    if ((d->n_spheres && !d->spheres) || (d->n_disks && !d->disks) || (uint64_t)d->n_spheres + d->n_disks > 0x7fffffffull) { g_err = "quadric arrays missing or too large"; return MI_ERR_INVALID; }
-    for (uint32_t i = 0; i < d->n_disks; ++i)
-        if (d->disks[i].kind != MI_QUADRIC_DISK) { g_err = "mi_disk.kind: only disks (0) are built"; return MI_ERR_UNSUPPORTED; }
-    for (uint32_t i = 0; i < d->n_tris * 3; ++i)
-        if (d->tri_indices[i] < 0 || (uint32_t)d->tri_indices[i] >= d->n_verts) { g_err = "triangle vertex index out of range"; return MI_ERR_INVALID; }
-    for (uint32_t i = 0; i < d->n_tris; ++i)
-        if (d->tri_mesh[i] >= d->n_meshes) { g_err = "triangle mesh index out of range"; return MI_ERR_INVALID; }
-    for (uint32_t i = 0; i < d->n_meshes; ++i)
-        if (d->meshes[i].alpha_tex >= (int)d->n_textures || d->meshes[i].shadow_alpha_tex >= (int)d->n_textures) { g_err = "mi_mesh alpha texture index out of range"; return MI_ERR_INVALID; }
-    for (uint32_t i = 0; i < d->n_materials; ++i) {
-        const mi_material &m = d->materials[i];
-        if (m.n_bxdfs < 0 || m.n_bxdfs > MI_MAX_BXDFS) { g_err = "material lobe count out of range"; return MI_ERR_INVALID; }
-        if (m.bump_tex >= (int)d->n_textures || m.bump_tex < -1) { g_err = "mi_material.bump_tex out of range"; return MI_ERR_INVALID; }
-        if (m.bump_tex >= 0 && d->textures[m.bump_tex].type == MI_TEX_UV) { g_err = "mi_material.bump_tex names a MI_TEX_UV record, which has no float value"; return MI_ERR_INVALID; }
-        for (int k = 0; k < 2; ++k) {   // roughness maps: float image textures with a pyramid behind them, or noise textures (EvalFloatImageTexture)
-            const int rt = m.rough_tex[k];
-            if (rt < -1 || rt >= (int)d->n_textures) { g_err = "mi_material.rough_tex out of range"; return MI_ERR_INVALID; }
-            if (rt >= 0 && !MI_TEX_IS_NOISE(d->textures[rt].type) && !FloatClassRecord(d->textures[rt]) && (d->textures[rt].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[rt].mipmap >= d->n_mipmaps)) {
-                g_err = "mi_material.rough_tex must name an image texture with a mipmap or a noise texture"; return MI_ERR_INVALID;
-            }
-        }
-        // (ABI v10) the sigma map, the lobe rules and the glass switch: what the shading kernels index with them
-        if (m.sigma_tex < -1 || m.sigma_tex >= (int)d->n_textures ||
-            (m.sigma_tex >= 0 && !MI_TEX_IS_NOISE(d->textures[m.sigma_tex].type) && !FloatClassRecord(d->textures[m.sigma_tex]) &&
-             (d->textures[m.sigma_tex].type != MI_TEX_IMAGEMAP || (uint32_t)d->textures[m.sigma_tex].mipmap >= d->n_mipmaps))) {
-            g_err = "mi_material.sigma_tex must be -1 or name an image texture with a mipmap or a noise texture"; return MI_ERR_INVALID;
-        }
-        for (int k = 0; k < m.n_bxdfs; ++k) {
-            const mi_lobe_tex &lt = m.tex[k];
-            if (lt.rule < MI_LOBE_IF_R || lt.rule > MI_LOBE_METAL) { g_err = "mi_lobe_tex.rule is not a mi_lobe_rule"; return MI_ERR_INVALID; }
-            if (lt.tex_R < -1 || lt.tex_R >= (int)d->n_textures || lt.tex_S < -1 || lt.tex_S >= (int)d->n_textures) { g_err = "mi_lobe_tex texture index out of range"; return MI_ERR_INVALID; }
-            for (int tx : {lt.tex_R, lt.tex_S})   // (it has no pyramid either: the spectrum evaluation would look one up)
-                if (tx >= 0 && d->textures[tx].type == MI_TEX_BILERP) { g_err = "mi_lobe_tex names a MI_TEX_BILERP record, which has no spectrum value"; return MI_ERR_INVALID; }
-            if (lt.rule >= MI_LOBE_DISNEY_SHEEN && lt.rule <= MI_LOBE_DISNEY_STRANS && lt.tex_R < 0) { g_err = "a \"disney\" lobe rule needs the colour's texture in tex_R"; return MI_ERR_INVALID; }
-        }
-        if ((m.rough_flags & MI_ROUGH_GLASS) && (m.n_bxdfs < 1 || m.bxdf[0].type != MI_BXDF_FRESNEL_SPECULAR)) {
-            g_err = "MI_ROUGH_GLASS: lobe 0 must be the FresnelSpecular one"; return MI_ERR_INVALID;
-        }
-    }
-    for (uint32_t i = 0; i < d->n_textures; ++i) {
-        const mi_texture &t = d->textures[i];
-        if (t.type < MI_TEX_IMAGEMAP || t.type > MI_TEX_CHECKERBOARD3D) { g_err = "mi_texture.type is not a mi_tex_type"; return MI_ERR_INVALID; }
-        if (t.mapping < MI_MAP_UV || t.mapping > MI_MAP_PLANAR) { g_err = "mi_texture.mapping is not a mi_tex_mapping"; return MI_ERR_INVALID; }
-        if (t.mapping != MI_MAP_UV && !MI_TEX_HAS_MAPPING2D(t.type)) { g_err = "mi_texture.mapping set on a record without a 2-D mapping"; return MI_ERR_INVALID; }
-        if ((t.type == MI_TEX_UV && t.is_float) || (t.type == MI_TEX_BILERP && !t.is_float)) { g_err = "MI_TEX_UV is a spectrum record and MI_TEX_BILERP a float one"; return MI_ERR_INVALID; }
-        if (t.type == MI_TEX_IMAGEMAP && (uint32_t)t.mipmap >= d->n_mipmaps) { g_err = "mi_texture.mipmap out of range"; return MI_ERR_INVALID; }
-        // (the octave loops run per lane: bounded here as the front end bounds them)
-        if (MI_TEX_IS_NOISE(t.type) && (t.octaves < 0 || t.octaves > MI_NOISE_MAX_OCTAVES)) { g_err = "mi_texture.octaves outside 0..32"; return MI_ERR_INVALID; }
-    }
-    // the traversal kernels hold no noise code, no other class and no mapping but UVMapping2D: a mask is an image texture under it
-    for (uint32_t i = 0; i < d->n_meshes; ++i)
-        for (int a : {d->meshes[i].alpha_tex, d->meshes[i].shadow_alpha_tex}) {
-            if (a >= 0 && d->textures[a].type != MI_TEX_IMAGEMAP) { g_err = "mi_mesh alpha textures must be image textures"; return MI_ERR_INVALID; }
-            if (a >= 0 && d->textures[a].mapping != MI_MAP_UV) { g_err = "mi_mesh alpha textures must be image textures under the uv mapping"; return MI_ERR_INVALID; }
-        }
-    for (uint32_t i = 0; i < d->n_mipmaps; ++i) {
-        const mi_mipmap &m = d->mipmaps[i];
-        if (m.n_levels < 1 || m.n_levels > MI_MAX_MIP_LEVELS || !m.texels || m.width < 1 || m.height < 1) { g_err = "malformed mi_mipmap"; return MI_ERR_INVALID; }
-    }
-    for (uint32_t i = 0; i < d->n_envmaps; ++i) {
-        const mi_envmap &e = d->envmaps[i];
-        // (a projection light's map is the image alone: nu = nv = 0 and no tables)
-        const bool tables = e.cond_func && e.cond_cdf && e.cond_func_int && e.marg_func && e.marg_cdf;
-        const bool noTables = !e.cond_func && !e.cond_cdf && !e.cond_func_int && !e.marg_func && !e.marg_cdf;
-        if (e.width < 1 || e.height < 1 || !e.rgb || !((e.nu >= 1 && e.nv >= 1 && tables) || (e.nu == 0 && e.nv == 0 && noTables))) {
-            g_err = "malformed mi_envmap"; return MI_ERR_INVALID;
-        }
-    }
-    int nInfinite = 0;
-    for (uint32_t i = 0; i < d->n_lights; ++i) {
-        const mi_light &l = d->lights[i];
-        if (l.type == MI_LIGHT_DIFFUSE_AREA && (l.shape >= 0 ? (uint32_t)l.shape >= d->n_tris : (uint64_t)(uint32_t)(~l.shape) >= (uint64_t)d->n_spheres + d->n_disks)) { g_err = "area light shape index out of range"; return MI_ERR_INVALID; }
-        if (l.type < MI_LIGHT_DIFFUSE_AREA || l.type > MI_LIGHT_PROJECTION) { g_err = "mi_light.type is not a light type"; return MI_ERR_INVALID; }
-        if (l.type == MI_LIGHT_PROJECTION && (l.proj_map < -1 || l.proj_map >= (int)d->n_envmaps)) { g_err = "mi_light.proj_map out of range"; return MI_ERR_INVALID; }
-        if (l.type != MI_LIGHT_INFINITE) continue;
-        if ((uint32_t)l.envmap >= d->n_envmaps || d->envmaps[l.envmap].nu < 1) { g_err = "infinite light without environment map"; return MI_ERR_INVALID; }
-        if (++nInfinite > 4) { g_err = "more than 4 infinite lights"; return MI_ERR_INVALID; }
-    }
-    const mi_lightdistrib &ld = d->light_distrib;
-    if (d->n_lights > 0 && ld.type != MI_LD_SPATIAL && (!ld.func || !ld.cdf || !ld.func_int)) { g_err = "light distribution tables missing"; return MI_ERR_INVALID; }
-    if (d->n_lights > 0 && ld.type == MI_LD_SPATIAL) {
-        const size_t nVox = (size_t)ld.n_voxels[0] * ld.n_voxels[1] * ld.n_voxels[2];
-        if (nVox == 0 || nVox * d->n_lights > (1ull << 31)) { g_err = "spatial light distribution too large for the dense per-voxel table"; return MI_ERR_UNSUPPORTED; }
-    }
-    if (d->integrator.n_ca_bands < 1 || d->integrator.n_ca_bands > MI_NSPEC) { g_err = "n_ca_bands must be in [1, 31]"; return MI_ERR_INVALID; }
-    if (d->camera_type < MI_CAMERA_PERSPECTIVE || d->camera_type > MI_CAMERA_ENVIRONMENT) { g_err = "unknown mi_scene_desc.camera_type"; return MI_ERR_INVALID; }
-    if (d->camera_type == MI_CAMERA_REALISTIC) {
-        const mi_lens *l = d->lens;
-        if (!l || l->n_elements < 1 || l->n_elements > MI_MAX_LENS_ELEMENTS || l->full_res[0] < 1 || l->full_res[1] < 1 || !(l->film_diagonal > 0)) {
-            g_err = "realistic camera: mi_scene_desc.lens missing or malformed (1 .. 32 elements, the film's resolution and diagonal)";
-            return MI_ERR_INVALID;
-        }
-    }
-    if (d->integrator.max_depth < 0 || d->integrator.max_depth > 255) { g_err = "max_depth must be in [0, 255] (a path's bounce count travels in 8 bits of its state word)"; return MI_ERR_UNSUPPORTED; }
-    const mi_sampler &sm = d->sampler;
-    if (sm.type < MI_SAMPLER_HALTON || sm.type > MI_SAMPLER_STRATIFIED) { g_err = "unknown mi_sampler.type"; return MI_ERR_INVALID; }
-    if (sm.samples_per_pixel < 1) { g_err = "mi_sampler.samples_per_pixel must be positive"; return MI_ERR_INVALID; }
-    if (sm.type >= MI_SAMPLER_ZEROTWO) {
-        if (sm.pixel_dims < 0 || sm.pixel_dims > 64) { g_err = "mi_sampler.pixel_dims must be in [0, 64]"; return MI_ERR_INVALID; }
-        if (sm.samples_per_pixel > (1 << 20)) { g_err = "pixel samplers tabulate every sample of a pixel: at most 2^20 samples per pixel"; return MI_ERR_UNSUPPORTED; }
-        if (sm.type == MI_SAMPLER_STRATIFIED && (sm.x_samples < 1 || sm.y_samples < 1 || (int64_t)sm.x_samples * sm.y_samples != sm.samples_per_pixel)) {
-            g_err = "stratified sampler: samples_per_pixel must be x_samples * y_samples"; return MI_ERR_INVALID;
-        }
-        if (sm.type == MI_SAMPLER_ZEROTWO && (sm.samples_per_pixel & (sm.samples_per_pixel - 1)) != 0) { g_err = "02sequence sampler: samples_per_pixel must be a power of two"; return MI_ERR_INVALID; }
-    }
-    if (sm.type == MI_SAMPLER_SOBOL) {
-        if (!sm.sobol_matrices || !sm.sobol_vdc || !sm.sobol_vdc_inv || sm.sobol_log2_resolution < 0 ||
-            sm.sobol_log2_resolution > 25 || sm.sobol_resolution != (1 << sm.sobol_log2_resolution)) { g_err = "malformed Sobol' sampler tables"; return MI_ERR_INVALID; }
-        if (sm.n_sobol_dims < 6 + 8 * d->integrator.max_depth * d->integrator.n_ca_bands) {
-            g_err = "Sobol' matrices cover too few dimensions for max_depth x n_ca_bands";
-            return MI_ERR_INVALID;
-        }
-    }
-    if (sm.n_dims < (sm.type == MI_SAMPLER_HALTON ? 6 + 8 * d->integrator.max_depth * d->integrator.n_ca_bands : 5)) {
-        g_err = "Halton tables cover too few dimensions for max_depth x n_ca_bands (the reference's prime table ends at 1000)";
-        return MI_ERR_INVALID;
-    }
-    if (d->film.cropped_bounds[2] - d->film.cropped_bounds[0] <= 0 || d->film.cropped_bounds[3] - d->film.cropped_bounds[1] <= 0) { g_err = "empty film"; return MI_ERR_INVALID; }
-    return MI_OK;
-}
-
-// -----------------------------------------------------------------------------
-// mi_pt_create, step 2: the tables the host derives from the checked description (no HIP calls)
-// -----------------------------------------------------------------------------
-
-// A leaf's count as the traversal records carry it: | LEAF_SIMPLE when the leaf holds triangles only (`coop`: unless
-// MIPT_NO_COOP_LEAVES is set).
-unsigned LeafMeta(const mi_scene_desc *d, const mi_bvh_node &leaf, bool coop) {
-    bool simple = coop;
-    for (uint32_t k = 0; k < leaf.n_prims && simple; ++k) {
-        const mi_prim &p = d->prims[leaf.offset + k];
-        simple = p.instance == 0 && p.shape >= 0;
-    }
-    return (unsigned)leaf.n_prims | (simple ? (unsigned)LEAF_SIMPLE : 0u);
-}
-
-struct BvhTables {
-    int width = 4;                       // MIPT_BVH_WIDTH=2: one record per BVH2 interior node, i.e. the reference's own node-visit counts
-    std::vector<float4> wnodes;          // the wide records (none: a wide-4 scene without nodes)
-    std::vector<int32_t> instWideRoot;   // wide-4, per instance: the first record of its object's tree
-    std::vector<float4> instRootBounds;  // ... and that tree's root box (min, max)
-};
-
-// The box of a wide-4 record's slot.
-void SetWide4Box(float4 *rec, int slot, const mi_bvh_node &c) {
-    float *f = (float *)rec + (slot < 2 ? 0 : 12) + (slot & 1) * 6;
-    f[0] = c.bmin[0]; f[1] = c.bmin[1]; f[2] = c.bmin[2]; f[3] = c.bmax[0]; f[4] = c.bmax[1]; f[5] = c.bmax[2];
-}
-
-// The links, the counts and the eight octants' visit orders of a wide-4 record.
-void FinishWide4Record(float4 *rec, const int link[4], const unsigned cnt[4], int axisRoot, const int groupN[2], const int groupAxis[2]) {
-    memcpy(&rec[6], link, 16);
-    const unsigned c01 = cnt[0] | (cnt[1] << 16), c23 = cnt[2] | (cnt[3] << 16);
-    unsigned ord[2] = {0, 0};
-    for (int oct = 0; oct < 8; ++oct) {
-        auto neg = [&](int axis) { return ((oct >> axis) & 1) != 0; };
-        int seq[4], n = 0;
-        bool used[4] = {false, false, false, false};
-        for (int pass = 0; pass < 2; ++pass) {
-            const int g = (neg(axisRoot) ? 1 : 0) ^ pass;   // near child's group first (bvh.cpp:686-692)
-            const int base = 2 * g;
-            if (groupN[g] == 2) {
-                const bool swap = neg(groupAxis[g]);
-                seq[n++] = base + (swap ? 1 : 0);
-                seq[n++] = base + (swap ? 0 : 1);
-            } else if (groupN[g] == 1) seq[n++] = base;
-        }
-        for (int k = 0; k < n; ++k) used[seq[k]] = true;
-        for (int sl = 0; sl < 4 && n < 4; ++sl) if (!used[sl]) seq[n++] = sl;   // absent slots last (never hit)
-        unsigned perm = 0;
-        for (int k = 0; k < 4; ++k) perm |= (unsigned)seq[k] << (2 * k);
-        ord[oct >> 2] |= perm << (8 * (oct & 3));
-    }
-    memcpy(&rec[7].x, &c01, 4); memcpy(&rec[7].y, &c23, 4);
-    memcpy(&rec[7].z, &ord[0], 4); memcpy(&rec[7].w, &ord[1], 4);
-}
-
-// Wide-4 records (OpenNode<4>): one per two-level subtree of the host's BVH2, in depth-first order. Slots 0/1 are the
-// left child's children (slot 0 alone = the left child itself when it is a leaf), slots 2/3 the right child's. False,
-// and `t` untouched, when a ray's stack could outgrow STACK_LDS + STACK_SPILL entries over them.
-bool BuildWide4(const mi_scene_desc *d, bool coop, BvhTables &t) {
-    const uint32_t nN = d->n_nodes;
-    const mi_bvh_node *nodes = d->nodes;
-    std::vector<int32_t> widx(nN, -1);
-    std::vector<uint32_t> order;   // BVH2 roots of the records, in record order
-    // the trees: the world's (root 0) and one per instanced object (mi_instance.root)
-    std::vector<uint32_t> treeRoots(1, 0u);
-    for (uint32_t k = 0; k < d->n_instances; ++k)
-        if (std::find(treeRoots.begin(), treeRoots.end(), d->instances[k].root) == treeRoots.end()) treeRoots.push_back(d->instances[k].root);
-    for (const uint32_t treeRoot : treeRoots) {
-        if (nodes[treeRoot].n_prims > 0) {   // a single-leaf tree gets a record of its own: the leaf in slot 0
-            widx[treeRoot] = (int32_t)order.size();
-            order.push_back(treeRoot);
-            continue;
-        }
-        std::vector<uint32_t> stack;
-        stack.push_back(treeRoot);
-        while (!stack.empty()) {
-            const uint32_t i = stack.back();
-            stack.pop_back();
-            widx[i] = (int32_t)order.size();
-            order.push_back(i);
-            uint32_t sub[4];
-            int nSub = 0;
-            const uint32_t ch[2] = {i + 1, (uint32_t)nodes[i].offset};
-            for (int c = 0; c < 2; ++c) {
-                if (nodes[ch[c]].n_prims > 0) continue;
-                const uint32_t g[2] = {ch[c] + 1, (uint32_t)nodes[ch[c]].offset};
-                for (int k = 0; k < 2; ++k) if (nodes[g[k]].n_prims == 0) sub[nSub++] = g[k];
-            }
-            for (int k = nSub - 1; k >= 0; --k) stack.push_back(sub[k]);   // first slot's subtree next in memory
-        }
-    }
-    const size_t nWide = std::max<size_t>(order.size(), 1);
-    std::vector<float4> w(nWide * 8, float4{0, 0, 0, 0});
-    std::vector<int> need(nWide, 0);   // stack entries a ray can hold below this record (filled bottom-up)
-    for (size_t r = order.size(); r-- > 0;) {   // records in reverse: a child record's stack need is known before its parent's
-        const uint32_t i = order[r];
-        float4 *rec = &w[r * 8];
-        if (nodes[i].n_prims > 0) {   // single-leaf tree: the root itself in slot 0
-            int link1[4] = {nodes[i].offset, 0, 0, 0};
-            unsigned cnt1[4] = {LeafMeta(d, nodes[i], coop), 0xffffu, 0xffffu, 0xffffu};
-            SetWide4Box(rec, 0, nodes[i]);
-            const int gN1[2] = {1, 0}, gA1[2] = {0, 0};
-            FinishWide4Record(rec, link1, cnt1, 0, gN1, gA1);
-            need[r] = 0;
-            continue;
-        }
-        int link[4] = {0, 0, 0, 0};
-        unsigned cnt[4] = {0xffffu, 0xffffu, 0xffffu, 0xffffu};
-        int gN[2] = {0, 0}, gA[2] = {0, 0}, below = 0, present = 0;
-        const uint32_t ch[2] = {i + 1, (uint32_t)nodes[i].offset};
-        for (int c = 0; c < 2; ++c) {
-            const mi_bvh_node &cn = nodes[ch[c]];
-            uint32_t sl[2];
-            if (cn.n_prims > 0) { gN[c] = 1; sl[0] = ch[c]; }
-            else { gN[c] = 2; gA[c] = cn.axis; sl[0] = ch[c] + 1; sl[1] = (uint32_t)cn.offset; }
-            for (int k = 0; k < gN[c]; ++k) {
-                const mi_bvh_node &gn = nodes[sl[k]];
-                const int slot = 2 * c + k;
-                SetWide4Box(rec, slot, gn);
-                if (gn.n_prims > 0) { link[slot] = gn.offset; cnt[slot] = LeafMeta(d, gn, coop); }
-                else { link[slot] = widx[sl[k]]; cnt[slot] = 0; below = std::max(below, need[widx[sl[k]]]); }
-                ++present;
-            }
-        }
-        need[r] = present - 1 + below;
-        FinishWide4Record(rec, link, cnt, nodes[i].axis, gN, gA);
-    }
-    int needAll = need[0];   // the world tree's need, plus -- inside an instance -- the return entry and the object tree's
-    for (uint32_t k = 0; k < d->n_instances; ++k) needAll = std::max(needAll, need[0] + 1 + need[widx[d->instances[k].root]]);
-    // (pbrt's own 64-entry stack bounds the BVH2 depth; a wide record can hold up to three entries per two levels)
-    if (needAll > STACK_LDS + STACK_SPILL) return false;
-    t.wnodes = std::move(w);
-    t.instWideRoot.assign(std::max<uint32_t>(d->n_instances, 1), 0);
-    t.instRootBounds.assign((size_t)std::max<uint32_t>(d->n_instances, 1) * 2, float4{0, 0, 0, 0});
-    for (uint32_t k = 0; k < d->n_instances; ++k) {
-        const mi_bvh_node &rn = nodes[d->instances[k].root];
-        t.instWideRoot[k] = widx[d->instances[k].root];
-        t.instRootBounds[2 * k] = float4{rn.bmin[0], rn.bmin[1], rn.bmin[2], 0};
-        t.instRootBounds[2 * k + 1] = float4{rn.bmax[0], rn.bmax[1], rn.bmax[2], 0};
-    }
-    return true;
-}
-
-// Wide-2 records: one 64-B record per interior node with both children's boxes.
-std::vector<float4> BuildWide2(const mi_scene_desc *d, bool coop) {
-    const uint32_t nN = d->n_nodes;
-    std::vector<int32_t> widx(nN, -1);
-    uint32_t nInterior = 0;
-    for (uint32_t i = 0; i < nN; ++i) if (d->nodes[i].n_prims == 0) widx[i] = (int32_t)nInterior++;
-    const bool rootLeaf = nN > 0 && d->nodes[0].n_prims > 0;
-    std::vector<float4> w((size_t)std::max<uint32_t>(nInterior, 1) * 4, float4{0, 0, 0, 0});
-    auto putChild = [&](float4 *rec, int which, uint32_t child, int axis) {
-        const mi_bvh_node &c = d->nodes[child];
-        int link, meta;
-        if (c.n_prims > 0) { link = c.offset; meta = (int)LeafMeta(d, c, coop); }
-        else { link = widx[child]; meta = 0; }
-        if (which == 0) {
-            rec[0] = float4{c.bmin[0], c.bmin[1], c.bmin[2], c.bmax[0]};
-            rec[1].x = c.bmax[1]; rec[1].y = c.bmax[2];
-            meta |= axis << 16;
-            memcpy(&rec[3].x, &link, 4); memcpy(&rec[3].z, &meta, 4);
-        } else {
-            rec[1].z = c.bmin[0]; rec[1].w = c.bmin[1];
-            rec[2] = float4{c.bmin[2], c.bmax[0], c.bmax[1], c.bmax[2]};
-            memcpy(&rec[3].y, &link, 4); memcpy(&rec[3].w, &meta, 4);
-        }
-    };
-    if (rootLeaf) {  // single-leaf tree: the root itself is the left "child", no right child
-        putChild(&w[0], 0, 0, 0);
-        const int absent = 0xffff;
-        memcpy(&w[3].w, &absent, 4);
-    } else {
-        for (uint32_t i = 0; i < nN; ++i) {
-            if (d->nodes[i].n_prims != 0) continue;
-            float4 *rec = &w[(size_t)widx[i] * 4];
-            putChild(rec, 0, i + 1, d->nodes[i].axis);
-            putChild(rec, 1, (uint32_t)d->nodes[i].offset, d->nodes[i].axis);
-        }
-    }
-    return w;
-}
-
-// The traversal records: wide-4 unless MIPT_BVH_WIDTH=2 asks for wide-2 or the tree is too deep for wide-4; object
-// instances are only traversed over wide-4 records.
-int BuildBvhTables(const mi_scene_desc *d, bool coop, BvhTables &t) {
-    t.width = 4;
-    if (const char *e = getenv("MIPT_BVH_WIDTH")) t.width = (atoi(e) == 2) ? 2 : 4;
-    if (t.width == 4 && d->n_nodes > 0 && !BuildWide4(d, coop, t)) t.width = 2;
-    if (t.width == 2 && d->n_instances > 0) {
-        g_err = "object instances are traversed over the two-level BVH records (MIPT_BVH_WIDTH=4), which MIPT_BVH_WIDTH=2 or this scene's tree depth rules out";
-        return MI_ERR_UNSUPPORTED;
-    }
-    if (t.width == 2) t.wnodes = BuildWide2(d, coop);
-    return MI_OK;
-}
-
-struct ShadingClasses {
-    std::vector<int> matClass;                       // per material: its shading class
-    unsigned classMask = 1u << MISS_CLASS;           // DScene::classMask
-    unsigned shadeClasses[N_SHADE_INSTANCES] = {0};  // mi_pt::shadeClasses
-    // what the two above were made from (mi_pt_shade_plan reports it)
-    int classLobes[MAX_CLASSES] = {0};       // per class: the longest lobe list
-    unsigned classTypes[MAX_CLASSES] = {0};  // per class: lobe types (bits 0..15) and fresnel kinds (bits 16..) present
-    int classInstance[MAX_CLASSES] = {0};    // per class in classMask: its k_shade instance
-    bool hasInfiniteLight = false, instanced = false;
-    unsigned hot = 0;   // the lights and sampler bits of the scene's matte and plastic instances
-};
-
-// Shading classes: one per distinct lobe-type list, in order of first appearance; then each class to its k_shade
-// instance (ShadeInstanceOf; `hot`: the lights and sampler bits of the scene's matte and plastic instances).
-int BuildShadingClasses(const mi_scene_desc *d, bool instanced, unsigned hot, ShadingClasses &sc) {
-    sc.matClass.assign(d->n_materials, 0);
-    int (&classLobes)[MAX_CLASSES] = sc.classLobes;
-    unsigned (&classTypes)[MAX_CLASSES] = sc.classTypes;
-    std::vector<std::vector<int>> signatures;
-    // (`noise`: some texture needs the hit point or is one of the classes beside image, 2-D spectrum checkerboard and noise --
-    // the code the TM_HOLDS_NOISE instances alone hold)
-    bool noise = false, projection = false;
-    for (uint32_t i = 0; i < d->n_textures; ++i) noise |= MI_TEX_IS_GENERAL(d->textures[i]);
-    for (uint32_t i = 0; i < d->n_lights; ++i) projection |= d->lights[i].type == MI_LIGHT_PROJECTION;
-    for (uint32_t i = 0; i < d->n_materials; ++i) {
-        const mi_material &m = d->materials[i];
-        std::vector<int> sig;
-        for (int j = 0; j < m.n_bxdfs; ++j) { sig.push_back(m.bxdf[j].type); sig.push_back(m.bxdf[j].fresnel); }
-        sig.push_back(m.textured ? 1 : 0);
-        size_t c = 0;
-        while (c < signatures.size() && signatures[c] != sig) ++c;
-        if (c == signatures.size()) signatures.push_back(sig);
-        const int cl = sc.matClass[i] = (int)std::min<size_t>(c, MISS_CLASS - 1);
-        sc.classMask |= 1u << cl;
-        classLobes[cl] = std::max(classLobes[cl], (c >= (size_t)MISS_CLASS - 1) ? MI_MAX_BXDFS : (int)m.n_bxdfs);
-        for (int j = 0; j < m.n_bxdfs; ++j) {
-            classTypes[cl] |= (1u << m.bxdf[j].type) | (1u << (16 + m.bxdf[j].fresnel));
-            if (m.bxdf[j].scaled) classTypes[cl] |= TM_SCALED;
-        }
-        if (m.textured) classTypes[cl] |= TM_TEXTURED;
-    }
-    for (int c = 0; c < MAX_CLASSES; ++c) {
-        if (!((sc.classMask >> c) & 1u)) continue;
-        const int i = ShadeInstanceOf(classTypes[c], classLobes[c], instanced, hot, d->n_disks > 0, noise, projection);
-        if (i < 0) { g_err = "no k_shade instance for shading class " + std::to_string(c); return MI_ERR_UNSUPPORTED; }
-        sc.classInstance[c] = i;
-        sc.shadeClasses[i] |= 1u << c;
-    }
-    return MI_OK;
-}
-
-// The shading plan of a description: what of the scene picks among the instances, then the classes and their instances.
-// mi_pt_create (BuildHostTables) and mi_pt_shade_plan both get it here. (The class records are accumulated: sc starts empty.)
-int PlanShading(const mi_scene_desc *d, ShadingClasses &sc) {
-    sc = ShadingClasses{};
-    for (uint32_t i = 0; i < d->n_lights; ++i) sc.hasInfiniteLight |= d->lights[i].type == MI_LIGHT_INFINITE;
-    sc.instanced = d->n_instances > 0;
-    // the matte and plastic instances exist with and without the environment-light code and with the Halton sampler alone or all three
-    sc.hot = (sc.hasInfiniteLight ? TM_LIGHTS_ALL : TM_LIGHTS_NO_ENV) | (d->sampler.type == MI_SAMPLER_HALTON ? 0u : TM_SAMPLERS);
-    return BuildShadingClasses(d, sc.instanced, sc.hot, sc);
-}
-
-// Whether Triangle::Intersect rejects the triangle (vertices v, positions a, b, c) as degenerate (triangle.cpp:303-314):
-// decided once here with the same arithmetic (doubles in Cross).
-bool DegenerateTriangle(const mi_scene_desc *d, const int32_t *v, const mi_mesh &m, float4 a, float4 b, float4 c) {
-    auto cross = [](const float *u, const float *w, double *o) {
-        o[0] = (double)u[1] * w[2] - (double)u[2] * w[1];
-        o[1] = (double)u[2] * w[0] - (double)u[0] * w[2];
-        o[2] = (double)u[0] * w[1] - (double)u[1] * w[0];
-    };
-    float uv[3][2] = {{0, 0}, {1, 0}, {1, 1}};
-    if (m.flags & MI_MESH_HAS_UV) for (int k = 0; k < 3; ++k) { uv[k][0] = d->UV[2 * v[k]]; uv[k][1] = d->UV[2 * v[k] + 1]; }
-    float duv02[2] = {uv[0][0] - uv[2][0], uv[0][1] - uv[2][1]}, duv12[2] = {uv[1][0] - uv[2][0], uv[1][1] - uv[2][1]};
-    float dp02[3] = {a.x - c.x, a.y - c.y, a.z - c.z}, dp12[3] = {b.x - c.x, b.y - c.y, b.z - c.z};
-    float determinant = duv02[0] * duv12[1] - duv02[1] * duv12[0];
-    bool degenerateUV = std::abs(determinant) < 1e-8;
-    bool needNg = degenerateUV;
-    if (!degenerateUV) {
-        float invdet = 1 / determinant;
-        float dpdu[3], dpdv[3];
-        for (int k = 0; k < 3; ++k) {
-            dpdu[k] = (duv12[1] * dp02[k] - duv02[1] * dp12[k]) * invdet;
-            dpdv[k] = (-duv12[0] * dp02[k] + duv02[0] * dp12[k]) * invdet;
-        }
-        double cr[3];
-        cross(dpdu, dpdv, cr);
-        float cx = (float)cr[0], cy = (float)cr[1], cz = (float)cr[2];
-        if (cx * cx + cy * cy + cz * cz == 0) needNg = true;
-    }
-    if (!needNg) return false;
-    float e1[3] = {c.x - a.x, c.y - a.y, c.z - a.z}, e2[3] = {b.x - a.x, b.y - a.y, b.z - a.z};
-    double cr[3];
-    cross(e1, e2, cr);
-    float cx = (float)cr[0], cy = (float)cr[1], cz = (float)cr[2];
-    return cx * cx + cy * cy + cz * cz == 0;
-}
-
-// Pre-gathered leaf records: positions of each BVH-ordered primitive + flags, three float4 per primitive.
-std::vector<float4> BuildPrimRecords(const mi_scene_desc *d, const std::vector<int> &matClass, bool &hasAlphaMasks, bool &hasQuadrics) {
-    std::vector<float4> pt3((size_t)d->n_prims * 3);
-    for (uint32_t i = 0; i < d->n_prims; ++i) {
-        const mi_prim &p = d->prims[i];
-        float4 a{0, 0, 0, 0}, b{0, 0, 0, 0}, c{0, 0, 0, 0};
-        unsigned flags = 0;
-        int shapeIdx = 0;
-        if (p.instance != 0) {   // a TransformedPrimitive: no shape of its own
-            flags = PRIM_FLAG_INSTANCE;
-            shapeIdx = p.instance - 1;
-        } else if (p.shape >= 0) {
-            const int32_t *v = &d->tri_indices[3 * p.shape];
-            const float *P = d->P;
-            a = float4{P[3 * v[0]], P[3 * v[0] + 1], P[3 * v[0] + 2], 0};
-            b = float4{P[3 * v[1]], P[3 * v[1] + 1], P[3 * v[1] + 2], 0};
-            c = float4{P[3 * v[2]], P[3 * v[2] + 1], P[3 * v[2] + 2], 0};
-            shapeIdx = p.shape;
-            const mi_mesh &m = d->meshes[d->tri_mesh[p.shape]];
-            if (DegenerateTriangle(d, v, m, a, b, c)) flags |= PRIM_FLAG_DEGENERATE;
-            if (m.alpha_tex >= 0 || m.shadow_alpha_tex >= 0) { flags |= PRIM_FLAG_ALPHA; hasAlphaMasks = true; }
-        } else {
-            hasQuadrics = true;
-            flags |= PRIM_FLAG_SPHERE;
-            shapeIdx = ~p.shape;
-        }
-        flags |= (unsigned)(p.material >= 0 ? matClass[p.material] : MISS_CLASS) << PRIM_CLASS_SHIFT;
-        memcpy(&a.w, &flags, 4);
-        memcpy(&b.w, &shapeIdx, 4);
-        pt3[3 * i] = a; pt3[3 * i + 1] = b; pt3[3 * i + 2] = c;
-    }
-    return pt3;
-}
-
-// Dilated world bounds of the area lights' shapes (dark MIS rays, MIS_EXCL_DARK), two float4 per light (min, max).
-std::vector<float4> BuildLightBounds(const mi_scene_desc *d) {
-    std::vector<float4> lb((size_t)std::max<uint32_t>(d->n_lights, 1) * 2, float4{-INFINITY, -INFINITY, -INFINITY, 0});
-    for (uint32_t i = 0; i < d->n_lights; ++i) {
-        const mi_light &l = d->lights[i];
-        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        auto add = [&](float x, float y, float z) { const float p[3] = {x, y, z}; for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], p[a]); mx[a] = std::max(mx[a], p[a]); } };
-        bool have = false;
-        if (l.type == MI_LIGHT_DIFFUSE_AREA && l.shape >= 0 && (uint32_t)l.shape < d->n_tris) {
-            const int32_t *v = &d->tri_indices[3 * l.shape];
-            for (int k = 0; k < 3; ++k) add(d->P[3 * v[k]], d->P[3 * v[k] + 1], d->P[3 * v[k] + 2]);
-            have = true;
-        } else if (l.type == MI_LIGHT_DIFFUSE_AREA && l.shape < 0 && (uint32_t)(~l.shape) < d->n_spheres) {
-            const mi_sphere &sp = d->spheres[~l.shape];   // Sphere::ObjectBound through ObjectToWorld (shape.cpp:50)
-            for (int c = 0; c < 8; ++c) {
-                const float x = (c & 1) ? sp.radius : -sp.radius, y = (c & 2) ? sp.radius : -sp.radius, z = (c & 4) ? sp.z_max : sp.z_min;
-                const float *m = sp.o2w;
-                const float w = m[12] * x + m[13] * y + m[14] * z + m[15];
-                add((m[0] * x + m[1] * y + m[2] * z + m[3]) / w, (m[4] * x + m[5] * y + m[6] * z + m[7]) / w, (m[8] * x + m[9] * y + m[10] * z + m[11]) / w);
-            }
-            have = true;
-        } else if (l.type == MI_LIGHT_DIFFUSE_AREA && l.shape < 0 && (uint64_t)(uint32_t)(~l.shape) < (uint64_t)d->n_spheres + d->n_disks) {
-            const mi_disk &k = d->disks[(uint32_t)(~l.shape) - d->n_spheres];   // Disk::ObjectBound (disk.cpp:43-46) through ObjectToWorld
-            for (int c = 0; c < 4; ++c) {
-                const float x = (c & 1) ? k.radius : -k.radius, y = (c & 2) ? k.radius : -k.radius, z = k.height;
-                const float *m = k.o2w;
-                const float w = m[12] * x + m[13] * y + m[14] * z + m[15];
-                add((m[0] * x + m[1] * y + m[2] * z + m[3]) / w, (m[4] * x + m[5] * y + m[6] * z + m[7]) / w, (m[8] * x + m[9] * y + m[10] * z + m[11]) / w);
-            }
-            have = true;
-        }
-        if (have) {
-            float scale = 0;
-            for (int a = 0; a < 3; ++a) scale = std::max(scale, std::max(std::abs(mn[a]), std::abs(mx[a])) + (mx[a] - mn[a]));
-            const float e = 1e-3f * scale;
-            lb[2 * i] = float4{mn[0] - e, mn[1] - e, mn[2] - e, 0};
-            lb[2 * i + 1] = float4{mx[0] + e, mx[1] + e, mx[2] + e, 0};
-        } else {   // not an area light: everything may hit
-            lb[2 * i] = float4{-INFINITY, -INFINITY, -INFINITY, 0};
-            lb[2 * i + 1] = float4{INFINITY, INFINITY, INFINITY, 0};
-        }
-    }
-    return lb;
-}
-
-// The area lights' primitives (DScene::lightPrim), and whether the MIS rays can be asked as visibility queries (k_trav,
-// MODE 3): no instances (the traversal kernels compiled for those keep the closest-hit form), no alpha mask on an
-// emitter's own mesh, and every area light the shape of exactly one primitive.
-std::vector<int> BuildLightPrims(const mi_scene_desc *d, bool &misAny) {
-    std::vector<int> lp((size_t)std::max<uint32_t>(d->n_lights, 1), (int)MIS_EXCL_NONE), seen((size_t)std::max<uint32_t>(d->n_lights, 1), 0);
-    bool ok = d->n_instances == 0 && d->n_prims < MIS_EXCL_DARK;
-    for (uint32_t i = 0; i < d->n_prims; ++i) {
-        const int al = d->prims[i].area_light;
-        if (al < 0) continue;
-        if ((uint32_t)al >= d->n_lights) { ok = false; continue; }
-        lp[al] = (int)i;
-        if (++seen[al] > 1 || d->prims[i].shape != d->lights[al].shape || d->prims[i].instance != 0) ok = false;
-    }
-    for (uint32_t i = 0; i < d->n_lights; ++i) {
-        const mi_light &l = d->lights[i];
-        if (l.type != MI_LIGHT_DIFFUSE_AREA) continue;
-        if (!seen[i]) ok = false;
-        // an emitter whose own mesh is masked: Shape::Pdf intersects it without the mask (shape.cpp:60), the traversal with it
-        if (l.shape >= 0 && (uint32_t)l.shape < d->n_tris) {
-            const mi_mesh &m = d->meshes[d->tri_mesh[l.shape]];
-            if (m.alpha_tex >= 0 || m.shadow_alpha_tex >= 0) ok = false;
-        }
-    }
-#ifdef MIPT_NO_MIS_ANY
-    ok = false;
-#endif
-    misAny = ok;
-    return lp;
-}
-
-// The Halton sampler's division magics: ceil(2^64 / p) for p not a power of two; p == 2 is never divided here.
-std::vector<uint64_t> BuildPrimeMagics(const mi_sampler &sm) {
-    std::vector<uint64_t> magic(sm.n_dims);
-    for (int i = 0; i < sm.n_dims; ++i) magic[i] = (~0ull) / (uint64_t)sm.primes[i] + 1;
-    return magic;
-}
-
-// The Halton records (HaltonDim, d_scene.h) of every sampler dimension, and behind them a copy of the permutations, which
-// permOffset reaches from the table's start. invBase and tail are computed here in float, in the expression order of
-// ScrambledRadicalInverseBase (d_sampling.h): this file is compiled without contraction on both sides and IEEE division is
-// correctly rounded on both, so the two floats are the bits the device's own divisions give.
-std::vector<HaltonDim> BuildHaltonDims(const mi_sampler &sm, const std::vector<uint64_t> &magic) {
-    const size_t nDims = (size_t)sm.n_dims, permBytes = (size_t)sm.n_perms * sizeof(uint16_t);
-    std::vector<HaltonDim> table(nDims + (permBytes + sizeof(HaltonDim) - 1) / sizeof(HaltonDim));
-    memset(table.data(), 0, table.size() * sizeof(HaltonDim));
-    for (size_t i = 0; i < nDims; ++i) {
-        HaltonDim &r = table[i];
-        const uint16_t *perm = sm.perms + sm.prime_sums[i];
-        r.base = (uint32_t)sm.primes[i];
-        r.permOffset = (uint32_t)(nDims * (sizeof(HaltonDim) / sizeof(uint16_t)) + (size_t)sm.prime_sums[i]);
-        r.magic = magic[i];
-        const float invBase = 1.f / (float)sm.primes[i];
-        r.invBase = invBase;
-        r.tail = invBase * (float)perm[0] / (1 - invBase);
-    }
-    if (permBytes) memcpy((void *)(table.data() + nDims), sm.perms, permBytes);
-    return table;
-}
-
-// The per-pixel Halton index offsets over a 128 x 128 tile (GetIndexForSample, halton.cpp:98-118).
-std::vector<uint32_t> BuildPixelOffsets(const mi_sampler &sm) {
-    std::vector<uint32_t> table(128 * 128, 0);
-    if (sm.sample_stride <= 1) return table;
-    auto inverseRadicalInverse = [](uint64_t base, uint64_t inverse, int nDigits) {
-        uint64_t index = 0;
-        for (int i = 0; i < nDigits; ++i) { uint64_t digit = inverse % base; inverse /= base; index = index * base + digit; }
-        return index;
-    };
-    for (int py = 0; py < 128; ++py)
-        for (int px = 0; px < 128; ++px) {
-            int64_t offset = 0;
-            const int pm[2] = {px, py};
-            for (int i = 0; i < 2; ++i) {
-                uint64_t dimOffset = inverseRadicalInverse(i == 0 ? 2 : 3, (uint64_t)pm[i], sm.base_exponents[i]);
-                offset += (int64_t)(dimOffset * (uint64_t)(sm.sample_stride / sm.base_scales[i]) * (uint64_t)sm.mult_inverse[i]);
-            }
-            offset %= (int64_t)sm.sample_stride;
-            table[py * 128 + px] = (uint32_t)offset;
-        }
-    return table;
-}
-
-// MIPMap::weightLut (mipmap.h:199-206).
-std::vector<float> BuildEwaWeights() {
-    std::vector<float> lut(128);
-    for (int i = 0; i < 128; ++i) {
-        float alpha = 2;
-        float r2 = float(i) / float(128 - 1);
-        lut[i] = std::exp(-alpha * r2) - std::exp(-alpha);
-    }
-    return lut;
-}
-
-struct HostTables {
-    BvhTables bvh;
-    ShadingClasses classes;
-    std::vector<float4> primTri, lightBounds;
-    std::vector<int> lightPrim;
-    std::vector<uint64_t> primeMagic;
-    std::vector<HaltonDim> haltonDims;
-    std::vector<uint32_t> pixelOffsets;
-    std::vector<float> ewaWeights;
-    bool hasAlphaMasks = false, hasQuadrics = false, misAny = false;
-};
-
-int BuildHostTables(const mi_scene_desc *d, HostTables &h) {
-    const bool coop = getenv("MIPT_NO_COOP_LEAVES") == nullptr;
-    int rc = BuildBvhTables(d, coop, h.bvh);
-    if (rc != MI_OK) return rc;
-    if ((rc = PlanShading(d, h.classes)) != MI_OK) return rc;
-    h.primTri = BuildPrimRecords(d, h.classes.matClass, h.hasAlphaMasks, h.hasQuadrics);
-    h.lightBounds = BuildLightBounds(d);
-    h.lightPrim = BuildLightPrims(d, h.misAny);
-    h.primeMagic = BuildPrimeMagics(d->sampler);
-    h.haltonDims = BuildHaltonDims(d->sampler, h.primeMagic);
-    h.pixelOffsets = BuildPixelOffsets(d->sampler);
-    h.ewaWeights = BuildEwaWeights();
-    return MI_OK;
-}
-
-// -----------------------------------------------------------------------------
-// mi_pt_create, step 3: the renderer's fields, the uploads, the create-time kernels and the render state
-// -----------------------------------------------------------------------------
-void SetSceneFields(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
-    DScene &s = pt->scene;
-    s.bvhWidth = h.bvh.width;
-    s.nInstances = d->n_instances;
-    s.misAny = h.misAny ? 1 : 0;
-    s.classMask = h.classes.classMask;
-    s.nNodes = d->n_nodes; s.nPrims = d->n_prims; s.nLights = d->n_lights; s.nMaterials = d->n_materials;
-    for (int i = 0; i < MI_NSPEC; ++i) s.cieY[i] = d->cie_y[i];
-    s.invSqrtSpp = 1 / std::sqrt((float)d->sampler.samples_per_pixel);
-    s.nInfiniteLights = 0;
-    for (int k = 0; k < 4; ++k) s.infiniteLights[k] = -1;
-    for (uint32_t i = 0; i < d->n_lights; ++i)
-        if (d->lights[i].type == MI_LIGHT_INFINITE) s.infiniteLights[s.nInfiniteLights++] = (int)i;
-    s.camera = d->camera;
-    s.cameraType = d->camera_type;
-    s.lens = nullptr;   // (UploadScene: the device copy)
-    s.motions = nullptr; s.timePlane = 0;   // (UploadScene, when an instance moves)
-    s.lensDiff = 0;
-    if (d->camera_type != MI_CAMERA_PERSPECTIVE)   // (k_shade restates the perspective camera's offset rays itself)
-        for (uint32_t i = 0; i < d->n_materials; ++i) if (d->materials[i].textured) s.lensDiff = 1;
-    s.fullRes[0] = d->film.full_res[0]; s.fullRes[1] = d->film.full_res[1];
-    s.envIpd = d->env_ipd; s.envPoleMergeTo = d->env_pole_merge_to; s.envPoleMergeFrom = d->env_pole_merge_from;
-    s.envConvergenceDistance = d->env_convergence_distance;
-    for (int i = 0; i < 4; ++i) { s.croppedBounds[i] = d->film.cropped_bounds[i]; s.sampleBounds[i] = d->film.sample_bounds[i]; s.pixelBounds[i] = d->integrator.pixel_bounds[i]; }
-    s.filterRadius[0] = d->film.filter_radius[0]; s.filterRadius[1] = d->film.filter_radius[1];
-    s.maxSampleLuminance = d->film.max_sample_luminance;
-    for (int i = 0; i < 2; ++i) { s.baseScales[i] = d->sampler.base_scales[i]; s.baseExponents[i] = d->sampler.base_exponents[i]; s.multInverse[i] = d->sampler.mult_inverse[i]; }
-    s.sampleStride = d->sampler.sample_stride;
-    s.sampleAtPixelCenter = d->sampler.sample_at_pixel_center;
-    s.samplerType = d->sampler.type;
-    s.samplesPerPixel = d->sampler.samples_per_pixel;
-    s.index32 = 0; s.storePixelSample = 1;
-    s.ignoreRayWeight = 0;
-    s.pixelDims = d->sampler.pixel_dims; s.xSamples = d->sampler.x_samples; s.ySamples = d->sampler.y_samples; s.jitter = d->sampler.jitter;
-    s.sobolResolution = d->sampler.sobol_resolution;
-    s.sobolLog2Resolution = d->sampler.sobol_log2_resolution;
-    s.maxDepth = d->integrator.max_depth;
-    s.rrThreshold = d->integrator.rr_threshold;
-    s.nBands = d->integrator.n_ca_bands;
-    s.bandDelta = (int)std::round((float)MI_NSPEC / (float)s.nBands);  // spectralpath.cpp:258
-    if (d->n_nodes) for (int i = 0; i < 3; ++i) { s.wbMin[i] = d->nodes[0].bmin[i]; s.wbMax[i] = d->nodes[0].bmax[i]; }
-    s.ldType = d->light_distrib.type;
-    for (int i = 0; i < 3; ++i) s.nVoxels[i] = d->light_distrib.n_voxels[i];
-    pt->hasAlphaMasks = h.hasAlphaMasks;
-    pt->hasInstances = d->n_instances > 0;
-    pt->hasQuadrics = h.hasQuadrics;
-    pt->nQuadrics = d->n_spheres + d->n_disks;
-    pt->samplerDims = d->sampler.n_dims;
-    for (uint32_t i = 0; i < d->n_lights; ++i) pt->lightTypes.push_back(d->lights[i].type);
-    for (uint32_t i = 0; i < d->n_materials; ++i) {
-        const mi_material &m = d->materials[i];
-        const bool tex = m.textured || m.bump_tex >= 0 || m.rough_tex[0] >= 0 || m.rough_tex[1] >= 0 || m.sigma_tex >= 0;
-        pt->materialLobes.push_back(tex ? -1 - m.n_bxdfs : m.n_bxdfs);
-    }
-    pt->hasInfiniteLight = h.classes.hasInfiniteLight;
-    memcpy(pt->shadeClasses, h.classes.shadeClasses, sizeof(pt->shadeClasses));
-    pt->nTextures = d->n_textures;
-    for (uint32_t i = 0; i < d->n_textures; ++i) pt->textureTypes.push_back(d->textures[i].type);
-    pt->spp = d->sampler.samples_per_pixel;
-    if (d->prim_meta) pt->primMetaHost.assign(d->prim_meta, d->prim_meta + d->n_prims);
-}
-
-// The description's arrays and the host tables into device memory. Environment maps and image pyramids go as their
-// tables first, then as the records that point at them.
-int UploadScene(mi_pt *pt, const mi_scene_desc *d, const HostTables &h) {
-    DScene &s = pt->scene;
-    Uploads up{pt};
-    up((const float4 *)d->nodes, (size_t)d->n_nodes * 2, s.nodes);
-    if (!h.bvh.wnodes.empty()) up(h.bvh.wnodes.data(), h.bvh.wnodes.size(), s.wnodes);
-    if (!h.bvh.instWideRoot.empty()) {
-        up(h.bvh.instWideRoot.data(), h.bvh.instWideRoot.size(), s.instWideRoot);
-        up(h.bvh.instRootBounds.data(), h.bvh.instRootBounds.size(), s.instRootBounds);
-    }
-    up(h.primTri.data(), h.primTri.size(), s.primTri);
-    up(d->prims, d->n_prims, s.prims);
-    if (d->n_instances) up(d->instances, d->n_instances, s.instances);
-    if (d->n_motions) { up(d->motions, d->n_motions, s.motions); s.timePlane = TimePlaneOf(s); }
-    up(d->tri_indices, (size_t)d->n_tris * 3, s.triIndices);
-    up(d->tri_mesh, d->n_tris, s.triMesh);
-    up(d->P, (size_t)d->n_verts * 3, s.P);
-    up(d->N, (size_t)d->n_verts * 3, s.N);
-    up(d->UV, (size_t)d->n_verts * 2, s.UV);
-    up(d->meshes, d->n_meshes, s.meshes);
-    up(d->spheres, d->n_spheres, s.spheres);
-    up(d->disks, d->n_disks, s.disks);
-    s.nSpheres = (int)d->n_spheres;
-    up(d->materials, d->n_materials, s.materials);
-    up(d->lights, d->n_lights, s.lights);
-    up(&d->camera, 1, s.cameraMotion);
-    if (d->camera_type == MI_CAMERA_REALISTIC) up(d->lens, 1, s.lens);   // (the by-value record now points at the device copy)
-    up(h.lightBounds.data(), h.lightBounds.size(), s.lightBounds);
-    up(h.lightPrim.data(), h.lightPrim.size(), s.lightPrim);
-    up(d->sampler.primes, d->sampler.n_dims, s.primes);
-    up(d->sampler.prime_sums, d->sampler.n_dims, s.primeSums);
-    up(d->sampler.perms, d->sampler.n_perms, s.perms);
-    up(d->film.filter_table, 256, s.filterTable);
-    if (d->sampler.type == MI_SAMPLER_SOBOL) {
-        up(d->sampler.sobol_matrices, (size_t)d->sampler.n_sobol_dims * MI_SOBOL_MATRIX_SIZE, s.sobolMatrices);
-        up(d->sampler.sobol_vdc, (size_t)MI_SOBOL_MATRIX_SIZE, s.sobolVdc);
-        up(d->sampler.sobol_vdc_inv, (size_t)MI_SOBOL_MATRIX_SIZE, s.sobolVdcInv);
-    }
-    up(h.primeMagic.data(), h.primeMagic.size(), s.primeMagic);
-    up(h.haltonDims.data(), h.haltonDims.size(), s.haltonDims);
-    up(h.pixelOffsets.data(), h.pixelOffsets.size(), s.pixelOffsetTable);
-    std::vector<mi_envmap> envs(d->envmaps, d->envmaps + d->n_envmaps);
-    for (mi_envmap &m : envs) {
-        const mi_envmap e = m;
-        up(e.rgb, (size_t)e.width * e.height * 3, m.rgb);
-        up(e.cond_func, (size_t)e.nu * e.nv, m.cond_func);
-        up(e.cond_cdf, (size_t)(e.nu + 1) * e.nv, m.cond_cdf);
-        up(e.cond_func_int, (size_t)e.nv, m.cond_func_int);
-        up(e.marg_func, (size_t)e.nv, m.marg_func);
-        up(e.marg_cdf, (size_t)e.nv + 1, m.marg_cdf);
-    }
-    if (!envs.empty()) up(envs.data(), envs.size(), s.envmaps);
-    up(&d->rgb_illum[0][0], (size_t)7 * MI_NSPEC, s.rgbIllum);
-    std::vector<mi_mipmap> mips(d->mipmaps, d->mipmaps + d->n_mipmaps);
-    for (mi_mipmap &m : mips) {
-        size_t nTexels = 0;
-        for (int l = 0; l < m.n_levels; ++l) nTexels = std::max<size_t>(nTexels, (size_t)m.level_offset[l] + (size_t)std::max(1, m.width >> l) * std::max(1, m.height >> l));
-        const float *texels = m.texels;
-        up(texels, nTexels * 3, m.texels);
-    }
-    if (!mips.empty()) up(mips.data(), mips.size(), s.mipmaps);
-    // (a spectrum noise value v reaches the lobes in the checkerboard's compact form: (1 - v) * spec1 + v * spec2 with spec1 = 0,
-    // spec2 = 1 is v in every bin -- EvalImageTexture, TexBin)
-    std::vector<mi_texture> texs(d->textures, d->textures + d->n_textures);
-    for (mi_texture &t : texs)
-        if (MI_TEX_IS_NOISE(t.type))
-            for (int b = 0; b < MI_NSPEC; ++b) { t.spec1[b] = 0.f; t.spec2[b] = 1.f; }
-    if (!texs.empty()) up(texs.data(), texs.size(), s.textures);
-    up(h.ewaWeights.data(), h.ewaWeights.size(), s.ewaWeights);
-    return up.rc;
-}
-
-// The tables that kernels build at create: the pixel samplers' tables (every sampled dimension of every sample of every
-// pixel of the sample bounds, 12 bytes each: StartPixel of the reference, done once for all pixels) and the spatial light
-// distribution; the other light distributions are uploaded as they are.
-int BuildDeviceTables(mi_pt *pt, const mi_scene_desc *d) {
-    DScene &s = pt->scene;
-    int rc = MI_OK;
-    if (d->sampler.type >= MI_SAMPLER_ZEROTWO && d->sampler.pixel_dims > 0) {
-        const size_t nPix = (size_t)(s.sampleBounds[2] - s.sampleBounds[0]) * (size_t)(s.sampleBounds[3] - s.sampleBounds[1]);
-        const size_t nVal = nPix * (size_t)s.pixelDims * (size_t)s.samplesPerPixel;
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { (void)hipGetLastError(); freeB = ~(size_t)0; }
-        if (nVal * 12 > freeB / 2) { g_err = "the pixel sampler's tables (" + std::to_string(nVal * 12 >> 20) + " MiB) exceed half the free device memory"; return MI_ERR_NOMEM; }
-        float *t1 = nullptr, *t2 = nullptr;
-        if ((rc = Alloc(pt, nVal * 4 + 16, &t1, "pixel sampler tables")) != MI_OK || (rc = Alloc(pt, nVal * 8 + 16, &t2, "pixel sampler tables")) != MI_OK) return rc;
-        s.pixTab1 = t1; s.pixTab2 = t2;
-        hipLaunchKernelGGL(k_pixel_tables, dim3((unsigned)((nPix + 127) / 128)), dim3(128), 0, 0, s, t1, t2, (unsigned long long)nPix);
-        if (hipDeviceSynchronize() != hipSuccess) { g_err = "k_pixel_tables failed"; return MI_ERR_HIP; }
-    }
-    Uploads up{pt};
-    if (d->n_lights == 0) {
-        up((const float *)nullptr, 0, s.ldFunc); up((const float *)nullptr, 0, s.ldCdf); up((const float *)nullptr, 0, s.ldFuncInt);
-        return up.rc;
-    }
-    if (s.ldType != MI_LD_SPATIAL) {
-        up(d->light_distrib.func, d->n_lights, s.ldFunc);
-        up(d->light_distrib.cdf, d->n_lights + 1, s.ldCdf);
-        up(d->light_distrib.func_int, 1, s.ldFuncInt);
-        return up.rc;
-    }
-    const size_t nVox = (size_t)s.nVoxels[0] * s.nVoxels[1] * s.nVoxels[2];
-    float *f = nullptr, *c = nullptr, *fi = nullptr;
-    if ((rc = Alloc(pt, nVox * d->n_lights * 4, &f, "light distribution")) != MI_OK || (rc = Alloc(pt, nVox * (d->n_lights + 1) * 4, &c, "light distribution")) != MI_OK ||
-        (rc = Alloc(pt, nVox * 4, &fi, "light distribution")) != MI_OK) return rc;
-    s.ldFunc = f; s.ldCdf = c; s.ldFuncInt = fi;
-    hipLaunchKernelGGL(k_build_spatial, dim3((unsigned)((nVox + 127) / 128)), dim3(128), 0, 0, s, f, c, fi, (uint32_t)nVox);
-    if (hipDeviceSynchronize() != hipSuccess) { g_err = "k_build_spatial failed"; return MI_ERR_HIP; }
-    return MI_OK;
-}
-
-// The film, and per sub-renderer (concurrent on their own streams; MIPT_STREAMS overrides their count, 1..8) the
-// counters, the stream and the events.
-int CreateRenderState(mi_pt *pt, const mi_scene_desc *d) {
-    pt->filmW = d->film.cropped_bounds[2] - d->film.cropped_bounds[0];
-    pt->filmH = d->film.cropped_bounds[3] - d->film.cropped_bounds[1];
-    pt->nPix = (size_t)pt->filmW * pt->filmH;
-    int rc = Alloc(pt, pt->nPix * 32 * sizeof(float), &pt->film, "film");
-    if (rc != MI_OK) return rc;
-    hipMemset(pt->film, 0, pt->nPix * 32 * sizeof(float));
-    int nSub = 1;
-    if (const char *e = getenv("MIPT_STREAMS")) nSub = std::max(1, std::min(8, atoi(e)));
-    pt->subs.resize(nSub);
-    for (SubRenderer &sub : pt->subs) {
-        if ((rc = Alloc(pt, sizeof(DevCounters), &sub.ctr, "counters")) != MI_OK) return rc;
-        if (hipHostMalloc((void **)&sub.reads, sizeof(*sub.reads), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            sub.reads = nullptr;
-            g_err = "hipHostMalloc(per-iteration reads) failed";
-            return MI_ERR_NOMEM;
-        }
-        if (hipStreamCreateWithFlags(&sub.stream, hipStreamNonBlocking) != hipSuccess) { g_err = "hipStreamCreate failed"; return MI_ERR_HIP; }
-        for (int a = 0; a < 2; ++a)
-            for (int b = 0; b < N_EV; ++b)
-                if (hipEventCreate(&sub.evIter[a][b]) != hipSuccess) { g_err = "hipEventCreate failed"; return MI_ERR_HIP; }
-        int prioLeast = 0, prioGreatest = 0;   // (the lowest priority: the dark traversal fills what the main stream leaves idle)
-        if (hipDeviceGetStreamPriorityRange(&prioLeast, &prioGreatest) != hipSuccess) { (void)hipGetLastError(); prioLeast = 0; }
-        if (hipStreamCreateWithPriority(&sub.darkStream, hipStreamNonBlocking, prioLeast) != hipSuccess) { g_err = "hipStreamCreate failed"; return MI_ERR_HIP; }
-        hipEvent_t *darkEvents[] = {&sub.evDarkGo, &sub.evDarkDone, &sub.evDark[0][0], &sub.evDark[0][1], &sub.evDark[1][0], &sub.evDark[1][1]};
-        for (int k = 0; k < 6; ++k)   // (the two that only order the streams carry no timestamp)
-            if (hipEventCreateWithFlags(darkEvents[k], k < 2 ? hipEventDisableTiming : hipEventDefault) != hipSuccess) { g_err = "hipEventCreate failed"; return MI_ERR_HIP; }
-    }
-    return MI_OK;
-}
-
-// -----------------------------------------------------------------------------
-// The launches of one wavefront iteration, shared by RenderSub, the path-dump tool and mi_pt_trace_wavefront
-// -----------------------------------------------------------------------------
-using SceneKernel = void (*)(DScene, Pool, DevCounters *);
-
-// The k_trav instance of a ray class for the scene. Scenes with object instances always have the wide-4 records
-// (BuildBvhTables) and never MODE 3 (misAny is 0 for them): three instances serve them.
-template <int MODE>
-SceneKernel TravKernel(const mi_pt *pt) {
-    if (pt->hasInstances)   // (never asked for MODE 3 or 4)
-        return pt->scene.motions ? k_trav<MODE >= 3 ? 2 : MODE, true, 4, true, true> : k_trav<MODE >= 3 ? 2 : MODE, true, 4, true>;
-    const bool w4 = pt->scene.bvhWidth == 4;
-    if (pt->hasAlphaMasks) return w4 ? k_trav<MODE, true, 4> : k_trav<MODE, true, 2>;
-    return w4 ? k_trav<MODE, false, 4> : k_trav<MODE, false, 2>;
-}
-
-// `closestMis`: the MIS rays (mode 2) with the closest-hit kernel even where the scene could ask them as visibility queries.
-// Mode 4: the dark MIS rays of Pool::darkQ (DScene::misAny scenes only). `beside`: on that stream and on exactly `travGrid`.
-void LaunchTraversal(mi_pt *pt, SubRenderer &sub, int mode, dim3 travGrid, bool closestMis = false, hipStream_t beside = nullptr) {
-    if (mode == 2 && pt->scene.misAny && !closestMis) mode = 3;   // the MIS rays as visibility queries (k_trav, MODE 3)
-    if (!beside && TRAV_IS_ANY(mode) && !pt->hasAlphaMasks && !pt->hasInstances && travGrid.x == (unsigned)pt->numCUs * TRAV_BLOCKS_PER_CU) travGrid.x = (unsigned)pt->numCUs * MIPT_TRAV_WAVES_PER_EU_ANY;   // (a full-size launch: one more block per CU)
-    const SceneKernel k = mode == 0 ? TravKernel<0>(pt) : mode == 1 ? TravKernel<1>(pt) : mode == 3 ? TravKernel<3>(pt) : mode == 4 ? TravKernel<4>(pt) : TravKernel<2>(pt);
-    hipLaunchKernelGGL(k, travGrid, dim3(BLOCK), 0, beside ? beside : sub.stream, pt->scene, sub.pool, sub.ctr);
-}
-
-// The dark MIS rays (DScene::misAny: Pool::darkQ, k_trav<4>). Nothing inside the iteration reads what the kernel does -- it
-// adds to regularRays, nodesVisited and triTests -- so it need not stand in the chain of dependent launches: it runs on
-// SubRenderer::darkStream from the end of k_shade, beside the shadow and live MIS stages and the next iteration's k_generate,
-// k_trav<0> and k_resolve_extend, on a grid small enough to leave those their blocks. It reads darkQ and the R_MI planes,
-// whose next writer is the next k_shade: LaunchShade waits for evDarkDone. All ordering is stream events.
-// MIPT_DARK_BLOCKS_PER_CU: the grid of that launch. MIPT_DARK_AFTER_SHADOW: hand over after k_resolve_shadow instead.
-#ifndef MIPT_DARK_BLOCKS_PER_CU
-#define MIPT_DARK_BLOCKS_PER_CU 3   // (same-box A/B of 1, 2, 3, 5 at both hand-over points: DESIGN.md, round 7)
-#endif
-#ifndef MIPT_DARK_AFTER_SHADOW
-#define MIPT_DARK_AFTER_SHADOW 0
-#endif
-static_assert(MIPT_DARK_BLOCKS_PER_CU >= 1 && MIPT_DARK_BLOCKS_PER_CU <= MIPT_TRAV_WAVES_PER_EU_ANY, "MIPT_DARK_BLOCKS_PER_CU: 1 .. the blocks of the any-hit kernels that a CU holds");
-static_assert(MIPT_DARK_AFTER_SHADOW == 0 || MIPT_DARK_AFTER_SHADOW == 1, "MIPT_DARK_AFTER_SHADOW: 0 or 1");
-
-// The time of the launch in evDark[k] into the MIS class. Called when the host knows that launch complete.
-void HarvestDark(SubRenderer &sub, int k) {
-    if (!sub.darkTimed[k]) return;
-    sub.darkTimed[k] = false;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, sub.evDark[k][0], sub.evDark[k][1]) == hipSuccess) sub.t[5] += ms * 1e-3;
-    else (void)hipGetLastError();   // (a time not had is no reason to stop the render, and must not be taken for a launch's error)
-}
-
-int LaunchDarkBeside(mi_pt *pt, SubRenderer &sub, unsigned poolBlocks) {
-    const int k = (int)(sub.darkSeq & 1);
-    // the launch before the last used this set: the k_shade after it waited for its end, and the host has waited for the
-    // main stream since (the read after k_generate)
-    HarvestDark(sub, k);
-    HIPCHK(hipEventRecord(sub.evDarkGo, sub.stream));
-    HIPCHK(hipStreamWaitEvent(sub.darkStream, sub.evDarkGo, 0));
-    HIPCHK(hipEventRecord(sub.evDark[k][0], sub.darkStream));
-    LaunchTraversal(pt, sub, 4, dim3(std::min(poolBlocks, (unsigned)pt->numCUs * MIPT_DARK_BLOCKS_PER_CU)), false, sub.darkStream);
-    HIPCHK(hipEventRecord(sub.evDark[k][1], sub.darkStream));
-    HIPCHK(hipMemsetAsync(&sub.ctr->darkCount, 0, DARK_CLEAR_BYTES, sub.darkStream));
-    HIPCHK(hipEventRecord(sub.evDarkDone, sub.darkStream));
-    sub.darkTimed[k] = true;
-    sub.darkPending = true;
-    ++sub.darkSeq; ++sub.darkLaunches;
-    return MI_OK;
-}
-
-// MIPT_DARK_STREAM=0, and the tools that step through an iteration: the same kernel in line, after the live MIS stage.
-int LaunchDarkInLine(mi_pt *pt, SubRenderer &sub, dim3 travGrid) {
-    LaunchTraversal(pt, sub, 4, travGrid);
-    HIPCHK(hipMemsetAsync(&sub.ctr->darkCount, 0, DARK_CLEAR_BYTES, sub.stream));
-    ++sub.darkLaunches;
-    return MI_OK;
-}
-
-// Before the next writer of darkQ and the R_MI planes, and before the counters are read: the main stream behind the dark one.
-int JoinDark(SubRenderer &sub) {
-    if (sub.darkPending) HIPCHK(hipStreamWaitEvent(sub.stream, sub.evDarkDone, 0));
-    sub.darkPending = false;
-    return MI_OK;
-}
-
-// The grid of a kernel that walks a queue in steps of the grid (k_resolve_shadow, k_resolve_mis): QUEUE_GRID_RESIDENT times the
-// blocks the device holds at once, at most the `poolBlocks` that cover the longest queue there can be. A block that finds
-// its queue ended is not free, and a pool-sized grid has 390 k of them (0.18 ms per launch, however short the queue).
-// MIPT_QUEUE_BLOCKS (read at every render; for tests) caps the grid.
-#ifndef MIPT_QUEUE_GRID_RESIDENT
-#define MIPT_QUEUE_GRID_RESIDENT 4
-#endif
-constexpr unsigned QUEUE_GRID_RESIDENT = MIPT_QUEUE_GRID_RESIDENT;
-static_assert(QUEUE_GRID_RESIDENT >= 1 && QUEUE_GRID_RESIDENT <= 64, "MIPT_QUEUE_GRID_RESIDENT: 1..64");
-dim3 QueueGrid(const mi_pt *pt, int blocksPerCU, unsigned poolBlocks) {
-    unsigned want = (unsigned)pt->numCUs * (unsigned)std::max(1, blocksPerCU) * QUEUE_GRID_RESIDENT;
-    if (pt->queueBlocksCap) want = std::min(want, pt->queueBlocksCap);
-    return dim3(std::max(1u, std::min(want, poolBlocks)));
-}
-void ReadQueueBlocksCap(mi_pt *pt) {
-    const char *e = getenv("MIPT_QUEUE_BLOCKS");
-    pt->queueBlocksCap = e ? (unsigned)std::max(0, atoi(e)) : 0u;
-    e = getenv("MIPT_SHADE_GRID");   // (read with it, at every render: "pool" = the grids before the class counts sized them)
-    pt->shadeGridPool = e && strcmp(e, "pool") == 0;
-    e = getenv("MIPT_DARK_STREAM");   // (likewise: "0" = the dark MIS rays in line on the main stream)
-    pt->darkInLine = e && strcmp(e, "0") == 0;
-}
-// The resolve kernels of the three ray classes, by [class][instanced].
-const SceneKernel kResolve[3][2] = {{k_resolve_extend<false>, k_resolve_extend<true>},
-                                    {k_resolve_shadow<false>, k_resolve_shadow<true>},
-                                    {k_resolve_mis<false>, k_resolve_mis<true>}};
-
-// Resident blocks per CU of the two resolve kernels that walk a queue.
-int QueryQueueOccupancy(mi_pt *pt) {
-    for (int mode = 1; mode < 3; ++mode) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kResolve[mode][pt->hasInstances ? 1 : 0], BLOCK, 0) != hipSuccess || nb < 1) { g_err = "occupancy query failed"; return MI_ERR_HIP; }
-        pt->resolveBlocksPerCU[mode] = nb;
-    }
-#ifdef MIPT_TRAV_STATS
-    {   // the traversal kernels of the scene: the grids above count on 4 blocks per CU closest-hit, 5 any-hit
-        const SceneKernel ks[5] = {TravKernel<0>(pt), TravKernel<1>(pt), TravKernel<2>(pt), TravKernel<3>(pt), TravKernel<4>(pt)};
-        for (int mode = 0; mode < 5; ++mode) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)ks[mode], BLOCK, 0) != hipSuccess) nb = -1;
-            fprintf(stderr, "TRAVSTAT k_trav<%d> blocks per CU %d\n", mode, nb);
-        }
-    }
-#endif
-    return MI_OK;
-}
-
-// What follows the traversal of ray class `mode` (0: path rays, 1: shadow rays, 2: MIS rays): its resolve kernel on `grid`,
-// then k_resolve_overflow for the rays that the quadric lists or the visibility queries (MODE 3) handed over.
-void LaunchResolve(mi_pt *pt, SubRenderer &sub, int mode, dim3 grid) {
-    const bool inst = pt->hasInstances;
-    if (mode != 0) grid = QueueGrid(pt, pt->resolveBlocksPerCU[mode], grid.x);   // (k_resolve_extend takes the pool's slots, not a queue)
-    hipLaunchKernelGGL(kResolve[mode][inst ? 1 : 0], grid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr);
-    if (pt->hasQuadrics || (mode == 2 && pt->scene.misAny))
-        hipLaunchKernelGGL((inst ? (pt->scene.motions ? k_resolve_overflow<true, true> : k_resolve_overflow<true>) : k_resolve_overflow<false>), dim3(OVERFLOW_GRID), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, mode);
-}
-
-// The last stage of a metadata pass (instead of LaunchShade and the shadow and MIS stages): every slot, one per thread.
-void LaunchMetadataCommit(mi_pt *pt, SubRenderer &sub, dim3 grid) {
-    hipLaunchKernelGGL((pt->hasInstances ? (pt->scene.motions ? k_commit_metadata<true, true> : k_commit_metadata<true>) : k_commit_metadata<false>), grid, dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool,
-                       pt->primMeta, pt->metaStrategy);
-}
-
-// The blocks that k_shade needs for the queues of `classes`: the kernel's prologue lays them back to back, each padded to
-// whole blocks on its own, so the sum of the ceilings and not the ceiling of the sum.
-unsigned long long ShadeGridBlocks(const uint32_t *counts, unsigned classes) {
-    unsigned long long blocks = 0;
-    for (int c = 0; c < MAX_CLASSES; ++c)
-        if ((classes >> c) & 1u) blocks += ((unsigned long long)counts[c] + BLOCK - 1) / BLOCK;
-    return blocks;
-}
-
-// The shading queues' lengths of this iteration, on the host: one copy of the 16 cursors (a line each) into the
-// sub-renderer's pinned block and one wait. After LaunchResolve(.., 0, ..), whose k_resolve_overflow appends to the queues too.
-int ReadShadeCounts(SubRenderer &sub, uint32_t *counts) {
-    HIPCHK(hipMemcpyAsync(sub.reads->shadeCount, sub.ctr->shadeCount, sizeof(sub.reads->shadeCount), hipMemcpyDeviceToHost, sub.stream));
-    HIPCHK(hipStreamSynchronize(sub.stream));
-    for (int c = 0; c < MAX_CLASSES; ++c) counts[c] = sub.reads->shadeCount[c].v;
-    return MI_OK;
-}
-
-// Every k_shade instance of the plan on the blocks its queues fill (an instance with empty queues is not launched): a
-// block past the queues is not free (1.4 ns each, 0.53 ms per launch on the 96M-slot pool's 393 232), and in a full iteration
-// the instances share one pool's worth of vertices. The price is a host round trip per iteration (ReadShadeCounts).
-// MIPT_SHADE_GRID=pool: `grid` (the pool's blocks) + MAX_CLASSES for every instance, as before, and no read.
-int LaunchShade(mi_pt *pt, SubRenderer &sub, dim3 grid) {
-    uint32_t counts[MAX_CLASSES];
-    if (!pt->shadeGridPool) {
-        const int rc = ReadShadeCounts(sub, counts);
-        if (rc != MI_OK) return rc;
-    }
-    {   // (behind the read, so that the host does not wait for the dark traversal as well)
-        const int rc = JoinDark(sub);
-        if (rc != MI_OK) return rc;
-    }
-    for (int i = 0; i < N_SHADE_INSTANCES; ++i) {
-        if (!pt->shadeClasses[i]) continue;
-        const unsigned long long blocks = pt->shadeGridPool ? (unsigned long long)grid.x + MAX_CLASSES : ShadeGridBlocks(counts, pt->shadeClasses[i]);
-        if (blocks == 0) continue;
-        const ShadeInstance &si = kShadeInstances[i];
-        const bool lens = pt->scene.lensDiff && si.kernel[0][1];   // (a realistic camera in front of textures: the twin that loads the stored differentials)
-        const bool motion = pt->scene.motions && si.kernel[1][0];   // (moving instances: the twin that interpolates)
-        hipLaunchKernelGGL(si.kernel[motion][lens], dim3((unsigned)blocks), dim3(BLOCK), 0, sub.stream, pt->scene, sub.pool, sub.ctr, pt->shadeClasses[i]);
-        ++sub.shadeLaunches;
-        sub.shadeBlocks += blocks;
-    }
-    return MI_OK;
-}
-
-// Tiles of 16 samples along one axis of the sample bounds.
-int TilesAlong(const DScene &s, int axis) { return (s.sampleBounds[2 + axis] - s.sampleBounds[axis] + 15) / 16; }
-
-// The work of one pass of one sub-renderer: of the 16 x 16 tiles of the sample bounds every shardCount-th from shardIndex on,
-// `spp` samples from sample number `sampleBegin` in each of their pixels, handed out in runs (MIPT_WORK_RUN caps them).
-// mi_pt_debug_path asks the same way for the one tile of its pixel.
-WorkDesc PlanWork(const DScene &s, int shardIndex, int shardCount, long long spp, long long sampleBegin) {
-    WorkDesc wd{};
-    wd.nTilesX = TilesAlong(s, 0);
-    wd.nTilesY = TilesAlong(s, 1);
-    const int nTiles = wd.nTilesX * wd.nTilesY;
-    wd.shardIndex = shardIndex;
-    wd.shardCount = shardCount;
-    wd.nTilesShard = (wd.shardIndex < nTiles) ? (nTiles - wd.shardIndex + wd.shardCount - 1) / wd.shardCount : 0;
-    wd.spp = spp;
-    wd.sampleBegin = sampleBegin;
-    wd.totalWork = (unsigned long long)wd.nTilesShard * 256ull * (unsigned long long)wd.spp;
-    int runCap = 256;  // (round 3, with the dense film flush: 64 -> 256 takes 5 % off k_generate, killeroo +0.9 %, the 10M-triangle scene
-                       // +0.7 %, cornell-glass the same; 1024 measures as 256. Same-box A/B at the end of round 2: 16 -> 64 took 4 % off k_generate and 1 % off the camera-ray
-                       // traversal, the other kernels unchanged -- 3596 -> 3620 Mray/s; 128 ... 1024 measure the same as 64.
-                       // Earlier in the round longer runs cost the shading kernels 2-5 % and 16 was the optimum.)
-    if (const char *e = getenv("MIPT_WORK_RUN")) runCap = std::max(1, atoi(e));
-    wd.run = 1;
-    while (2 * wd.run <= runCap && wd.spp % (2 * wd.run) == 0) wd.run *= 2;
-    return wd;
-}
-
-// The pool of a render of `wd` on one of `subCount` sub-renderers, its slots of nQuadPlanes and nFloatPlanes: `pathPool` slots
-// in all (mi_render_params.path_pool), or by default what the work, the measurements below and the device's free memory
-// ask for. Allocated (EnsurePool) when this returns MI_OK, `poolN` slots.
-int SizePool(SubRenderer &sub, const WorkDesc &wd, uint32_t pathPool, int subCount, int nQuadPlanes, int nFloatPlanes, uint32_t &poolN) {
-    // Default pool: one slot per sample to render, up to the cap (earlier in round 2, at half: a 1/8 shard took 0.1196 s with the
-    // quarter's 16M slots, 0.1169 s with 32M), at most 96M slots in total (below)
-    // and at least 4M (8M per sub-renderer when several share the GPU): bigger pools mean fewer, better-filled
-    // launches, but the last iterations of a render drain the pool at low occupancy, which a small job (one
-    // shard of a multi-GPU frame) feels. Measured on the 1024-spp killeroo frame and its shards
-    // (tools/shard_tune.py): a 1/8 shard on four sub-renderers takes 0.149 s with 16M slots and 0.143 s with
-    // 32M; 64M slots (47 GB) make the traversal launches 3 % faster and k_shade / k_generate 4-6 % slower
-    // (the path state outgrows the TLB reach), no gain for the full frame.
-    poolN = pathPool;
-    if (poolN == 0) {
-        const unsigned long long quarter = wd.totalWork * (unsigned long long)subCount;   // (all of them: a 1/8 shard of the killeroo frame takes 0.1071 s on 32M slots, 0.1046 s on 64M)
-        const unsigned long long floorN = subCount > 1 ? (8ull << 20) * (unsigned long long)subCount : (1ull << 22);
-        // (`quarter`: half, since round 2.) The cap: 96M slots = 77 GB of path state of the 288 GB. With the kernels of the end
-        // of round 2 bigger pools pay again (fewer, longer launches: the persistent traversal kernels lose less to their
-        // tails, k_shade and k_generate no longer slow down): killeroo 1024 spp 3740 Mray/s at 32M, 3880 at 64M, 3912 at
-        // 96M, 3931 at 128M; the 10M-triangle scene +0.4 %, cornell-glass -0.3 % at 64M.
-        poolN = (uint32_t)std::min<unsigned long long>(3ull << 25, std::max<unsigned long long>(floorN, quarter));
-    }
-    poolN = std::max<uint32_t>(BLOCK, poolN / subCount / BLOCK * BLOCK);
-    if (pathPool == 0) {
-        // the default is a preference: it takes at most 65 % of what the device has free (counting what this sub-renderer's
-        // present pool would give back), so that what comes after the pool -- the film staging of the hand-over, RCCL's
-        // buffers at the first collective, another renderer in the process -- still finds memory
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-            const size_t budget = (size_t)(0.65 * (double)(freeB + sub.poolBytes)) / (size_t)subCount;
-            const size_t fit = budget / PoolSlotBytes(nQuadPlanes, nFloatPlanes) / BLOCK * BLOCK;
-            if (fit < poolN) poolN = (uint32_t)std::max<size_t>(fit, (size_t)BLOCK);
-        } else (void)hipGetLastError();
-    }
-    if (wd.totalWork < poolN) poolN = (uint32_t)((wd.totalWork + BLOCK - 1) / BLOCK * BLOCK);
-    if (poolN < BLOCK) poolN = BLOCK;
-    int rc = EnsurePool(sub, poolN, nQuadPlanes, nFloatPlanes);
-    // the default size is a preference, not a requirement: on a device that cannot hold it the render goes on with half,
-    // a quarter, ... (an explicit mi_render_params.path_pool is taken at its word and fails)
-    while (rc == MI_ERR_NOMEM && pathPool == 0 && poolN > (1u << 22)) {
-        poolN = poolN / 2 / BLOCK * BLOCK;
-        rc = EnsurePool(sub, poolN, nQuadPlanes, nFloatPlanes);
-    }
-    return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-const char *mi_pt_last_error(void) { return g_err.c_str(); }
-
-int mi_pt_create(const mi_scene_desc *d, int device_ordinal, mi_pt **out) {
-    if (!d || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (d->abi_version != MI_ABI_VERSION) { g_err = "mi_scene_desc ABI version mismatch"; return MI_ERR_INVALID; }
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev == 0) { g_err = "no HIP device available (this path has no CPU fallback)"; return MI_ERR_NO_DEVICE; }
-    if (device_ordinal < 0 || device_ordinal >= nDev) { g_err = "device ordinal out of range"; return MI_ERR_NO_DEVICE; }
-    int rc = CheckSceneDesc(d);
-    if (rc != MI_OK) return rc;
-    HostTables h;
-    if ((rc = BuildHostTables(d, h)) != MI_OK) return rc;
-    HIPCHK(hipSetDevice(device_ordinal));
-    mi_pt *pt = new mi_pt();
-    pt->device = device_ordinal;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess && prop.multiProcessorCount > 0) pt->numCUs = prop.multiProcessorCount;
-    SetSceneFields(pt, d, h);
-    rc = UploadScene(pt, d, h);
-    if (rc == MI_OK) rc = BuildDeviceTables(pt, d);
-    if (rc == MI_OK) rc = CreateRenderState(pt, d);
-    if (rc == MI_OK) rc = QueryQueueOccupancy(pt);
-    if (rc != MI_OK) {   // the one exit of a failed create: whatever was built is registered in pt
-        mi_pt_destroy(pt);
-        return rc;
-    }
-    *out = pt;
-    return MI_OK;
-}
-
-// One sub-renderer = one path pool with its queues and counters on its own HIP stream.
-// mi_pt_render splits its tile shard over pt->subs.size() sub-renderers that run
-// concurrently (one host thread each): while one pool is in a traversal kernel's tail
-// the other pool's kernels fill the idle CUs, which a single dependent chain of launches
-// cannot do.
-static int RenderSub(mi_pt *pt, SubRenderer &sub, const mi_render_params *rp, int subIndex, int subCount) {
-    HIPCHK(hipSetDevice(pt->device));
-    hipStream_t st = sub.stream;
-    const DScene &s = pt->scene;
-    const WorkDesc wd = PlanWork(s, rp->shard_index + rp->shard_count * subIndex, rp->shard_count * subCount, PassSpp(pt, rp), rp->sample_begin);
-    sub.iterations = 0;
-    sub.shadeLaunches = sub.shadeBlocks = 0;
-    // (a render that failed half way may have left the dark stream busy: nothing of it may meet this render's clears)
-    HIPCHK(hipStreamSynchronize(sub.darkStream));
-    sub.darkPending = false; sub.darkTimed[0] = sub.darkTimed[1] = false;
-    sub.darkLaunches = 0;
-    for (double &t : sub.t) t = 0;
-    sub.result = DevCounters{};
-    if (wd.totalWork == 0) return MI_OK;
-    uint32_t poolN = 0;
-    int rc = SizePool(sub, wd, rp->path_pool, subCount, QuadPlanes(s), FloatPlanes(s), poolN);
-    if (rc != MI_OK) return rc;
-    HIPCHK(hipMemsetAsync(sub.pool.i + (size_t)I_FLAGS * poolN, 0, (size_t)poolN * sizeof(int), st));
-    HIPCHK(hipMemsetAsync(sub.ctr, 0, sizeof(DevCounters), st));
-    const dim3 grid((poolN + BLOCK - 1) / BLOCK), block(BLOCK);
-    const dim3 chunkGrid((grid.x + SLOT_CHUNKS - 1) / SLOT_CHUNKS);   // kernels that take SLOT_CHUNKS x 256 slots per block
-    const dim3 travGrid(std::min<unsigned>(grid.x, (unsigned)pt->numCUs * TRAV_BLOCKS_PER_CU));
-    // Per-kernel-class time: HIP events at the kernel boundaries of every iteration,
-    // read back after the per-iteration sync that the alive counter needs anyway.
-    // (first event, second event, the class in SubRenderer::t that the time between them goes to)
-    static const int kSpans[][3] = {{0, 1, 1}, {1, 2, 2}, {2, 3, 3}, {3, 4, 4}, {4, 5, 5},
-                                    // the closest-hit traversal launch alone: from an event recorded right before it (after the host's
-                                    // per-iteration read of `alive`), so the host round trip is in [2] but not in [6]
-                                    {7, 6, 6}};
-    auto harvest = [&](int set, bool full) {   // (`full`: the iteration went on past k_generate, whose span comes first)
-        float ms = 0;
-        for (const int (&sp)[3] : kSpans) {
-            hipEventElapsedTime(&ms, sub.evIter[set][sp[0]], sub.evIter[set][sp[1]]); sub.t[sp[2]] += ms * 1e-3;
-            if (!full) return;
-        }
-    };
-    int set = 0;
-    bool havePrev = false;   // the other event set holds a full iteration whose times are not in sub.t yet
-    while (true) {
-        hipEvent_t *ev = sub.evIter[set];
-        HIPCHK(hipMemsetAsync(&sub.ctr->alive, 0, ITER_CLEAR_BYTES, st));
-        HIPCHK(hipEventRecord(ev[0], st));
-        hipLaunchKernelGGL(GenerateKernelOf(s), chunkGrid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
-        HIPCHK(hipEventRecord(ev[1], st));
-        HIPCHK(hipMemcpyAsync(&sub.reads->alive, &sub.ctr->alive.v, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&sub.reads->drawn, &sub.ctr->nextWork, sizeof(sub.reads->drawn), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const unsigned alive = sub.reads->alive;
-        const unsigned long long drawn = sub.reads->drawn;
-        if (havePrev) harvest(set ^ 1, true);
-        // done when no path is alive and every work item has been drawn (an iteration can draw nothing but items outside
-        // the pixel bounds and leave the pool empty with work still to hand out)
-        if (alive == 0) {
-            harvest(set, false);
-            if (drawn >= wd.totalWork) break;
-        } else {
-            HIPCHK(hipEventRecord(ev[7], st));
-            LaunchTraversal(pt, sub, 0, travGrid);
-            HIPCHK(hipEventRecord(ev[6], st));
-            LaunchResolve(pt, sub, 0, chunkGrid);
-            HIPCHK(hipEventRecord(ev[2], st));
-            if (pt->metaStrategy >= 0) {   // a metadata pass: the hit is the answer (its commit is timed as the shade class; no shadow or MIS rays)
-                LaunchMetadataCommit(pt, sub, grid);
-                HIPCHK(hipEventRecord(ev[3], st));
-                HIPCHK(hipEventRecord(ev[4], st));
-                HIPCHK(hipEventRecord(ev[5], st));
-            } else {
-                const bool darkBeside = s.misAny && !pt->darkInLine;
-                if ((rc = LaunchShade(pt, sub, grid)) != MI_OK) return rc;
-                HIPCHK(hipEventRecord(ev[3], st));
-                if (darkBeside && !MIPT_DARK_AFTER_SHADOW && (rc = LaunchDarkBeside(pt, sub, grid.x)) != MI_OK) return rc;
-                LaunchTraversal(pt, sub, 1, travGrid);
-                LaunchResolve(pt, sub, 1, grid);
-                HIPCHK(hipEventRecord(ev[4], st));
-                if (darkBeside && MIPT_DARK_AFTER_SHADOW && (rc = LaunchDarkBeside(pt, sub, grid.x)) != MI_OK) return rc;
-                LaunchTraversal(pt, sub, 2, travGrid);
-                LaunchResolve(pt, sub, 2, grid);
-                if (s.misAny && pt->darkInLine && (rc = LaunchDarkInLine(pt, sub, travGrid)) != MI_OK) return rc;
-                HIPCHK(hipEventRecord(ev[5], st));
-            }
-            HIPCHK(hipGetLastError());   // a launch of this iteration that was refused (bad configuration) stops the render here
-        }
-        havePrev = alive != 0;
-        set ^= 1;
-        if (++sub.iterations > 100000000ull) { g_err = "render loop did not terminate"; return MI_ERR_HIP; }
-    }
-    if ((rc = JoinDark(sub)) != MI_OK) return rc;   // the last iteration's dark rays are in the counters too
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipStreamSynchronize(sub.darkStream));
-    HarvestDark(sub, 0); HarvestDark(sub, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(&sub.result, sub.ctr, sizeof(DevCounters), hipMemcpyDeviceToHost));
-    sub.stackPushed = sub.stackBeyondLds = 0;
-    for (const DevStats &r : sub.result.stats) { sub.stackPushed += r.stackPushed; sub.stackBeyondLds += r.stackBeyondLds; }
-    return MI_OK;
-}
-
-// One frame (or pass, or shard) into the film and out to the caller: the body shared by mi_pt_render and mi_pt_render_metadata,
-// which differ in pt->metaStrategy and in the DScene the pass sees.
-static int RenderFrame(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *weight_sum, mi_counters *counters) {
-    if (!pt || !rp) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (rp->shard_count < 1 || rp->shard_index < 0 || rp->shard_index >= rp->shard_count) { g_err = "bad shard"; return MI_ERR_INVALID; }
-    {   // sample numbers are ints in the path state (I_SAMPLE) and in the oracle: [sample_begin, sample_begin + spp) stays below 2^31 - 1
-        const long long passSpp = PassSpp(pt, rp);
-        if (rp->sample_begin < 0 || rp->sample_begin > 0x7fffffffll || passSpp > 0x7fffffffll - rp->sample_begin) {
-            g_err = "sample numbers out of range: sample_begin >= 0 and sample_begin + spp <= 2^31 - 1";
-            return MI_ERR_INVALID;
-        }
-    }
-    if (pt->scene.samplerType >= MI_SAMPLER_ZEROTWO &&
-        (rp->sample_begin < 0 || rp->sample_begin + PassSpp(pt, rp) > pt->spp)) {
-        g_err = "a pixel sampler (02sequence / stratified) has tables for samples_per_pixel samples: the pass asks for sample numbers beyond them";
-        return MI_ERR_INVALID;
-    }
-    HIPCHK(hipSetDevice(pt->device));
-    ReadQueueBlocksCap(pt);
-    {   // what this pass lets the kernels leave out (DScene::index32 / storePixelSample)
-        DScene &sc = pt->scene;
-        const unsigned long long lastSample = (unsigned long long)rp->sample_begin + (unsigned long long)PassSpp(pt, rp);
-        sc.index32 = (sc.samplerType == MI_SAMPLER_HALTON && (lastSample + 1ull) * (unsigned long long)std::max(1, sc.sampleStride) < (1ull << 32)) ? 1 : 0;
-        sc.storePixelSample = (sc.samplerType >= MI_SAMPLER_RANDOM || sc.nBands > 1 || (pt->nTextures > 0 && (sc.camera.lens_radius > 0 || sc.camera.animated))) ? 1 : 0;
-    }
-    hipStream_t st = (hipStream_t)rp->stream;
-    if (!(rp->flags & MI_RENDER_ACCUMULATE)) HIPCHK(hipMemsetAsync(pt->film, 0, pt->nPix * 32 * sizeof(float), st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!(rp->flags & MI_RENDER_FILM_ON_DEVICE)) {   // the hand-over's staging before the pools size themselves
-        if (film_sum && !pt->stageSum) HIPCHK(hipMalloc((void **)&pt->stageSum, pt->nPix * 31 * sizeof(float)));
-        if (weight_sum && !pt->stageW) HIPCHK(hipMalloc((void **)&pt->stageW, pt->nPix * sizeof(float)));
-    }
-    const int nSub = (int)pt->subs.size();
-    std::vector<int> rcs(nSub, MI_OK);
-    std::vector<std::string> errs(nSub);
-    const auto t0 = std::chrono::steady_clock::now();
-    {
-        std::vector<std::thread> threads;
-        for (int k = 1; k < nSub; ++k)
-            threads.emplace_back([&, k] { rcs[k] = RenderSub(pt, pt->subs[k], rp, k, nSub); errs[k] = g_err; });
-        rcs[0] = RenderSub(pt, pt->subs[0], rp, 0, nSub);
-        errs[0] = g_err;
-        for (auto &t : threads) t.join();
-    }
-    for (int k = 0; k < nSub; ++k)
-        if (rcs[k] != MI_OK) {
-            // a failed sub-renderer may have left kernels queued: nothing of the caller's may be touched after we return
-            (void)hipDeviceSynchronize();
-            g_err = errs[k];
-            return rcs[k];
-        }
-    HIPCHK(hipDeviceSynchronize());
-    pt->lastSeconds[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    unsigned long long iterations = 0;
-    DevStats c{};
-    for (int i = 1; i < 7; ++i) pt->lastSeconds[i] = 0;
-    for (const SubRenderer &sub : pt->subs) {
-        for (int i = 1; i < 7; ++i) pt->lastSeconds[i] += sub.t[i];
-        iterations += sub.iterations;
-        for (const DevStats &r : sub.result.stats) {
-            c.cameraRays += r.cameraRays; c.regularRays += r.regularRays; c.shadowRays += r.shadowRays;
-            c.totalPaths += r.totalPaths; c.zeroRadiancePaths += r.zeroRadiancePaths; c.pathLengthSum += r.pathLengthSum;
-            c.nodesVisited += r.nodesVisited; c.triTests += r.triTests; c.badSamples += r.badSamples;
-            c.extendNodes += r.extendNodes; c.extendTris += r.extendTris; c.extendRays += r.extendRays;
-        }
-    }
-    if (counters) {
-        *counters = mi_counters{};
-        counters->camera_rays = c.cameraRays; counters->regular_rays = c.regularRays; counters->shadow_rays = c.shadowRays;
-        counters->total_paths = c.totalPaths; counters->zero_radiance_paths = c.zeroRadiancePaths;
-        counters->path_length_sum = c.pathLengthSum; counters->bvh_nodes_visited = c.nodesVisited;
-        counters->tri_tests = c.triTests; counters->bad_samples = c.badSamples;
-        counters->iterations = iterations;
-        counters->extend_rays = c.extendRays;
-        counters->extend_nodes = c.extendNodes; counters->extend_tri_tests = c.extendTris;
-        counters->launches[0] = counters->launches[1] = counters->launches[2] = iterations;
-    }
-    if (film_sum || weight_sum) {
-        const bool onDev = (rp->flags & MI_RENDER_FILM_ON_DEVICE) != 0;
-        float *dSum = nullptr, *dW = nullptr;
-        if (onDev) { dSum = film_sum; dW = weight_sum; }
-        else {   // staging for the host hand-over: allocated once per renderer (above), freed by mi_pt_destroy
-            if (film_sum) dSum = pt->stageSum;
-            if (weight_sum) dW = pt->stageW;
-        }
-        size_t total = pt->nPix * 32;
-        hipLaunchKernelGGL(k_film_split, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pt->film, dSum, dW, pt->nPix);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-        if (!onDev) {
-            if (film_sum) HIPCHK(hipMemcpy(film_sum, dSum, pt->nPix * 31 * sizeof(float), hipMemcpyDeviceToHost));
-            if (weight_sum) HIPCHK(hipMemcpy(weight_sum, dW, pt->nPix * sizeof(float), hipMemcpyDeviceToHost));
-        }
-    }
-    return MI_OK;
-}
-
-int mi_pt_render(mi_pt *pt, const mi_render_params *rp, float *film_sum, float *weight_sum, mi_counters *counters) {
-    return RenderFrame(pt, rp, film_sum, weight_sum, counters);
-}
-
-int mi_pt_render_metadata(mi_pt *pt, const mi_render_params *rp, int strategy, float *film_sum, float *weight_sum, mi_counters *counters) {
-    if (!pt || !rp) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (strategy < MI_METADATA_DEPTH || strategy > MI_METADATA_COORDINATES) { g_err = "mi_pt_render_metadata: unknown strategy"; return MI_ERR_INVALID; }
-    if (pt->primMetaHost.size() != pt->scene.nPrims) { g_err = "mi_pt_render_metadata: the scene description came without prim_meta"; return MI_ERR_INVALID; }
-    HIPCHK(hipSetDevice(pt->device));
-    if (!pt->primMeta) {   // the first metadata pass of this renderer
-        const int rc = Upload(pt, pt->primMetaHost.data(), pt->primMetaHost.size(), &pt->primMeta);
-        if (rc != MI_OK) { pt->primMeta = nullptr; return rc; }
-    }
-    // the pass's own view of the scene, as mi_pt_debug_path takes one: no depth limit ends a hit before the commit
-    // (EndsUnshaded), one ray per camera sample whatever "spectralpath" asks for
-    SceneViewGuard restore{pt};
-    pt->scene.maxDepth = 255;
-    pt->scene.nBands = 1;
-    pt->scene.bandDelta = MI_NSPEC;
-    pt->scene.ignoreRayWeight = 1;   // MetadataIntegrator::IgnoreRayWeight (metadata.h:64): a vignetted sample adds zeros with weight 1
-    pt->metaStrategy = strategy;
-    return RenderFrame(pt, rp, film_sum, weight_sum, counters);
-}
-
-int mi_pt_device_film(mi_pt *pt, void **dev_ptr, uint64_t *n_floats) {
-    if (!pt || !dev_ptr || !n_floats) { g_err = "null argument"; return MI_ERR_INVALID; }
-    *dev_ptr = pt->film;
-    *n_floats = pt->nPix * 32;
-    return MI_OK;
-}
-
-int mi_pt_pool_info(mi_pt *pt, uint64_t *slots, uint64_t *bytes) {
-    if (!pt || !slots || !bytes) { g_err = "null argument"; return MI_ERR_INVALID; }
-    *slots = 0; *bytes = 0;
-    for (const SubRenderer &sub : pt->subs) { *slots += sub.pool.n; *bytes += sub.poolBytes; }
-    return MI_OK;
-}
-
-int mi_pt_last_timings(mi_pt *pt, double *seconds, int n) {
-    if (!pt || !seconds) { g_err = "null argument"; return MI_ERR_INVALID; }
-    for (int i = 0; i < n && i < 8; ++i) seconds[i] = pt->lastSeconds[i];
-    return MI_OK;
-}
-
-int mi_pt_texture_lookup(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *rgb) {
-    if (!pt || !queries || !rgb) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
-    if (pt->textureTypes[tex] != MI_TEX_IMAGEMAP) { g_err = "mi_pt_texture_lookup: not an image texture"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    return RunProbe(pt->device, queries, (size_t)n * 6 * sizeof(float), rgb, (size_t)n * 3 * sizeof(float), [&](void *dq, void *dout) {
-        hipLaunchKernelGGL(k_texture_lookup, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, tex, (float *)dq, n, (float *)dout);
-    });
-}
-
-int mi_pt_texture_probe(mi_pt *pt, int32_t tex, uint32_t n, const float *queries, float *out) {
-    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
-    if (!MI_TEX_IS_NOISE(pt->textureTypes[tex])) { g_err = "mi_pt_texture_probe: not a noise texture"; return MI_ERR_INVALID; }
-    if (n > (1u << 24)) { g_err = "mi_pt_texture_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    return RunProbe(pt->device, queries, (size_t)n * 9 * sizeof(float), out, (size_t)n * sizeof(float), [&](void *dq, void *dout) {
-        hipLaunchKernelGGL(k_texture_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)tex, (float *)dq, n, (float *)dout);
-    });
-}
-
-int mi_pt_texture_eval_probe(mi_pt *pt, int32_t tex, int32_t mode, uint32_t n, const float *queries, float *out) {
-    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (tex < 0 || (uint32_t)tex >= pt->nTextures) { g_err = "texture index out of range"; return MI_ERR_INVALID; }
-    if (mode < 0 || mode > 1) { g_err = "mi_pt_texture_eval_probe: mode must be 0 or 1"; return MI_ERR_INVALID; }
-    if (mode == 0 && !MI_TEX_HAS_MAPPING2D(pt->textureTypes[tex])) { g_err = "mi_pt_texture_eval_probe: the record has no 2-D mapping"; return MI_ERR_INVALID; }
-    if (n > (1u << 24)) { g_err = "mi_pt_texture_eval_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    const size_t nOut = mode == 0 ? 6 : MI_NSPEC;
-    return RunProbe(pt->device, queries, (size_t)n * MI_TEXTURE_EVAL_QUERY_FLOATS * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
-        hipLaunchKernelGGL(k_texture_eval_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)tex, (int)mode, (float *)dq, n, (float *)dout);
-    });
-}
-
-int mi_pt_shape_probe(mi_pt *pt, int32_t quadric, int32_t mode, uint32_t n, const float *queries, float *out) {
-    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (quadric < 0 || (uint32_t)quadric >= pt->nQuadrics) { g_err = "mi_pt_shape_probe: quadric index out of range"; return MI_ERR_INVALID; }
-    if (mode < 0 || mode > 2) { g_err = "mi_pt_shape_probe: mode must be 0, 1 or 2"; return MI_ERR_INVALID; }
-    if (n > (1u << 24)) { g_err = "mi_pt_shape_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    const size_t nIn = mode == 0 ? 7 : (mode == 1 ? 5 : 6);
-    const size_t nOut = mode == 0 ? MI_SHAPE_PROBE_HIT_FLOATS : (mode == 1 ? MI_SHAPE_PROBE_SAMPLE_FLOATS : 1);
-    return RunProbe(pt->device, queries, (size_t)n * nIn * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
-        hipLaunchKernelGGL(k_shape_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)quadric, (int)mode, (float *)dq, n, (float *)dout);
-    });
-}
-
-int mi_pt_light_probe(mi_pt *pt, int32_t light, int32_t mode, uint32_t n, const float *queries, float *out) {
-    if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (light < 0 || (size_t)light >= pt->lightTypes.size()) { g_err = "mi_pt_light_probe: light index out of range"; return MI_ERR_INVALID; }
-    if (mode < 0 || mode > 2) { g_err = "mi_pt_light_probe: mode must be 0, 1 or 2"; return MI_ERR_INVALID; }
-    const int type = pt->lightTypes[light];
-    const bool delta = type == MI_LIGHT_POINT || type == MI_LIGHT_DISTANT || type == MI_LIGHT_SPOT || type == MI_LIGHT_PROJECTION;
-    if (mode == 2 && delta) { g_err = "mi_pt_light_probe: mode 2 (Le / L) on a delta light"; return MI_ERR_INVALID; }
-    if (n > (1u << 24)) { g_err = "mi_pt_light_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    const size_t nIn = mode == 0 ? 8 : (mode == 1 ? 9 : (type == MI_LIGHT_INFINITE ? 3 : 6));
-    const size_t nOut = mode == 0 ? MI_LIGHT_PROBE_SAMPLE_FLOATS : (mode == 1 ? 1 : MI_NSPEC);
-    return RunProbe(pt->device, queries, (size_t)n * nIn * sizeof(float), out, (size_t)n * nOut * sizeof(float), [&](void *dq, void *dout) {
-        hipLaunchKernelGGL(k_light_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)light, (int)mode, (float *)dq, n, (float *)dout);
-    });
-}
-
-int mi_pt_sampler_probe(mi_pt *pt, int32_t group, uint32_t n, const uint64_t *indices, const int32_t *first_dims, float *out) {
-    if (!pt || !indices || !first_dims || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (group != 0 && group != 1 && group != 2 && group != 5) { g_err = "mi_pt_sampler_probe: group must be 0, 1, 2 or 5"; return MI_ERR_INVALID; }
-    if (n > (1u << 24)) { g_err = "mi_pt_sampler_probe: more than 2^24 queries"; return MI_ERR_INVALID; }
-    const int count = group == 0 ? 1 : group;
-    std::vector<uint64_t> q(2 * (size_t)n);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (first_dims[i] < 2 || first_dims[i] + count > pt->samplerDims) { g_err = "mi_pt_sampler_probe: dimensions outside [2, n_dims)"; return MI_ERR_INVALID; }
-        if (group != 0 && (indices[i] >> 32)) { g_err = "mi_pt_sampler_probe: the grouped routines take 32-bit indices"; return MI_ERR_INVALID; }
-        q[2 * (size_t)i] = indices[i];
-        q[2 * (size_t)i + 1] = (uint64_t)first_dims[i];
-    }
-    if (n == 0) return MI_OK;
-    return RunProbe(pt->device, q.data(), q.size() * sizeof(uint64_t), out, (size_t)n * count * sizeof(float), [&](void *dq, void *dout) {
-        hipLaunchKernelGGL(k_sampler_probe, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (int)group, (const uint64_t *)dq, n, (float *)dout);
-    });
-}
-
-int mi_pt_bsdf_probe(mi_pt *pt, int32_t material, int32_t instance, int32_t mode, int32_t form, int32_t flags, uint32_t n, const float *queries, float *out) {
+extern "C" int mi_pt_bsdf_probe(mi_pt *pt, int32_t material, int32_t instance, int32_t mode, int32_t form, int32_t flags, uint32_t n, const float *queries, float *out) {
     if (!pt || !queries || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
     if (material < 0 || (size_t)material >= pt->materialLobes.size()) { g_err = "mi_pt_bsdf_probe: material index out of range"; return MI_ERR_INVALID; }
     if (instance < 0 || instance >= N_SHADE_INSTANCES) { g_err = "mi_pt_bsdf_probe: instance index out of range"; return MI_ERR_INVALID; }
@@ -5659,335 +3871,36 @@ int mi_pt_bsdf_probe(mi_pt *pt, int32_t material, int32_t instance, int32_t mode
     });
 }
 
-int mi_pt_bsdf_probe_forms(int32_t instance, uint32_t *forms) {
-    if (!forms) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (instance < 0 || instance >= N_SHADE_INSTANCES) { g_err = "mi_pt_bsdf_probe_forms: instance index out of range"; return MI_ERR_INVALID; }
-    *forms = BsdfProbeForms(kShadeInstances[instance].nl, kShadeInstances[instance].tm);
-    if (*forms == 0u) { g_err = "mi_pt_bsdf_probe_forms: the instance has no row in MIPT_BSDF_PROBE_ROWS"; return MI_ERR_INVALID; }
-    return MI_OK;
+// The k_trav instance of a ray class for the scene. Scenes with object instances always have the wide-4 records
+// (BuildBvhTables) and never MODE 3 (misAny is 0 for them): three instances serve them.
+template <int MODE>
+static SceneKernel TravKernel(const mi_pt *pt) {
+    if (pt->hasInstances)   // (never asked for MODE 3 or 4)
+        return pt->scene.motions ? k_trav<MODE >= 3 ? 2 : MODE, true, 4, true, true> : k_trav<MODE >= 3 ? 2 : MODE, true, 4, true>;
+    const bool w4 = pt->scene.bvhWidth == 4;
+    if (pt->hasAlphaMasks) return w4 ? k_trav<MODE, true, 4> : k_trav<MODE, true, 2>;
+    return w4 ? k_trav<MODE, false, 4> : k_trav<MODE, false, 2>;
+}
+SceneKernel TravKernelOf(const mi_pt *pt, int mode) {
+    return mode == 0 ? TravKernel<0>(pt) : mode == 1 ? TravKernel<1>(pt) : mode == 3 ? TravKernel<3>(pt) : mode == 4 ? TravKernel<4>(pt) : TravKernel<2>(pt);
 }
 
-int mi_pt_camera_rays(mi_pt *pt, const int32_t *samples, uint32_t n, float *out) {
-    if (!pt || !samples || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (n > (1u << 24)) { g_err = "mi_pt_camera_rays: more than 2^24 samples"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    const DScene &s = pt->scene;
-    if (s.cameraType != MI_CAMERA_PERSPECTIVE) {   // the lens camera's ray at 550 nm (band 0) or an opt-in camera's, in this call's layout
-        std::vector<float> ex((size_t)n * MI_CAMERA_RAY_EX_FLOATS);
-        const int rc = mi_pt_camera_rays_ex(pt, samples, n, 0, ex.data());
-        if (rc != MI_OK) return rc;
-        for (uint32_t i = 0; i < n; ++i) memcpy(out + 8 * (size_t)i, ex.data() + (size_t)i * MI_CAMERA_RAY_EX_FLOATS, 8 * sizeof(float));
-        return MI_OK;
-    }
-    if (const int rc = CheckCameraSamples(pt, samples, n, "mi_pt_camera_rays")) return rc;
-    return RunProbe(pt->device, samples, (size_t)n * 3 * sizeof(int32_t), out, (size_t)n * 8 * sizeof(float), [&](void *ds, void *dout) {
-        hipLaunchKernelGGL((s.camera.animated ? k_camera_rays<true> : k_camera_rays<false>), ProbeGrid(n), dim3(BLOCK), 0, 0, s, (int32_t *)ds, n, (float *)dout);
-    });
+// The resolve kernels of the three ray classes, by [class][instanced].
+static const SceneKernel kResolve[3][2] = {{k_resolve_extend<false>, k_resolve_extend<true>},
+                                           {k_resolve_shadow<false>, k_resolve_shadow<true>},
+                                           {k_resolve_mis<false>, k_resolve_mis<true>}};
+SceneKernel ResolveKernelOf(const mi_pt *pt, int mode) { return kResolve[mode][pt->hasInstances ? 1 : 0]; }
+
+OverflowKernel OverflowKernelOf(const mi_pt *pt) {
+    return pt->hasInstances ? (pt->scene.motions ? k_resolve_overflow<true, true> : k_resolve_overflow<true>) : k_resolve_overflow<false>;
 }
-
-int mi_pt_camera_rays_ex(mi_pt *pt, const int32_t *samples, uint32_t n, int32_t band, float *out) {
-    if (!pt || !samples || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (n > (1u << 24)) { g_err = "mi_pt_camera_rays_ex: more than 2^24 samples"; return MI_ERR_INVALID; }
-    const DScene &s = pt->scene;
-    if (band < 0 || band >= std::max(1, s.nBands)) { g_err = "mi_pt_camera_rays_ex: no such band"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    if (const int rc = CheckCameraSamples(pt, samples, n, "mi_pt_camera_rays_ex")) return rc;
-    const bool moving = s.camera.animated != 0;
-    auto kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_PERSPECTIVE> : k_camera_rays_ex<false, MI_CAMERA_PERSPECTIVE>;
-    if (s.cameraType == MI_CAMERA_REALISTIC) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_REALISTIC> : k_camera_rays_ex<false, MI_CAMERA_REALISTIC>;
-    if (s.cameraType == MI_CAMERA_ORTHOGRAPHIC) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_ORTHOGRAPHIC> : k_camera_rays_ex<false, MI_CAMERA_ORTHOGRAPHIC>;
-    if (s.cameraType == MI_CAMERA_ENVIRONMENT) kernel = moving ? k_camera_rays_ex<true, MI_CAMERA_ENVIRONMENT> : k_camera_rays_ex<false, MI_CAMERA_ENVIRONMENT>;
-    return RunProbe(pt->device, samples, (size_t)n * 3 * sizeof(int32_t), out, (size_t)n * MI_CAMERA_RAY_EX_FLOATS * sizeof(float), [&](void *ds, void *dout) {
-        hipLaunchKernelGGL(kernel, ProbeGrid(n), dim3(BLOCK), 0, 0, s, (int32_t *)ds, n, (int)band, (float *)dout);
-    });
+MetadataKernel MetadataCommitKernelOf(const mi_pt *pt) {
+    return pt->hasInstances ? (pt->scene.motions ? k_commit_metadata<true, true> : k_commit_metadata<true>) : k_commit_metadata<false>;
 }
-
-// Parity tools for the shading plan (include/mi_pt.h): host code only.
-int mi_pt_shade_instances(int32_t *nl, uint32_t *tm, uint32_t capacity, uint32_t *count) {
-    if (!count) { g_err = "null argument"; return MI_ERR_INVALID; }
-    *count = N_SHADE_INSTANCES;
-    if ((nl || tm) && capacity < (uint32_t)N_SHADE_INSTANCES) { g_err = "mi_pt_shade_instances: buffer too small"; return MI_ERR_INVALID; }
-    for (int i = 0; i < N_SHADE_INSTANCES; ++i) {
-        if (nl) nl[i] = kShadeInstances[i].nl;
-        if (tm) tm[i] = kShadeInstances[i].tm;
-    }
-    return MI_OK;
+TraceReadKernel TraceReadKernelOf(const mi_pt *pt) {
+    return pt->hasInstances ? (pt->scene.motions ? k_trace_read<true, true> : k_trace_read<true>) : k_trace_read<false>;
 }
-
-int mi_pt_shade_mask(const char *name, uint32_t *mask) {
-    if (!name || !mask) { g_err = "null argument"; return MI_ERR_INVALID; }
-#define MIPT_MASK_NAME(M_) {#M_, M_}
-    static const struct { const char *name; unsigned mask; } kMasks[] = {
-        MIPT_MASK_NAME(TM_DIFFUSE), MIPT_MASK_NAME(TM_PLASTIC), MIPT_MASK_NAME(TM_GLASS), MIPT_MASK_NAME(TM_UBER), MIPT_MASK_NAME(TM_DISNEY),
-        MIPT_MASK_NAME(TM_GENERIC), MIPT_MASK_NAME(TM_FULL), MIPT_MASK_NAME(TM_ALL), MIPT_MASK_NAME(TM_SCALED), MIPT_MASK_NAME(TM_TEXTURED),
-        MIPT_MASK_NAME(TM_INSTANCES), MIPT_MASK_NAME(TM_SAMPLERS), MIPT_MASK_NAME(TM_LIGHTS_ALL), MIPT_MASK_NAME(TM_LIGHTS_NO_ENV)};
-#undef MIPT_MASK_NAME
-    for (const auto &m : kMasks)
-        if (strcmp(m.name, name) == 0) { *mask = m.mask; return MI_OK; }
-    g_err = std::string("mi_pt_shade_mask: no mask named ") + name;
-    return MI_ERR_INVALID;
-}
-
-int mi_pt_shade_grid(const uint32_t *counts, uint32_t n_counts, uint32_t classes, uint32_t *blocks) {
-    if (!counts || !blocks) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (n_counts != (uint32_t)MAX_CLASSES) { g_err = "mi_pt_shade_grid: one count per shading class, 16"; return MI_ERR_INVALID; }
-    const unsigned long long n = ShadeGridBlocks(counts, classes);
-    if (n > 0xffffffffull) { g_err = "mi_pt_shade_grid: more than 2^32 - 1 blocks"; return MI_ERR_INVALID; }
-    *blocks = (uint32_t)n;
-    return MI_OK;
-}
-
-int mi_pt_shade_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *blocks) {
-    if (!pt || !launches || !blocks) { g_err = "null argument"; return MI_ERR_INVALID; }
-    *launches = 0; *blocks = 0;
-    for (const SubRenderer &sub : pt->subs) { *launches += sub.shadeLaunches; *blocks += sub.shadeBlocks; }
-    return MI_OK;
-}
-
-int mi_pt_dark_launch_stats(mi_pt *pt, uint64_t *launches, uint64_t *entries, uint64_t *rays, uint64_t *resolve_skipped) {
-    if (!pt || !launches || !entries || !rays || !resolve_skipped) { g_err = "null argument"; return MI_ERR_INVALID; }
-    *launches = 0; *entries = 0; *rays = 0; *resolve_skipped = 0;
-    for (const SubRenderer &sub : pt->subs) {
-        *launches += sub.darkLaunches;
-        for (const DevStats &r : sub.result.stats) { *entries += r.darkEntries; *rays += r.darkRays; *resolve_skipped += r.misDarkSeen; }
-    }
-    return MI_OK;
-}
-
-int mi_pt_trav_stack_stats(mi_pt *pt, uint64_t out[2]) {
-    if (!pt || !out) { g_err = "null argument"; return MI_ERR_INVALID; }
-    out[0] = out[1] = 0;
-    for (const SubRenderer &sub : pt->subs) { out[0] += sub.stackPushed; out[1] += sub.stackBeyondLds; }
-    return MI_OK;
-}
-
-int mi_pt_shade_plan(const mi_scene_desc *d, int32_t *material_class, uint32_t material_capacity, int32_t *class_id,
-                     int32_t *class_instance, int32_t *class_lobes, uint32_t *class_types, uint32_t class_capacity,
-                     uint32_t *n_classes, uint32_t *hot) {
-    if (!d) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (d->abi_version != MI_ABI_VERSION) { g_err = "mi_scene_desc ABI version mismatch"; return MI_ERR_INVALID; }
-    int rc = CheckSceneDesc(d);
-    if (rc != MI_OK) return rc;
-    ShadingClasses sc;
-    if ((rc = PlanShading(d, sc)) != MI_OK) return rc;
-    if (material_class) {
-        if (material_capacity < d->n_materials) { g_err = "mi_pt_shade_plan: material buffer too small"; return MI_ERR_INVALID; }
-        for (uint32_t i = 0; i < d->n_materials; ++i) material_class[i] = sc.matClass[i];
-    }
-    if ((class_id || class_instance || class_lobes || class_types) && class_capacity < (uint32_t)MAX_CLASSES) {
-        g_err = "mi_pt_shade_plan: class buffers too small"; return MI_ERR_INVALID;
-    }
-    uint32_t n = 0;
-    for (int c = 0; c < MAX_CLASSES; ++c) {
-        if (!((sc.classMask >> c) & 1u)) continue;
-        if (class_id) class_id[n] = c;
-        if (class_instance) class_instance[n] = sc.classInstance[c];
-        if (class_lobes) class_lobes[n] = sc.classLobes[c];
-        if (class_types) class_types[n] = sc.classTypes[c];
-        ++n;
-    }
-    if (n_classes) *n_classes = n;
-    if (hot) *hot = sc.hot;
-    return MI_OK;
-}
-
-int mi_pt_light_distribution(mi_pt *pt, float *func, float *func_int, uint64_t capacity_voxels) {
-    if (!pt) { g_err = "null argument"; return MI_ERR_INVALID; }
-    const DScene &s = pt->scene;
-    if (s.ldType != MI_LD_SPATIAL || s.nLights == 0) { g_err = "mi_pt_light_distribution: the scene has no spatial light distribution"; return MI_ERR_INVALID; }
-    const size_t nVox = (size_t)s.nVoxels[0] * s.nVoxels[1] * s.nVoxels[2];
-    if (capacity_voxels < nVox) { g_err = "mi_pt_light_distribution: buffer too small"; return MI_ERR_INVALID; }
-    HIPCHK(hipSetDevice(pt->device));
-    if (func) HIPCHK(hipMemcpy(func, s.ldFunc, nVox * s.nLights * sizeof(float), hipMemcpyDeviceToHost));
-    if (func_int) HIPCHK(hipMemcpy(func_int, s.ldFuncInt, nVox * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
-}
-
-// Parity tool: one camera sample through the wavefront pipeline with a 256-slot pool, the path's state copied out at the
-// kernel boundaries of every iteration (layout of a record: include/mi_pt.h, MI_PATH_RECORD_FLOATS).
-int mi_pt_debug_path(mi_pt *pt, int32_t px, int32_t py, int64_t sample, int32_t max_records, float *records, int32_t *n_records) {
-    if (!pt || !records || !n_records || max_records < 1) { g_err = "null argument"; return MI_ERR_INVALID; }
-    *n_records = 0;
-    HIPCHK(hipSetDevice(pt->device));
-    ReadQueueBlocksCap(pt);
-    SceneViewGuard restore{pt};
-    DScene &s = pt->scene;
-    if (px < s.sampleBounds[0] || px >= s.sampleBounds[2] || py < s.sampleBounds[1] || py >= s.sampleBounds[3]) { g_err = "pixel outside the sample bounds"; return MI_ERR_INVALID; }
-    s.pixelBounds[0] = px; s.pixelBounds[1] = py; s.pixelBounds[2] = px + 1; s.pixelBounds[3] = py + 1;
-    s.index32 = 0; s.storePixelSample = 1;
-    SubRenderer &sub = pt->subs[0];
-    hipStream_t st = sub.stream;
-    // the pixel's tile alone: a shard of its own among as many shards as there are tiles, one sample per pixel (256 work items)
-    const int tile = ((py - s.sampleBounds[1]) / 16) * TilesAlong(s, 0) + (px - s.sampleBounds[0]) / 16;
-    const WorkDesc wd = PlanWork(s, tile, TilesAlong(s, 0) * TilesAlong(s, 1), 1, sample);
-    const uint32_t poolN = BLOCK;
-    int rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
-    if (rc != MI_OK) return rc;
-    HIPCHK(hipMemsetAsync(sub.pool.i + (size_t)I_FLAGS * poolN, 0, (size_t)poolN * sizeof(int), st));
-    HIPCHK(hipMemsetAsync(sub.ctr, 0, sizeof(DevCounters), st));
-    HIPCHK(hipMemsetAsync(pt->film, 0, pt->nPix * 32 * sizeof(float), st));
-    const dim3 grid(1), block(BLOCK), travGrid(1);
-    const Pool &pool = sub.pool;
-    std::vector<int> flags(poolN);
-    auto F4 = [&](int plane, uint32_t slot, float *dst) { return hipMemcpy(dst, pool.r + pool.RecordIndex(plane, slot), 16, hipMemcpyDeviceToHost); };
-    auto I1 = [&](int plane, uint32_t slot, int *dst) { return hipMemcpy(dst, pool.i + pool.ScalarIndex(plane, slot), 4, hipMemcpyDeviceToHost); };
-    auto Spec = [&](int set, uint32_t slot, float *dst31) {
-        float line[32];
-        hipError_t e = hipMemcpy(line, pool.q + pool.QuadIndex(set, slot), 128, hipMemcpyDeviceToHost);
-        memcpy(dst31, line, 31 * sizeof(float));
-        return e;
-    };
-    int slot = -1;
-    for (int it = 0; it < 4096; ++it) {
-        HIPCHK(hipMemsetAsync(&sub.ctr->alive, 0, ITER_CLEAR_BYTES, st));
-        hipLaunchKernelGGL(GenerateKernelOf(s), grid, block, 0, st, s, sub.pool, pt->film, sub.ctr, wd);
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipMemcpy(flags.data(), pool.i + (size_t)I_FLAGS * poolN, poolN * sizeof(int), hipMemcpyDeviceToHost));
-        slot = -1;
-        for (uint32_t k = 0; k < poolN; ++k) if (flags[k] & F_ALIVE) { slot = (int)k; break; }
-        if (slot < 0) break;
-        if (*n_records >= max_records) break;
-        float *r = records + (size_t)(*n_records) * MI_PATH_RECORD_FLOATS;
-        for (int k = 0; k < MI_PATH_RECORD_FLOATS; ++k) r[k] = 0.f;
-        LaunchTraversal(pt, sub, 0, travGrid);
-        LaunchResolve(pt, sub, 0, grid);
-        HIPCHK(hipStreamSynchronize(st));
-        int bounces = 0, prim = -1, dim = 0;
-        float ray0[4], ray1[4], hit[4];
-        int word0 = 0;
-        HIPCHK(I1(I_FLAGS, slot, &word0)); HIPCHK(I1(I_HITPRIM, slot, &prim));
-        bounces = (word0 >> BOUNCE_SHIFT) & 0xff;
-        if (s.samplerType >= MI_SAMPLER_ZEROTWO) HIPCHK(I1(I_DIM, slot, &dim)); else dim = (int)((unsigned)word0 >> DIM_SHIFT);
-        HIPCHK(F4(R_RAY0, slot, ray0)); HIPCHK(F4(R_RAY1, slot, ray1)); HIPCHK(F4(R_HIT, slot, hit));
-        r[0] = (float)bounces; r[1] = (float)prim; r[2] = (float)dim;
-        r[4] = ray0[0]; r[5] = ray0[1]; r[6] = ray0[2]; r[7] = prim >= 0 ? hit[0] : ray0[3];
-        r[8] = ray1[0]; r[9] = ray1[1]; r[10] = ray1[2]; r[11] = ray1[3];
-        if ((rc = LaunchShade(pt, sub, grid)) != MI_OK) return rc;
-        LaunchTraversal(pt, sub, 1, travGrid);
-        LaunchResolve(pt, sub, 1, grid);
-        LaunchTraversal(pt, sub, 2, travGrid);
-        LaunchResolve(pt, sub, 2, grid);
-        if (s.misAny && (rc = LaunchDarkInLine(pt, sub, travGrid)) != MI_OK) return rc;
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        int fl = 0;
-        HIPCHK(I1(I_FLAGS, slot, &fl));
-        if (s.samplerType >= MI_SAMPLER_ZEROTWO) HIPCHK(I1(I_DIM, slot, &dim)); else dim = (int)((unsigned)fl >> DIM_SHIFT);
-        HIPCHK(F4(R_RAY0, slot, ray0)); HIPCHK(F4(R_RAY1, slot, ray1));
-        r[3] = (fl & F_ALIVE) ? 0.f : 1.f;
-        r[12] = ray0[0]; r[13] = ray0[1]; r[14] = ray0[2]; r[15] = (float)dim;
-        r[16] = ray1[0]; r[17] = ray1[1]; r[18] = ray1[2]; r[19] = ray1[3];
-        if (fl & F_BETA_ONE) for (int k = 0; k < 31; ++k) r[20 + k] = 1.f;
-        else HIPCHK(Spec(Q_BETA, slot, r + 20));
-        if (!(fl & F_L_ZERO)) HIPCHK(Spec((fl & F_L_IN_B) ? Q_LB : Q_L, slot, r + 51));
-        ++*n_records;
-    }
-    ReleasePool(sub);   // the next render sizes its own
-    HIPCHK(hipMemset(pt->film, 0, pt->nPix * 32 * sizeof(float)));
-    return MI_OK;
-}
-
-static int TraceRays(mi_pt *pt, const float *rays, int stride, uint32_t n, int any_hit, float *hits) {
-    if (!pt || !rays || !hits) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    return RunProbe(pt->device, rays, (size_t)n * stride * sizeof(float), hits, (size_t)n * 4 * sizeof(float), [&](void *dr, void *dh) {
-        hipLaunchKernelGGL(k_trace, ProbeGrid(n), dim3(BLOCK), 0, 0, pt->scene, (float *)dr, n, any_hit, (float *)dh, stride);
-    });
-}
-
-int mi_pt_trace(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits) { return TraceRays(pt, rays, 7, n, any_hit, hits); }
-int mi_pt_trace_timed(mi_pt *pt, const float *rays, uint32_t n, int any_hit, float *hits) { return TraceRays(pt, rays, 8, n, any_hit, hits); }
-
-int mi_pt_math_probe(int device_ordinal, int op, uint32_t n, const float *x, const float *y, float *out) {
-    if (!x || !y || !out || op < 0 || op > 6) { g_err = "mi_pt_math_probe: bad argument"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || device_ordinal < 0 || device_ordinal >= nDev) { g_err = "no HIP device available (this path has no CPU fallback)"; return MI_ERR_NO_DEVICE; }
-    HIPCHK(hipSetDevice(device_ordinal));
-    DevBuf dx, dy, dout;   // (two inputs: not RunProbe's shape)
-    HIPCHK(dx.alloc((size_t)n * 2 * sizeof(float)));
-    HIPCHK(dy.alloc((size_t)n * 2 * sizeof(float)));
-    HIPCHK(dout.alloc((size_t)n * 3 * sizeof(float)));
-    HIPCHK(hipMemcpy(dx.p, x, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dy.p, y, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_math_probe, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, 0, op, n, dx.as<float>(), dy.as<float>(), dout.as<float>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return MI_OK;
-}
-
-static int TraceWavefront(mi_pt *pt, const float *rays, int stride, uint32_t n, int mode, float *hits, float *extra) {
-    if (!pt || !rays || !hits) { g_err = "null argument"; return MI_ERR_INVALID; }
-    if (mode < 0 || mode > 3) { g_err = "mi_pt_trace_wavefront: mode must be 0 (path rays), 1 (shadow rays), 2 (MIS rays) or 3 (MIS rays as visibility queries)"; return MI_ERR_INVALID; }
-    if (mode == 3 && !pt->scene.misAny) { g_err = "mi_pt_trace_wavefront: mode 3 needs a scene without instances and without an alpha mask on an emitter's mesh (others keep the closest-hit form of the MIS rays)"; return MI_ERR_INVALID; }
-    if (n == 0) return MI_OK;
-    if (n > (1u << 24)) { g_err = "mi_pt_trace_wavefront: at most 16M rays per call"; return MI_ERR_INVALID; }
-    // the kernels fix what the render fixes: a shadow ray ends at 1 - ShadowEpsilon (Interaction::SpawnRayTo), a BSDF-sampled
-    // ray never ends (SpawnRay)
-    for (uint32_t i = 0; i < n && mode == 3; ++i)
-        if (!(rays[(size_t)i * stride + 6] > 0)) { g_err = "mi_pt_trace_wavefront: mode 3 rays carry the end of the emitter's span, tMax > 0"; return MI_ERR_INVALID; }
-    for (uint32_t i = 0; i < n && (mode == 1 || mode == 2); ++i) {
-        const float tMax = rays[(size_t)i * stride + 6];
-        if (mode == 1 ? tMax != 1 - kShadowEpsilon : !std::isinf(tMax) || tMax < 0) {
-            g_err = mode == 1 ? "mi_pt_trace_wavefront: shadow rays (mode 1) carry tMax = 1 - 0.0001f" : "mi_pt_trace_wavefront: MIS rays (mode 2) carry tMax = +infinity";
-            return MI_ERR_INVALID;
-        }
-    }
-    HIPCHK(hipSetDevice(pt->device));
-    ReadQueueBlocksCap(pt);
-    SubRenderer &sub = pt->subs[0];
-    hipStream_t st = sub.stream;
-    const DScene &s = pt->scene;
-    const uint32_t poolN = (n + SLOT_CHUNKS * BLOCK - 1) / (SLOT_CHUNKS * BLOCK) * (SLOT_CHUNKS * BLOCK);
-    int rc = EnsurePool(sub, poolN, QuadPlanes(s), FloatPlanes(s));
-    if (rc != MI_OK) return rc;
-    struct PoolGuard { SubRenderer &sub; ~PoolGuard() { ReleasePool(sub); } } guard{sub};   // the next render sizes its own
-    DevBuf dr, dh, dx;
-    HIPCHK(dr.alloc((size_t)n * stride * sizeof(float)));
-    HIPCHK(dh.alloc((size_t)n * 4 * sizeof(float)));
-    HIPCHK(dx.alloc((size_t)n * 4 * sizeof(float)));
-    HIPCHK(hipMemcpy(dr.p, rays, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(sub.ctr, 0, sizeof(DevCounters), st));
-    const dim3 grid(poolN / BLOCK), block(BLOCK);
-    const dim3 chunkGrid(grid.x / SLOT_CHUNKS);
-    const dim3 travGrid(std::min<unsigned>(grid.x, (unsigned)pt->numCUs * TRAV_BLOCKS_PER_CU));
-    hipLaunchKernelGGL(k_trace_load, grid, block, 0, st, sub.pool, sub.ctr, dr.as<float>(), n, mode, s.motions ? s.timePlane : -1, s.camera.shutter_open, stride);
-    LaunchTraversal(pt, sub, mode, travGrid, true);   // (mode 2: the closest-hit kernel, whose records this call returns)
-    hipLaunchKernelGGL(k_trace_raw, grid, block, 0, st, sub.pool, n, mode, dx.as<float>());
-    if (mode < 2) LaunchResolve(pt, sub, mode, mode == 0 ? chunkGrid : grid);   // (modes 2 and 3: k_trace_read resolves the hit)
-    hipLaunchKernelGGL((pt->hasInstances ? (s.motions ? k_trace_read<true, true> : k_trace_read<true>) : k_trace_read<false>), grid, block, 0, st, s, sub.pool, n, mode, dh.as<float>(), dx.as<float>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(hits, dh.p, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    if (extra) HIPCHK(hipMemcpy(extra, dx.p, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<DevStats> stripes(STAT_STRIPES);   // (the stack statistics of this call; the counters of the last render stay as they are)
-    HIPCHK(hipMemcpy(stripes.data(), sub.ctr, sizeof(DevStats) * STAT_STRIPES, hipMemcpyDeviceToHost));
-    for (SubRenderer &other : pt->subs) other.stackPushed = other.stackBeyondLds = 0;   // (the call ran on the first sub-renderer alone)
-    for (const DevStats &r : stripes) { sub.stackPushed += r.stackPushed; sub.stackBeyondLds += r.stackBeyondLds; }
-    return MI_OK;
-}
-int mi_pt_trace_wavefront(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra) { return TraceWavefront(pt, rays, 7, n, mode, hits, extra); }
-int mi_pt_trace_wavefront_timed(mi_pt *pt, const float *rays, uint32_t n, int mode, float *hits, float *extra) { return TraceWavefront(pt, rays, 8, n, mode, hits, extra); }
-
-void mi_pt_destroy(mi_pt *pt) {
-    if (!pt) return;
-    hipSetDevice(pt->device);
-    hipDeviceSynchronize();
-    for (void *p : pt->allocs) hipFree(p);   // (the film and the sub-renderers' counters among them)
-    if (pt->stageSum) hipFree(pt->stageSum);
-    if (pt->stageW) hipFree(pt->stageW);
-    for (SubRenderer &sub : pt->subs) {
-        ReleasePool(sub);
-        for (int a = 0; a < 2; ++a) for (int b = 0; b < N_EV; ++b) if (sub.evIter[a][b]) hipEventDestroy(sub.evIter[a][b]);
-        if (sub.stream) hipStreamDestroy(sub.stream);
-        // (the hipDeviceSynchronize above has joined the dark stream, after a failed create or render as well)
-        for (hipEvent_t e : {sub.evDarkGo, sub.evDarkDone, sub.evDark[0][0], sub.evDark[0][1], sub.evDark[1][0], sub.evDark[1][1]}) if (e) hipEventDestroy(e);
-        if (sub.darkStream) hipStreamDestroy(sub.darkStream);
-        if (sub.reads) hipHostFree(sub.reads);
-    }
-    delete pt;
-}
-
-}  // extern "C"
 #endif   // MIPT_HAS_MAIN
+
+
+}  // namespace dptk

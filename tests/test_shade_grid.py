@@ -1,7 +1,7 @@
 """The grid of a k_shade launch (mi_pt_shade_grid: host code of the HIP library, no device) against the kernel's prologue.
 
 k_shade finds its work from blockIdx.x alone: it walks the classes of its mask in rising order and subtracts each queue's
-ceil(n / 256) blocks until the index fits (pt_kernels.hip, the head of k_shade). The host sizes the launch from the same 16
+ceil(n / 256) blocks until the index fits (pt_kernels.hip, the head of k_shade). The host (pt_render.hip) sizes the launch from the same 16
 counts, so the two must agree block for block: a grid one block short drops up to 256 vertices of the last class, and
 ceil(sum / 256) instead of the sum of the ceilings drops them whenever two classes each hold a partial block. The prologue
 is restated here in Python and the library's answer is held to it."""
